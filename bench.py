@@ -22,6 +22,10 @@ per artisoptions_*.h: kilonova_lte = BASELINE.json configs[3], nltenebular = con
 classic build.
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the definitions of roofline and cpu_baseline).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step handed its caller: the packets (every field of a
+fixed, seeded sample of them) and the estimators with the event counters, as DIR/<name>.npy (see dump_outputs). The inputs are
+seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -63,6 +67,56 @@ PROFILE_ROUNDS = ("r06", "r05", "r04")  # the newest round that holds the counte
 NCU, NSIMD, CLOCK_GHZ = 256, 1024, 2.4   # MI355X: 256 CUs x 4 SIMDs, 2.4 GHz peak engine clock
 GATHER_INSTR_CLOCKS = 40.0             # CU clocks per 64-lane 16-byte gather instruction out of L2 (profiles/r02/gather_microbench.txt)
 LINE_FILL_CLOCKS = 150.0 / 64          # CU clocks per 128-byte line filled from L2 (profiles/r03/sector_bench.txt)
+DUMP_BYTES = 64_000_000                # --dump-outputs: all files together, headers included
+DUMP_PACKETS = 1 << 16                 # packets in the dumped sample
+DUMP_SEED = 20240601                   # of every sample's indices: the same for every build and run
+
+
+def _sample_index(n: int, k: int) -> np.ndarray:
+    """k sorted indices of [0, n): all of them when k >= n, else a seeded draw that depends on (n, k) alone."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(outdir: str, packets: np.ndarray, est_arrays: dict, stats: np.ndarray) -> dict:
+    """What one timed step computes, as outdir/<name>.npy (float32 where the value is a float32, else float64; integers are
+    exact in float64), DUMP_BYTES at most in all:
+      packet_<field>  every field of the packets at the sample's indices (_sample_index(len(packets), DUMP_PACKETS));
+                      packet_number says which packets they are
+      packet_<field>_set  for em_pos and trueem_pos, whose NaN means "no (true) emission yet" (kpkt.cc:483): 1 where the
+                      packet has the position, 0 where it is NaN (and packet_<field> holds 0 there), so that every file is finite
+      est_<name>      the estimator arrays (abi.Estimators.arrays()), whole where they fit in what the packets leave, else
+                      _sample_index(size, cap) of each (the smallest arrays are whole, the rest share the remaining bytes)
+      stats           the event counters (abi.STAT_NAMES)
+    Returns {name: [elements written, elements computed]}."""
+    os.makedirs(outdir, exist_ok=True)
+    out = {}
+    idx = _sample_index(len(packets), DUMP_PACKETS)
+    sub = packets[idx]
+    for f in abi.PACKET_DTYPE.names:
+        a = np.array(sub[f], np.float32 if sub[f].dtype == np.float32 else np.float64)
+        if f in ("em_pos", "trueem_pos"):
+            unset = np.isnan(a)
+            if not np.array_equal(unset.any(axis=1), unset.all(axis=1)):
+                raise RuntimeError(f"dump_outputs: packet_{f} has positions that are NaN in some coordinates only")
+            a[unset] = 0.0
+            out[f"packet_{f}_set"] = ((~unset[:, 0]).astype(np.float64), len(packets))
+        out["packet_" + f] = (a, packets[f].size)
+    out["stats"] = (np.asarray(stats, dtype=np.float64), stats.size)
+    left = (DUMP_BYTES - sum(a.nbytes for a, _ in out.values()) - 1024 * (len(out) + len(est_arrays))) // 8  # (1 KB per .npy header)
+    arrays = sorted(((k, np.ravel(v)) for k, v in est_arrays.items()), key=lambda kv: (kv[1].size, kv[0]))
+    for i, (k, v) in enumerate(arrays):
+        cap = min(v.size, left // (len(arrays) - i))
+        left -= cap
+        out["est_" + k] = (np.asarray(v[_sample_index(v.size, cap)], dtype=np.float64), v.size)
+    bad = [name for name, (a, _) in out.items() if not np.isfinite(a).all()]
+    if bad:
+        raise RuntimeError(f"dump_outputs: the step computed values that are not finite in {', '.join(bad)}")
+    for name, (a, _) in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    assert sum(os.path.getsize(os.path.join(outdir, name + ".npy")) for name in out) <= DUMP_BYTES
+    return {name: [a.size, n] for name, (a, n) in out.items()}
 
 
 class _CudaArrayView:
@@ -173,7 +227,12 @@ def main():
                          "BASELINE.json configs[3]'s text; the reference's classic CI set-up with virtual packets)")
     ap.add_argument("--t-days", type=float, default=20.0,
                     help="time of the timestep (a VPKT_ON build traces virtual packets inside its spectra window only: synth.vpkt_config 3-8 d)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's packets (a seeded sample), estimators and event counters as DIR/<name>.npy "
+                         "(rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # start the ranks ourselves: fresh child processes, nothing in this process has touched the GPU
@@ -322,6 +381,10 @@ def main():
     stats = np.zeros(abi.NSTATS, dtype=np.int64)
     est.c.stats = stats.ctypes.data_as(C.POINTER(C.c_int64))
     eng.download_estimators(est)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        eng.download_packets(pk)  # the population as the last timed step left it (pk, its input, is not needed any more)
+        dumped = dump_outputs(args.dump_outputs, pk, est.arrays(), stats)
     steps_rank = int(stats[abi.STAT_X_RPKT_STEPS] + stats[abi.STAT_X_KPKT_STEPS])
     steps_all = steps_rank
     if world > 1:
@@ -502,6 +565,9 @@ def main():
         out["kernel_ms_by_kind_last_step"] = eng.last_kernel_ms_by_kind()
         if os.environ.get("ARTIS_BENCH_VERBOSE"):
             print({abi.STAT_NAMES[i]: int(stats[i]) for i in range(abi.NSTATS) if stats[i]}, file=sys.stderr)
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": len(dumped),
+                                   "sampled": sorted(k for k, (w, n) in dumped.items() if w < n)}
         if baseline is not None:
             out["cpu_baseline"] = baseline
             out["gpu_over_cpu_baseline"] = value / baseline["value"]
