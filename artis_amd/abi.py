@@ -419,3 +419,24 @@ def seed_packet_rng(packets: np.ndarray, seed_base: int) -> None:
             r = (r ^ (r >> np.uint32(15))) * np.uint32(0x735A2D97)
             out[:, i] = r ^ (r >> np.uint32(15))
     packets["rngstate"] = out
+
+
+# ---- emergent spectra and light curves (include/artis_amd.h artis_spectra_config / artis_spectra)
+SPEC_MNUBINS = 1000
+SPEC_MABINS = 100
+SPEC_ALL_DIRBINS = -2
+SPEC_OUTPUTS = ["lum", "lumcmf", "flux", "flux_q", "flux_u", "emission", "emission_q", "emission_u", "trueemission", "absorption",
+                "absorption_q", "absorption_u", "gamma_lum", "gamma_lumcmf", "gamma_flux"]
+
+
+class SpectraConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("ntimesteps", C.c_int32), ("dirbin", C.c_int32), ("ts_start", _F64P),
+                ("ts_width", _F64P), ("tmin", C.c_double), ("tmax", C.c_double), ("emission_absorption", C.c_int32),
+                ("stokes", C.c_int32), ("gamma", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Spectra(C.Structure):
+    _fields_ = [("struct_size", C.c_int64)] + [(k, _F64P) for k in SPEC_OUTPUTS] + \
+               [(k, _F32P) for k in ("lower_freq", "delta_freq", "gamma_lower_freq", "gamma_delta_freq")] + \
+               [("nescaped_rpkt", C.c_int64), ("nescaped_gamma", C.c_int64)] + \
+               [(k, C.c_int32) for k in ("ntimesteps", "ndirslots", "nelements", "max_nions", "proccount", "reserved")]

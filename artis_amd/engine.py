@@ -54,6 +54,9 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_estimators_download.argtypes = [C.c_void_p, C.c_void_p]
     L.artis_amd_estimators_devptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.artis_amd_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    L.artis_amd_spectra_compute.argtypes = [C.c_void_p, C.POINTER(abi.SpectraConfig), C.c_void_p]
+    L.artis_amd_spectra_devptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.artis_amd_spectra_download.argtypes = [C.c_void_p, C.POINTER(abi.Spectra)]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -76,6 +79,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_options_preset",
     "artis_amd_allreduce_estimators", "artis_amd_comm_unique_id", "artis_amd_comm_init", "artis_amd_comm_count",
     "artis_amd_cache_tiles", "artis_amd_last_tiling", "artis_amd_last_tiling_fills", "artis_amd_last_tiling_parked", "artis_amd_last_pool_resets", "artis_amd_record_tiers", "artis_amd_last_thermal_variants", "artis_amd_last_pool_usage",
+    "artis_amd_spectra_compute", "artis_amd_spectra_devptr", "artis_amd_spectra_download",
 ]
 
 
@@ -138,6 +142,63 @@ class Engine:
         p, n = C.c_void_p(), C.c_int64()
         self._check(self.L.artis_amd_estimators_devptr(self.h, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    # emergent spectra and light curves of the resident packets (include/artis_amd.h artis_amd_spectra_*)
+    def spectra_compute(self, ts_start, ts_width, tmin: float, tmax: float, dirbin: int = -1, emission_absorption: bool = False,
+                        stokes: bool = False, gamma: bool = False, stream: int = 0):
+        starts = np.ascontiguousarray(ts_start, dtype=np.float64)
+        widths = np.ascontiguousarray(ts_width, dtype=np.float64)
+        if starts.shape != widths.shape or starts.ndim != 1:
+            raise EngineError("ts_start and ts_width must be 1-D arrays of one length")
+        cfg = abi.SpectraConfig(struct_size=C.sizeof(abi.SpectraConfig), ntimesteps=len(starts), dirbin=dirbin,
+                                ts_start=starts.ctypes.data_as(C.POINTER(C.c_double)), ts_width=widths.ctypes.data_as(C.POINTER(C.c_double)),
+                                tmin=tmin, tmax=tmax, emission_absorption=int(bool(emission_absorption)), stokes=int(bool(stokes)),
+                                gamma=int(bool(gamma)))
+        self._check(self.L.artis_amd_spectra_compute(self.h, C.byref(cfg), C.c_void_p(stream)))
+        self._spec_cfg = dict(nts=len(starts), all=dirbin == abi.SPEC_ALL_DIRBINS, ea=bool(emission_absorption), stokes=bool(stokes),
+                              gamma=bool(gamma))
+
+    def spectra_devptr(self):
+        p, n = C.c_void_p(), C.c_int64()
+        self._check(self.L.artis_amd_spectra_devptr(self.h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def spectra_download(self) -> dict:
+        c = self._spec_cfg
+        info = abi.Spectra(struct_size=C.sizeof(abi.Spectra))
+        self._check(self.L.artis_amd_spectra_download(self.h, C.byref(info)))  # shapes and counts first
+        T, D, B, P = info.ntimesteps, info.ndirslots, abi.SPEC_MNUBINS, info.proccount
+        A = info.nelements * info.max_nions
+        lead = (D,) if c["all"] else ()
+        shapes = {"lum": lead + (T,), "lumcmf": lead + (T,), "flux": lead + (B, T)}
+        if c["stokes"]:
+            shapes.update(flux_q=lead + (B, T), flux_u=lead + (B, T))
+        if c["ea"]:
+            shapes.update(emission=lead + (B, T, P), trueemission=lead + (B, T, P), absorption=lead + (B, T, A))
+            if c["stokes"]:
+                shapes.update(emission_q=lead + (B, T, P), emission_u=lead + (B, T, P), absorption_q=lead + (B, T, A),
+                              absorption_u=lead + (B, T, A))
+        if c["gamma"]:
+            shapes.update(gamma_lum=(T,), gamma_lumcmf=(T,), gamma_flux=(B, T))
+        out = {k: np.zeros(v) for k, v in shapes.items()}
+        for k, v in out.items():
+            setattr(info, k, v.ctypes.data_as(C.POINTER(C.c_double)))
+        grids = {k: np.zeros(abi.SPEC_MNUBINS, dtype=np.float32) for k in ("lower_freq", "delta_freq", "gamma_lower_freq", "gamma_delta_freq")}
+        for k, v in grids.items():
+            setattr(info, k, v.ctypes.data_as(C.POINTER(C.c_float)))
+        self._check(self.L.artis_amd_spectra_download(self.h, C.byref(info)))
+        out.update(grids)
+        out.update(nescaped=int(info.nescaped_rpkt), nescaped_gamma=int(info.nescaped_gamma), proccount=P,
+                   nelements=info.nelements, max_nions=info.max_nions)
+        return out
+
+    def spectra(self, ts_start, ts_width, tmin: float, tmax: float, dirbin: int = -1, emission_absorption: bool = False,
+                stokes: bool = False, gamma: bool = False) -> dict:
+        """The emergent spectra and light curves of the resident packets, binned on the device (tools/exspec.py's keys and the
+        reference's layouts: flux[nnu, nts], emission[nnu, nts, column], ...; a leading axis of 1 + MABINS with
+        dirbin=abi.SPEC_ALL_DIRBINS: slot 0 the angle average, slot s direction bin s - 1)."""
+        self.spectra_compute(ts_start, ts_width, tmin, tmax, dirbin, emission_absorption, stokes, gamma)
+        return self.spectra_download()
 
     def debug_cellcache(self, c: int) -> dict:
         d = self.model.d

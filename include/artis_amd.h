@@ -619,6 +619,49 @@ int artis_amd_last_kernel_ms_by_kind(artis_amd_engine *eng, double ms[8], int64_
  * level's rates when a packet first reaches it (macroatom.cc:398-417 calc_rates_if_needed). Any other build returns ARTIS_ERR_ARG. */
 int artis_amd_debug_visit_counts(artis_amd_engine *eng, uint32_t *counts, int64_t n);
 
+/* ---- emergent spectra and light curves ---------------------------------------
+ * The reference's binning of the escaped packets (add_to_spec_res / add_to_lc_res, spectrum_lightcurve.cc:544-713; exspec.cc:30-130)
+ * over the resident population, on the device. Every output element is the sequential sum of its contributions in the caller's
+ * packet order (the order artis_amd_packets_download returns): the same bits whatever slots the engine gave the packets.
+ * Layouts are the reference's (Spectra, spectrum_lightcurve.h), T = ntimesteps, B = ARTIS_SPEC_MNUBINS,
+ * P = proccount = 2 * nelements * max_nions + 1, A = nelements * max_nions:
+ *   lum, lumcmf [T]; flux(_q, _u) [nnu * T + nts]; emission(_q, _u), trueemission [(nnu * T + nts) * P + column];
+ *   absorption(_q, _u) [(nnu * T + nts) * A + element * max_nions + ion]; gamma_lum, gamma_lumcmf [T]; gamma_flux [nnu * T + nts].
+ * With dirbin == ARTIS_SPEC_ALL_DIRBINS every r-packet array has a leading axis of 1 + ARTIS_SPEC_MABINS slots: slot 0 the angle
+ * average, slot s direction bin s - 1. The gamma arrays are always the angle average. */
+#define ARTIS_SPEC_MNUBINS 1000 /* exspec.h:8 */
+#define ARTIS_SPEC_MABINS 100   /* exspec.h:12 */
+#define ARTIS_SPEC_ALL_DIRBINS (-2)
+typedef struct artis_spectra_config {
+  int64_t struct_size;       /* sizeof(artis_spectra_config) */
+  int32_t ntimesteps;        /* >= 1 */
+  int32_t dirbin;            /* -1: angle average; 0..MABINS-1: that direction bin (x MABINS); ARTIS_SPEC_ALL_DIRBINS */
+  const double *ts_start;    /* [ntimesteps] strictly increasing (globals::timesteps[].start) */
+  const double *ts_width;    /* [ntimesteps] */
+  double tmin, tmax;         /* globals::tmin / tmax */
+  int32_t emission_absorption;  /* emission, trueemission and absorption decompositions */
+  int32_t stokes;               /* Q and U of flux (and of emission / absorption) */
+  int32_t gamma;                /* gamma light curve and spectrum (0.05 .. 4 MeV, exspec.cc:61-64) */
+  int32_t reserved;
+} artis_spectra_config;
+typedef struct artis_spectra {
+  int64_t struct_size;  /* sizeof(artis_spectra) */
+  /* host arrays to fill (layouts above); NULL: skip. An array the last compute did not produce is an ARTIS_ERR_ARG. */
+  double *lum, *lumcmf, *flux, *flux_q, *flux_u, *emission, *emission_q, *emission_u, *trueemission, *absorption, *absorption_q,
+      *absorption_u, *gamma_lum, *gamma_lumcmf, *gamma_flux;
+  float *lower_freq, *delta_freq, *gamma_lower_freq, *gamma_delta_freq; /* [ARTIS_SPEC_MNUBINS] float32 bin edges; NULL: skip */
+  /* reported */
+  int64_t nescaped_rpkt, nescaped_gamma;
+  int32_t ntimesteps, ndirslots, nelements, max_nions, proccount, reserved;
+} artis_spectra;
+/* Bin the resident population (after artis_amd_packets_upload, artis_amd_update_packets_device or artis_amd_update_packets).
+ * Reads packets only. Scratch is allocated at the first call and reused. Synchronous. */
+int artis_amd_spectra_compute(artis_amd_engine *eng, const artis_spectra_config *cfg, void *hip_stream);
+/* The outputs of the last compute as one device block of *ndoubles doubles (for an all-reduce over ranks): the produced arrays
+ * of artis_spectra in the order of its fields. */
+int artis_amd_spectra_devptr(artis_amd_engine *eng, void **dptr, int64_t *ndoubles);
+int artis_amd_spectra_download(artis_amd_engine *eng, artis_spectra *out);
+
 #ifdef __cplusplus
 }
 #endif

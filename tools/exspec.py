@@ -96,3 +96,135 @@ def spectrum_and_lightcurve(packets: np.ndarray, ts_starts, ts_widths, tmin: flo
     ok_c &= ntc >= 0
     np.add.at(lumcmf, ntc[ok_c], p["e_cmf"][ok_c] / widths[ntc[ok_c]] * solidanglefactor / inv_gamma)
     return dict(flux=flux, lower_freq=lower, delta_freq=delta, lum=lum, lumcmf=lumcmf, nescaped=int(len(p)))
+
+
+# ---- emission / absorption decomposition, Stokes Q / U, gamma outputs and all direction bins (spectrum_lightcurve.cc:168-203,
+#      :544-640, exspec.cc:30-130), restated the same way: every output element adds its contributions in packet order (np.add.at)
+TYPE_GAMMA = 10
+EMTYPE_NOTSET, EMTYPE_FREEFREE = -9999000, -9999999
+MEV, H = 1.6021772e-6, 6.6260755e-27
+NU_MIN_GAMMA, NU_MAX_GAMMA = 0.05 * MEV / H, 4. * MEV / H  # exspec.cc:61-62
+
+
+def _grid(nu_min, nu_max):
+    dlognu = (np.log(nu_max) - np.log(nu_min)) / MNUBINS
+    edges = np.exp(np.log(nu_min) + np.arange(MNUBINS + 1) * dlognu)
+    lower = edges[:-1].astype(np.float32)
+    return dlognu, lower, (edges[1:] - lower.astype(np.float64)).astype(np.float32)
+
+
+def max_nions(model) -> int:
+    return int(np.max(model["elem_nions"]))
+
+
+def bf_columns(model) -> np.ndarray:
+    """element * max_nions + ion of every bflist entry: the bound-free emission type of (level, target t) is
+    -1 - (level_bflist_start[level] + t) (atomic.h:508), for the ionising levels of every ion"""
+    mx = max_nions(model)
+    cols = np.full(max(int(model["nbfcontinua"]), 1), -1, dtype=np.int64)
+    for ui in range(int(model["nions"])):
+        el = int(model["ion_element"][ui])
+        ion = ui - int(model["elem_uniqueionindexstart"][el])
+        l0 = int(model["ion_uniquelevelindexstart"][ui])
+        for lv in range(int(model["ion_nlevels_ionising"][ui])):
+            for t in range(int(model["level_nphixstargets"][l0 + lv])):
+                cols[int(model["level_bflist_start"][l0 + lv]) + t] = el * mx + ion
+    return cols
+
+
+def emission_columns(et: np.ndarray, model, nbfcontinua=None) -> np.ndarray:
+    """columnindex_from_emissiontype (spectrum_lightcurve.cc:168-203) of an array of emission types; -1: not counted"""
+    et = np.asarray(et, dtype=np.int64)
+    nel, mx = int(model["nelements"]), max_nions(model)
+    nbf = int(model["nbfcontinua"]) if nbfcontinua is None else nbfcontinua
+    nlines = int(model["nlines"])
+    out = np.full(et.shape, -1, dtype=np.int64)
+    bb = (et >= 0) & (et < nlines)
+    out[bb] = model["line_elementindex"][et[bb]].astype(np.int64) * mx + model["line_ionindex"][et[bb]]
+    out[et == EMTYPE_FREEFREE] = 2 * nel * mx
+    bf = (et < 0) & (et != EMTYPE_FREEFREE) & (et != EMTYPE_NOTSET)
+    if nbf == 0:
+        out[bf] = 2 * nel * mx
+    else:
+        idx = -1 - et
+        ok = bf & (idx < nbf)
+        cols = bf_columns(model)[idx[ok]]
+        out[ok] = np.where(cols >= 0, nel * mx + cols, -1)  # an entry that no level's target fills: not counted
+    return out
+
+
+def _escaped_rpkts(packets, dirbin):
+    sel = (packets["type"] == TYPE_ESCAPE) & (packets["escape_type"] == TYPE_RPKT)
+    p = packets[sel]
+    if dirbin >= 0:
+        return p[escapedirectionbin(p["dir"]) == dirbin], float(MABINS)
+    return p, 1.0
+
+
+def stokes_and_emission_absorption(packets: np.ndarray, ts_starts, ts_widths, tmin: float, tmax: float, model,
+                                   nu_min: float = 1e14, nu_max: float = 5e15, dirbin: int = -1, emission_absorption: bool = True,
+                                   stokes: bool = True, nbfcontinua=None) -> dict:
+    """add_to_spec_res (:544-640) beyond the flux: flux_q / flux_u [MNUBINS, nts] (stokes); emission(_q, _u), trueemission
+    [MNUBINS, nts, proccount] and absorption(_q, _u) [MNUBINS, nts, nelements * max_nions] (emission_absorption)."""
+    starts = np.asarray(ts_starts, dtype=np.float64)
+    widths = np.asarray(ts_widths, dtype=np.float64)
+    T = len(starts)
+    nel, mx = int(model["nelements"]), max_nions(model)
+    P, A = 2 * nel * mx + 1, nel * mx
+    p, saf = _escaped_rpkts(packets, dirbin)
+    dlognu, lower, delta = _grid(nu_min, nu_max)
+    t_arrive = p["escape_time"].astype(np.float64) - (p["pos"] * p["dir"]).sum(axis=1) / CLIGHT
+    nts = timestep_index(t_arrive, starts, tmax)
+    ok = (t_arrive > tmin) & (t_arrive < tmax) & (nts >= 0) & (p["nu_rf"] > nu_min) & (p["nu_rf"] < nu_max)
+    p, nts = p[ok], nts[ok]
+    nnu = np.clip(np.floor((np.log(p["nu_rf"]) - np.log(nu_min)) / dlognu).astype(np.int64), 0, MNUBINS - 1)
+    dE = p["e_rf"] / widths[nts] / delta[nnu].astype(np.float64) / 4.e12 / np.pi / PARSEC / PARSEC * saf
+    out = {}
+    if stokes:
+        for k, f in (("q", "stokes_q"), ("u", "stokes_u")):
+            a = np.zeros((MNUBINS, T))
+            np.add.at(a, (nnu, nts), p[f] * dE)
+            out["flux_" + k] = a
+    if not emission_absorption:
+        return out
+    comps = [("", None)] + ([("_q", "stokes_q"), ("_u", "stokes_u")] if stokes else [])
+    true_col = emission_columns(p["trueemissiontype"], model, nbfcontinua)
+    t = true_col >= 0
+    a = np.zeros((MNUBINS, T, P))
+    np.add.at(a, (nnu[t], nts[t], true_col[t]), dE[t])
+    out["trueemission"] = a
+    col = emission_columns(p["emissiontype"], model, nbfcontinua)
+    m = col >= 0
+    for suffix, f in comps:
+        a = np.zeros((MNUBINS, T, P))
+        np.add.at(a, (nnu[m], nts[m], col[m]), dE[m] if f is None else p[f][m] * dE[m])
+        out["emission" + suffix] = a
+    at = p["absorptiontype"].astype(np.int64)
+    b = (at >= 0) & (at < int(model["nlines"])) & (p["absorptionfreq"] > nu_min) & (p["absorptionfreq"] < nu_max)
+    pb, ntb, atb = p[b], nts[b], at[b]
+    nnu_abs = np.clip(np.floor((np.log(pb["absorptionfreq"]) - np.log(nu_min)) / dlognu).astype(np.int64), 0, MNUBINS - 1)
+    acol = model["line_elementindex"][atb].astype(np.int64) * mx + model["line_ionindex"][atb]
+    dEa = pb["e_rf"] / widths[ntb] / delta[nnu_abs].astype(np.float64) / 4.e12 / np.pi / PARSEC / PARSEC * saf
+    for suffix, f in comps:
+        a = np.zeros((MNUBINS, T, A))
+        np.add.at(a, (nnu_abs, ntb, acol), dEa if f is None else pb[f] * dEa)
+        out["absorption" + suffix] = a
+    return out
+
+
+def gamma_spectrum_and_lightcurve(packets: np.ndarray, ts_starts, ts_widths, tmin: float, tmax: float, vmax: float) -> dict:
+    """The escaped gamma packets (exspec.cc:80-86): gamma_lum, gamma_lumcmf [nts] and gamma_flux [MNUBINS, nts] over
+    0.05 .. 4 MeV, angle-averaged"""
+    g = packets[(packets["type"] == TYPE_ESCAPE) & (packets["escape_type"] == TYPE_GAMMA)].copy()
+    g["escape_type"] = TYPE_RPKT  # the same rules on the gamma frequency grid
+    r = spectrum_and_lightcurve(g, ts_starts, ts_widths, tmin, tmax, vmax, NU_MIN_GAMMA, NU_MAX_GAMMA)
+    return dict(gamma_lum=r["lum"], gamma_lumcmf=r["lumcmf"], gamma_flux=r["flux"], gamma_lower_freq=r["lower_freq"],
+                gamma_delta_freq=r["delta_freq"], nescaped_gamma=r["nescaped"])
+
+
+def all_dirbins(fn, *args, **kwargs) -> dict:
+    """fn(..., dirbin=b) for the angle average and every direction bin, stacked along a leading axis of 1 + MABINS
+    (slot 0: the angle average, slot s: direction bin s - 1); array outputs only"""
+    res = [fn(*args, dirbin=b, **kwargs) for b in range(-1, MABINS)]
+    return {k: np.stack([r[k] for r in res]) for k, v in res[0].items() if isinstance(v, np.ndarray) and k not in
+            ("lower_freq", "delta_freq")}
