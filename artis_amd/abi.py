@@ -440,3 +440,54 @@ class Spectra(C.Structure):
                [(k, _F32P) for k in ("lower_freq", "delta_freq", "gamma_lower_freq", "gamma_delta_freq")] + \
                [("nescaped_rpkt", C.c_int64), ("nescaped_gamma", C.c_int64)] + \
                [(k, C.c_int32) for k in ("ntimesteps", "ndirslots", "nelements", "max_nions", "proccount", "reserved")]
+
+
+# radiation-field fit (include/artis_amd.h artis_amd_radfield_*)
+RADFIELD_FITTED, RADFIELD_NUBAR_KEPT, RADFIELD_TJ_KEPT = 1, 2, 4
+RADFIELD_TJ_LOW, RADFIELD_TJ_HIGH, RADFIELD_TR_LOW, RADFIELD_TR_HIGH = 8, 16, 32, 64
+RADFIELD_COUNTS = ["trmin", "trmax", "retried", "zeroed", "notconverged"]  # ARTIS_RADFIELD_COUNT_* in index order
+
+
+class RadfieldConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("prev_mid", C.c_double), ("deltat", C.c_double), ("nprocs", C.c_int32),
+                ("lte_iteration", C.c_int32), ("assocvolume_tmin", _F64P), ("bfrate_normed_seed", _F32P)]
+
+
+class Radfield(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("J", _F64P), ("nuJ", _F64P), ("J_normfactor", _F64P), ("TJ", _F32P), ("TR", _F32P),
+                ("Te", _F32P), ("W", _F32P), ("flags", _I32P), ("cell_counts", _I32P), ("radfieldbin_T_R", _F32P),
+                ("radfieldbin_W", _F32P), ("bfrate_normed", _F32P), ("Jb_lu_normed", _F64P), ("Jb_lu_contribcount", _I64P),
+                ("totals", C.c_int64 * 5), ("npts_nonempty", C.c_int32), ("nbins", C.c_int32), ("nbfestim", C.c_int32),
+                ("detailed_linecount", C.c_int32), ("kernel_ms", C.c_double * 2)]
+
+
+def radfield_arrays(ncell: int, nbins: int, nbfestim: int, nlines: int) -> dict:
+    """zeroed host arrays for every output of artis_radfield (the keys are its field names)"""
+    out = dict(J=np.zeros(ncell), nuJ=np.zeros(ncell), J_normfactor=np.zeros(ncell), TJ=np.zeros(ncell, np.float32),
+               TR=np.zeros(ncell, np.float32), Te=np.zeros(ncell, np.float32), W=np.zeros(ncell, np.float32),
+               flags=np.zeros(ncell, np.int32), cell_counts=np.zeros((ncell, len(RADFIELD_COUNTS)), np.int32))
+    if nbins:
+        out.update(radfieldbin_T_R=np.zeros(ncell * nbins, np.float32), radfieldbin_W=np.zeros(ncell * nbins, np.float32))
+    if nbfestim:
+        out["bfrate_normed"] = np.zeros(ncell * nbfestim, np.float32)
+    if nlines:
+        out.update(Jb_lu_normed=np.zeros(ncell * nlines), Jb_lu_contribcount=np.zeros(ncell * nlines, np.int64))
+    return out
+
+
+def radfield_point(rf: Radfield, arrays: dict):
+    """point the fields of rf at the arrays of radfield_arrays()"""
+    types = dict(Radfield._fields_)
+    for k, v in arrays.items():
+        setattr(rf, k, v.ctypes.data_as(types[k]))
+
+
+def radfield_config(prev_mid: float, deltat: float, nprocs: int, assocvolume_tmin: np.ndarray, lte_iteration: bool = False,
+                    bfrate_normed_seed=None):
+    """(RadfieldConfig, the arrays it points into: keep them alive while it is used)"""
+    vol = np.ascontiguousarray(assocvolume_tmin, dtype=np.float64)
+    seed = None if bfrate_normed_seed is None else np.ascontiguousarray(bfrate_normed_seed, dtype=np.float32)
+    cfg = RadfieldConfig(struct_size=C.sizeof(RadfieldConfig), prev_mid=prev_mid, deltat=deltat, nprocs=nprocs,
+                         lte_iteration=int(bool(lte_iteration)), assocvolume_tmin=vol.ctypes.data_as(_F64P),
+                         bfrate_normed_seed=seed.ctypes.data_as(_F32P) if seed is not None else None)
+    return cfg, (vol, seed)

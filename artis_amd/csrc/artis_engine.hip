@@ -19,10 +19,13 @@
 #include <chrono>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
+#include <cmath>
 
 #include "model_build.h"
 #include "physics.h"
+#include "radfield_fit.h"
 #include "spectra.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -2543,6 +2546,9 @@ void spec_free_scratch(SpecState *st) {
   st->sort_tmp_bytes = 0;
 }
 
+struct RfState;  // artis_amd_radfield_*: defined with them at the end of this file
+void rf_free(RfState *st);
+
 void spec_free(SpecState *st) {
   if (!st) return;
   spec_free_scratch(st);
@@ -2558,6 +2564,7 @@ void spec_free(SpecState *st) {
 struct artis_amd_engine {
   int device = 0;
   SpecState *spec = nullptr;  // artis_amd_spectra_*: nothing until the first call
+  RfState *rf = nullptr;      // artis_amd_radfield_*: nothing until the first call
   ModelOwned own;
   std::vector<void *> model_allocs;
   std::vector<void *> cell_allocs;
@@ -3450,6 +3457,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   free_all(e->cache_allocs);
   free_packet_buffers(e);
   spec_free(e->spec);
+  rf_free(e->rf);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->d_krow, e->d_fill_cells, e->d_waiting,
                   e->d_bfrate_kept, e->d_collexc_terms, e->d_visit_counts};
@@ -4941,6 +4949,312 @@ int artis_amd_spectra_download(artis_amd_engine *e, artis_spectra *out) {
   out->nelements = e->Mh.nelements;
   out->max_nions = st->max_nions;
   out->proccount = st->shape.proccount;
+  return ARTIS_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ radiation-field fit (radfield_fit.h)
+// Two kernels on the caller's stream. k_rf_cell: one wave per cell; lane 0 normalises J (and nuJ) and fits T_J, T_R, W
+// (artis_rf::fit_cell), the wave's lanes normalise the cell's bound-free and line estimators and carry the bins of a cell
+// that is not fitted over from the cell state. k_rf_bins: one lane per (cell, bin), a cell's bins on neighbouring lanes so that
+// a wave's residuals have similar x; the estimators are read in place ([cell][bin]{J, nuJ}). Nothing is added with float
+// atomics: every output element has one writer. The bin counts are integer atomics (per cell, only for a bin that has the
+// bit) and one ballot per wave and count for the totals.
+namespace {
+
+struct RfArgs {
+  int64_t ncell;
+  // inputs: the estimator block (J, nuJ with stride 8), the cell state, the caller's volumes
+  const double *J_raw, *nuJ_raw, *bin_est, *bfrate_raw, *Jb_raw, *Jb_count;
+  const double *assocvol;
+  const int32_t *thick;
+  const float *TJ, *TR, *Te, *W, *prev_bin_T_R, *prev_bin_W;
+  double prev_mid, tmin, deltat;
+  int32_t nprocs, lte, nbf, nline;
+  // outputs
+  double *J, *nuJ, *normfactor;
+  float *oTJ, *oTR, *oTe, *oW;
+  int32_t *flags, *counts;
+  float *bin_T_R, *bin_W, *bf;
+  double *Jb, *Jbcount;
+  unsigned long long *totals;
+};
+
+__global__ void __launch_bounds__(BLOCK) k_rf_cell(RfArgs a) {
+  using namespace artis_rf;
+  const int64_t c = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) / 64;
+  const int lane = (int)(threadIdx.x & 63);
+  if (c >= a.ncell) return;  // whole waves
+  const int32_t thick = a.thick[c];
+  if (lane == 0) {
+    const CellIn in{a.J_raw[c * 8], a.nuJ_raw[c * 8], a.assocvol[c], a.prev_mid, a.tmin, a.deltat, a.nprocs, a.lte, thick,
+                    a.TJ[c], a.TR[c], a.Te[c], a.W[c]};
+    const CellOut o = fit_cell(in);
+    a.J[c] = o.J;
+    a.nuJ[c] = o.nuJ;
+    a.normfactor[c] = o.J_normfactor;
+    a.oTJ[c] = o.TJ;
+    a.oTR[c] = o.TR;
+    a.oTe[c] = o.Te;
+    a.oW[c] = o.W;
+    a.flags[c] = o.flags;
+    for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) a.counts[c * ARTIS_RADFIELD_NCOUNTS + k] = 0;
+  }
+  double estimator_normfactor, over4pi;
+  cell_normfactors(a.assocvol[c], a.prev_mid, a.tmin, a.deltat, a.nprocs, &estimator_normfactor, &over4pi);
+  if (a.bin_T_R && !cell_is_fitted(a.lte, thick)) {
+    for (int b = lane; b < NBINS; b += 64) {
+      a.bin_T_R[c * NBINS + b] = a.prev_bin_T_R[c * NBINS + b];
+      a.bin_W[c * NBINS + b] = a.prev_bin_W[c * NBINS + b];
+    }
+  }
+  if (a.bf && !a.lte && thick != ARTIS_CELL_THICK) {
+    for (int i = lane; i < a.nbf; i += 64) a.bf[c * a.nbf + i] = bfrate_normed(a.bfrate_raw[c * a.nbf + i], estimator_normfactor);
+  }
+  if (a.Jb) {
+    for (int i = lane; i < a.nline; i += 64) {
+      a.Jb[c * a.nline + i] = a.Jb_raw[c * a.nline + i] * over4pi;
+      a.Jbcount[c * a.nline + i] = a.Jb_count[c * a.nline + i];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(BLOCK) k_rf_bins(RfArgs a) {
+  using namespace artis_rf;
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  int bits = 0;
+  if (i < a.ncell * NBINS) {
+    const int64_t c = i / NBINS;
+    const int b = (int)(i - c * NBINS);
+    if (a.flags[c] & ARTIS_RADFIELD_FITTED) {
+      float T_R, W;
+      bits = fit_bin(a.bin_est[2 * i], a.bin_est[2 * i + 1], a.normfactor[c], b, a.Te[c], &T_R, &W);
+      a.bin_T_R[i] = T_R;
+      a.bin_W[i] = W;
+      for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++)
+        if (bits & (1 << k)) atomicAdd(&a.counts[c * ARTIS_RADFIELD_NCOUNTS + k], 1);
+    }
+  }
+  for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) {  // the bit k of a bin is count k (artis_rf::BIN_*)
+    const unsigned long long m = __ballot((bits >> k) & 1);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.totals[k], (unsigned long long)__popcll(m));
+  }
+}
+
+// the result block of artis_amd_radfield_*: one allocation, made at the first call, zeroed then (the bound-free block keeps
+// its values from call to call for the THICK cells, as the reference's prev_bfrate_normed does)
+struct RfState {
+  void *d_block = nullptr;
+  size_t bytes = 0;
+  int64_t ncell = 0, nbins = 0, nbf = 0, nline = 0;
+  double *d_J = nullptr, *d_nuJ = nullptr, *d_normfactor = nullptr, *d_assocvol = nullptr, *d_Jb = nullptr, *d_Jbcount = nullptr;
+  float *d_TJ = nullptr, *d_TR = nullptr, *d_Te = nullptr, *d_W = nullptr, *d_bin_T_R = nullptr, *d_bin_W = nullptr, *d_bf = nullptr;
+  int32_t *d_flags = nullptr, *d_counts = nullptr;
+  unsigned long long *d_totals = nullptr;
+  hipEvent_t ev[3] = {};
+  bool valid = false;
+  unsigned long long totals[ARTIS_RADFIELD_NCOUNTS] = {};
+  double kernel_ms[2] = {};
+};
+
+void rf_free(RfState *st) {
+  if (!st) return;
+  if (st->d_block) (void)hipFree(st->d_block);
+  for (hipEvent_t ev : st->ev)
+    if (ev) (void)hipEventDestroy(ev);
+  delete st;
+}
+
+int rf_arg_error(const char *msg) {
+  g_last_error = msg;
+  return ARTIS_ERR_ARG;
+}
+
+// carve every array out of one block (256-byte aligned pieces); with base == nullptr only the size is counted
+size_t rf_layout(RfState *st, char *base) {
+  size_t off = 0;
+  auto take = [&](auto **p, int64_t count, size_t elem) {
+    const size_t sz = ((size_t)(count > 0 ? count : 0) * elem + 255) & ~(size_t)255;
+    if (base) *p = count > 0 ? (std::remove_reference_t<decltype(*p)>)(base + off) : nullptr;
+    off += sz;
+  };
+  const int64_t n = st->ncell;
+  take(&st->d_J, n, sizeof(double));
+  take(&st->d_nuJ, n, sizeof(double));
+  take(&st->d_normfactor, n, sizeof(double));
+  take(&st->d_assocvol, n, sizeof(double));
+  take(&st->d_TJ, n, sizeof(float));
+  take(&st->d_TR, n, sizeof(float));
+  take(&st->d_Te, n, sizeof(float));
+  take(&st->d_W, n, sizeof(float));
+  take(&st->d_flags, n, sizeof(int32_t));
+  take(&st->d_counts, n * ARTIS_RADFIELD_NCOUNTS, sizeof(int32_t));
+  take(&st->d_totals, ARTIS_RADFIELD_NCOUNTS, sizeof(unsigned long long));
+  take(&st->d_bin_T_R, n * st->nbins, sizeof(float));
+  take(&st->d_bin_W, n * st->nbins, sizeof(float));
+  take(&st->d_bf, n * st->nbf, sizeof(float));
+  take(&st->d_Jb, n * st->nline, sizeof(double));
+  take(&st->d_Jbcount, n * st->nline, sizeof(double));
+  return off;
+}
+
+int rf_init(artis_amd_engine *e) {
+  if (e->rf) return ARTIS_OK;
+  RfState *st = new RfState();
+  st->ncell = e->Mh.npts_nonempty;
+  st->nbins = ARTIS_OPT_MULTIBIN_RADFIELD_MODEL_ON ? ARTIS_OPT_RADFIELDBINCOUNT : 0;
+  st->nbf = e->E.bfrate_raw ? e->Mh.nbfestim : 0;
+  st->nline = e->E.Jb_lu_raw ? e->Mh.detailed_linecount : 0;
+  st->bytes = rf_layout(st, nullptr);
+  size_t free_b = 0, total_b = 0;
+  hipError_t err = hipMemGetInfo(&free_b, &total_b);
+  if (err == hipSuccess && (double)st->bytes > 0.9 * (double)free_b) {
+    delete st;
+    return rf_arg_error("radfield: the result block does not fit the free device memory");
+  }
+  if (err == hipSuccess) err = hipMalloc(&st->d_block, st->bytes);
+  if (err == hipSuccess) err = hipMemset(st->d_block, 0, st->bytes);
+  for (hipEvent_t &ev : st->ev)
+    if (err == hipSuccess) err = hipEventCreate(&ev);
+  if (err != hipSuccess) {
+    rf_free(st);
+    g_last_error = std::string("radfield: allocation of the result block: ") + hipGetErrorString(err);
+    return ARTIS_ERR_HIP;
+  }
+  rf_layout(st, (char *)st->d_block);
+  e->rf = st;
+  return ARTIS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int artis_amd_radfield_fit(artis_amd_engine *e, const artis_radfield_config *cfg, void *hip_stream) {
+  if (!e || !cfg) return rf_arg_error("radfield: null engine or config");
+  if (cfg->struct_size != (int64_t)sizeof(artis_radfield_config))
+    return rf_arg_error("radfield: artis_radfield_config.struct_size does not match");
+  if (!e->have_cells) return rf_arg_error("radfield: no cell state (artis_amd_set_cellstate)");
+  if (!(cfg->deltat > 0) || !std::isfinite(cfg->deltat)) return rf_arg_error("radfield: deltat must be positive and finite");
+  if (!(cfg->prev_mid > 0) || !std::isfinite(cfg->prev_mid)) return rf_arg_error("radfield: prev_mid must be positive and finite");
+  if (cfg->nprocs < 1) return rf_arg_error("radfield: nprocs < 1");
+  if (!cfg->assocvolume_tmin) return rf_arg_error("radfield: null assocvolume_tmin");
+  const int64_t ncell = e->Mh.npts_nonempty;
+  for (int64_t c = 0; c < ncell; c++)
+    if (!(cfg->assocvolume_tmin[c] > 0) || !std::isfinite(cfg->assocvolume_tmin[c]))
+      return rf_arg_error("radfield: assocvolume_tmin must be positive and finite in every cell");
+  if (e->E.bfrate_raw && e->bfrate_kept_dirty)
+    return rf_arg_error("radfield: the last propagation call ended in an error, the bound-free estimators are incomplete");
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = rf_init(e);
+  if (rc != ARTIS_OK) return rc;
+  RfState *st = e->rf;
+  st->valid = false;
+  hipStream_t s = (hipStream_t)hip_stream;
+  HIP_TRY(hipMemcpyAsync(st->d_assocvol, cfg->assocvolume_tmin, sizeof(double) * (size_t)ncell, hipMemcpyHostToDevice, s));
+  if (cfg->bfrate_normed_seed && st->nbf > 0)
+    HIP_TRY(hipMemcpyAsync(st->d_bf, cfg->bfrate_normed_seed, sizeof(float) * (size_t)(ncell * st->nbf), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(st->d_totals, 0, sizeof(unsigned long long) * ARTIS_RADFIELD_NCOUNTS, s));
+  RfArgs a{};
+  a.ncell = ncell;
+  a.J_raw = e->E.J;
+  a.nuJ_raw = e->E.nuJ;
+  a.bin_est = e->E.radfieldbin_J;
+  a.bfrate_raw = e->E.bfrate_raw;
+  a.Jb_raw = e->E.Jb_lu_raw;
+  a.Jb_count = e->E.Jb_lu_contribcount;
+  a.assocvol = st->d_assocvol;
+  a.thick = e->C.thick;
+  a.TJ = e->C.TJ;
+  a.TR = e->C.TR;
+  a.Te = e->C.Te;
+  a.W = e->C.W;
+  a.prev_bin_T_R = e->C.radfieldbin_T_R;
+  a.prev_bin_W = e->C.radfieldbin_W;
+  a.prev_mid = cfg->prev_mid;
+  a.tmin = e->model_copy.tmin;
+  a.deltat = cfg->deltat;
+  a.nprocs = cfg->nprocs;
+  a.lte = cfg->lte_iteration != 0;
+  a.nbf = (int32_t)st->nbf;
+  a.nline = (int32_t)st->nline;
+  a.J = st->d_J;
+  a.nuJ = st->d_nuJ;
+  a.normfactor = st->d_normfactor;
+  a.oTJ = st->d_TJ;
+  a.oTR = st->d_TR;
+  a.oTe = st->d_Te;
+  a.oW = st->d_W;
+  a.flags = st->d_flags;
+  a.counts = st->d_counts;
+  a.bin_T_R = st->d_bin_T_R;
+  a.bin_W = st->d_bin_W;
+  a.bf = st->d_bf;
+  a.Jb = st->d_Jb;
+  a.Jbcount = st->d_Jbcount;
+  a.totals = st->d_totals;
+  HIP_TRY(hipEventRecord(st->ev[0], s));
+  if (ncell > 0) {
+    hipLaunchKernelGGL(k_rf_cell, dim3(nblocks(ncell * 64)), dim3(BLOCK), 0, s, a);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(st->ev[1], s));
+  if (ncell > 0 && st->nbins > 0) {
+    hipLaunchKernelGGL(k_rf_bins, dim3(nblocks(ncell * st->nbins)), dim3(BLOCK), 0, s, a);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(st->ev[2], s));
+  HIP_TRY(hipMemcpyAsync(st->totals, st->d_totals, sizeof(st->totals), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  float ms0 = 0.f, ms1 = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms0, st->ev[0], st->ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms1, st->ev[1], st->ev[2]));
+  st->kernel_ms[0] = ms0;
+  st->kernel_ms[1] = ms1;
+  st->valid = true;
+  return ARTIS_OK;
+}
+
+int artis_amd_radfield_download(artis_amd_engine *e, artis_radfield *out) {
+  if (!e || !out) return rf_arg_error("radfield: null argument");
+  if (out->struct_size != (int64_t)sizeof(artis_radfield)) return rf_arg_error("radfield: artis_radfield.struct_size does not match");
+  if (!e->rf || !e->rf->valid) return rf_arg_error("radfield: nothing fitted (artis_amd_radfield_fit)");
+  RfState *st = e->rf;
+  if (((out->radfieldbin_T_R || out->radfieldbin_W) && st->nbins == 0) || (out->bfrate_normed && st->nbf == 0) ||
+      ((out->Jb_lu_normed || out->Jb_lu_contribcount) && st->nline == 0))
+    return rf_arg_error("radfield: an array was asked for that this build does not make");
+  HIP_TRY(hipSetDevice(e->device));
+  const int64_t n = st->ncell;
+  auto get = [&](void *dst, const void *src, int64_t count, size_t elem) -> hipError_t {
+    if (!dst || count <= 0) return hipSuccess;
+    return hipMemcpy(dst, src, elem * (size_t)count, hipMemcpyDeviceToHost);
+  };
+  HIP_TRY(get(out->J, st->d_J, n, sizeof(double)));
+  HIP_TRY(get(out->nuJ, st->d_nuJ, n, sizeof(double)));
+  HIP_TRY(get(out->J_normfactor, st->d_normfactor, n, sizeof(double)));
+  HIP_TRY(get(out->TJ, st->d_TJ, n, sizeof(float)));
+  HIP_TRY(get(out->TR, st->d_TR, n, sizeof(float)));
+  HIP_TRY(get(out->Te, st->d_Te, n, sizeof(float)));
+  HIP_TRY(get(out->W, st->d_W, n, sizeof(float)));
+  HIP_TRY(get(out->flags, st->d_flags, n, sizeof(int32_t)));
+  HIP_TRY(get(out->cell_counts, st->d_counts, n * ARTIS_RADFIELD_NCOUNTS, sizeof(int32_t)));
+  HIP_TRY(get(out->radfieldbin_T_R, st->d_bin_T_R, n * st->nbins, sizeof(float)));
+  HIP_TRY(get(out->radfieldbin_W, st->d_bin_W, n * st->nbins, sizeof(float)));
+  HIP_TRY(get(out->bfrate_normed, st->d_bf, n * st->nbf, sizeof(float)));
+  HIP_TRY(get(out->Jb_lu_normed, st->d_Jb, n * st->nline, sizeof(double)));
+  if (out->Jb_lu_contribcount && st->nline > 0) {
+    std::vector<double> cnt((size_t)(n * st->nline));
+    HIP_TRY(get(cnt.data(), st->d_Jbcount, n * st->nline, sizeof(double)));
+    for (size_t i = 0; i < cnt.size(); i++) out->Jb_lu_contribcount[i] = (int64_t)cnt[i];
+  }
+  for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) out->totals[k] = (int64_t)st->totals[k];
+  out->npts_nonempty = (int32_t)n;
+  out->nbins = (int32_t)st->nbins;
+  out->nbfestim = (int32_t)st->nbf;
+  out->detailed_linecount = (int32_t)st->nline;
+  out->kernel_ms[0] = st->kernel_ms[0];
+  out->kernel_ms[1] = st->kernel_ms[1];
   return ARTIS_OK;
 }
 

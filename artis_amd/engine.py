@@ -57,6 +57,8 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_spectra_compute.argtypes = [C.c_void_p, C.POINTER(abi.SpectraConfig), C.c_void_p]
     L.artis_amd_spectra_devptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.artis_amd_spectra_download.argtypes = [C.c_void_p, C.POINTER(abi.Spectra)]
+    L.artis_amd_radfield_fit.argtypes = [C.c_void_p, C.POINTER(abi.RadfieldConfig), C.c_void_p]
+    L.artis_amd_radfield_download.argtypes = [C.c_void_p, C.POINTER(abi.Radfield)]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -80,6 +82,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_allreduce_estimators", "artis_amd_comm_unique_id", "artis_amd_comm_init", "artis_amd_comm_count",
     "artis_amd_cache_tiles", "artis_amd_last_tiling", "artis_amd_last_tiling_fills", "artis_amd_last_tiling_parked", "artis_amd_last_pool_resets", "artis_amd_record_tiers", "artis_amd_last_thermal_variants", "artis_amd_last_pool_usage",
     "artis_amd_spectra_compute", "artis_amd_spectra_devptr", "artis_amd_spectra_download",
+    "artis_amd_radfield_fit", "artis_amd_radfield_download",
 ]
 
 
@@ -199,6 +202,31 @@ class Engine:
         dirbin=abi.SPEC_ALL_DIRBINS: slot 0 the angle average, slot s direction bin s - 1)."""
         self.spectra_compute(ts_start, ts_width, tmin, tmax, dirbin, emission_absorption, stokes, gamma)
         return self.spectra_download()
+
+    # radiation-field fit of the grid update (include/artis_amd.h artis_amd_radfield_*)
+    def radfield_fit(self, prev_mid: float, deltat: float, assocvolume_tmin, nprocs: int = 1, lte_iteration: bool = False,
+                     bfrate_normed_seed=None, stream: int = 0) -> dict:
+        """Fit T_J, T_R, W (and the multibin W, T_R) of every cell to the engine's estimators and cell state on the device, then
+        download everything: numpy arrays under the field names of artis_radfield (cell_counts [ncell, 5]), the per-call
+        "totals" as a dict over abi.RADFIELD_COUNTS and "kernel_ms" (per-cell, per-bin kernel). assocvolume_tmin: [npts_nonempty]
+        (synth.assocvolume_tmin for the synthetic grids)."""
+        cfg, keep = abi.radfield_config(prev_mid, deltat, nprocs, assocvolume_tmin, lte_iteration, bfrate_normed_seed)
+        self._check(self.L.artis_amd_radfield_fit(self.h, C.byref(cfg), C.c_void_p(stream)))
+        del keep
+        return self.radfield_download()
+
+    def radfield_download(self) -> dict:
+        info = abi.Radfield(struct_size=C.sizeof(abi.Radfield))
+        self._check(self.L.artis_amd_radfield_download(self.h, C.byref(info)))  # sizes first
+        out = abi.radfield_arrays(info.npts_nonempty, info.nbins, info.nbfestim, info.detailed_linecount)
+        abi.radfield_point(info, out)
+        self._check(self.L.artis_amd_radfield_download(self.h, C.byref(info)))
+        if info.nbins:
+            out["radfieldbin_T_R"] = out["radfieldbin_T_R"].reshape(info.npts_nonempty, info.nbins)
+            out["radfieldbin_W"] = out["radfieldbin_W"].reshape(info.npts_nonempty, info.nbins)
+        out["totals"] = {k: int(info.totals[i]) for i, k in enumerate(abi.RADFIELD_COUNTS)}
+        out["kernel_ms"] = (float(info.kernel_ms[0]), float(info.kernel_ms[1]))
+        return out
 
     def debug_cellcache(self, c: int) -> dict:
         d = self.model.d

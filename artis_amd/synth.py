@@ -717,6 +717,27 @@ def build(preset: str = "small", ncoord: int = 8, gridtype: int = abi.GRID_CARTE
     return model, cs, ts, aux
 
 
+def assocvolume_tmin(model: abi.Model) -> np.ndarray:
+    """grid::get_modelcell_assocvolume_tmin (grid.cc:1565) of every non-empty cell of a grid made here: the volume at tmin of the
+    propagation cells that map to it (grid.cc:1576 get_propcell_volume_tmin; one propagation cell per model cell here).
+    3D Cartesian: (2 rmax / n)^3; 2D cylindrical: delta_z pi (r_out^2 - r_in^2); 1D spherical: 4/3 pi (r_out^3 - r_in^3)."""
+    gt, rmax = int(model["gridtype"]), float(model["rmax"])
+    nc = [int(x) for x in model["ncoordgrid"]]
+    mins = [np.asarray(a, dtype=np.float64) for a in model["coord_pos_min_tmin"]]
+    outer = [np.concatenate([m[1:], [rmax]]) if len(m) else m for m in mins]  # upper edge of a cell: the next one's lower edge
+    if gt == abi.GRID_CARTESIAN3D:
+        vol = np.full(nc[0] * nc[1] * nc[2], (outer[0][0] - mins[0][0]) ** 3)
+    elif gt == abi.GRID_CYLINDRICAL2D:
+        ir = np.tile(np.arange(nc[0]), nc[1])  # cellindex = ir + nr * iz
+        vol = (outer[1][0] - mins[1][0]) * np.pi * (outer[0][ir] ** 2 - mins[0][ir] ** 2)
+    else:
+        vol = 4.0 / 3.0 * np.pi * (outer[0] ** 3 - mins[0] ** 3)
+    prop = np.asarray(model["propcell_nonemptymgi"])
+    out = np.zeros(int(model["npts_nonempty"]))
+    np.add.at(out, prop[prop >= 0], vol[prop >= 0])
+    return out
+
+
 def evolve_cellstate(cs: abi.CellState, t0: float, t1: float, tfloor: float = 2500.0) -> abi.CellState:
     """The cell state of build() carried from time t0 to t1 by a DETERMINISTIC host rule that stands in for update_grid() (which is not part of
     the packet path) in multi-timestep tests: homologous expansion thins every density as (t0/t1)^3 -- rho, nne, nnetot, the ions' ground-level

@@ -662,6 +662,68 @@ int artis_amd_spectra_compute(artis_amd_engine *eng, const artis_spectra_config 
 int artis_amd_spectra_devptr(artis_amd_engine *eng, void **dptr, int64_t *ndoubles);
 int artis_amd_spectra_download(artis_amd_engine *eng, artis_spectra *out);
 
+/* ---- radiation-field fit ---------------------------------------------------------
+ * The radiation-field part of the reference's grid update (update_grid_cell, update_grid.cc:462-573), on the device, from the
+ * engine's estimator block (after the all-reduce: the summed estimators) and its current cell state (artis_amd_set_cellstate):
+ *   every non-empty cell: estimator_normfactor = 1 / (assocvolume_tmin * (prev_mid / tmin)^3) / deltat / nprocs,
+ *     J_normfactor = estimator_normfactor / 4 pi, J = J_raw * J_normfactor (normalise_J radfield.cc:893);
+ *   LTE iteration or THICK cell: T_J from J (get_T_J_from_J radfield.cc:956; non-finite: the previous T_J), clamped to
+ *     [MINTEMP, MAXTEMP]; T_R = T_e = T_J, W = 1; nuJ stays raw and the bins keep their current values;
+ *   other cells: nuJ normalised, the full-spectrum fit (set_params_fullspec radfield.cc:400; nubar non-finite or 0: T_J, T_R,
+ *     W stay) and, in multibin builds, (W, T_R) of every bin (fit_parameters radfield.cc:806: TOMS 748 root of the Planck mean
+ *     frequency in [500, 250000] K; the last bin takes T_e); T_e stays (its thermal-balance solve is the host's);
+ *   detailed bound-free estimators (builds with them): bfrate_normed = float(bfrate_raw * estimator_normfactor / H) for every
+ *     cell that is not THICK, unless lte_iteration (normalise_bf_estimators radfield.cc:902-925); THICK cells keep what the
+ *     engine's block held (zero when first made, or bfrate_normed_seed);
+ *   detailed line estimators (builds with them): Jb_lu_normed = Jb_lu_raw * J_normfactor and the contribution counts.
+ * The reference's log lines become flag bits per cell and counts per cell and per call. The call changes no estimator, packet,
+ * counter or cell state; two calls on the same state give identical results. */
+#define ARTIS_RADFIELD_FITTED 1      /* the cell went through the fit (not THICK, not lte_iteration) */
+#define ARTIS_RADFIELD_NUBAR_KEPT 2  /* nuJ / J non-finite or 0: T_J, T_R and W of the cell state kept */
+#define ARTIS_RADFIELD_TJ_KEPT 4     /* LTE / THICK: T_J from J non-finite, the previous T_J kept */
+#define ARTIS_RADFIELD_TJ_LOW 8      /* T_J clamped to MINTEMP */
+#define ARTIS_RADFIELD_TJ_HIGH 16    /* ... to MAXTEMP */
+#define ARTIS_RADFIELD_TR_LOW 32     /* full-spectrum T_R clamped to MINTEMP */
+#define ARTIS_RADFIELD_TR_HIGH 64    /* ... to MAXTEMP */
+/* per-cell and per-call counts of bins: [0] T_R at or below 500 K, [1] at or above 250000 K (both from the root search: a bin
+ * retried or zeroed afterwards is still counted here), [2] W > 1e4 or non-finite, retried at 250000 K, [3] of those, W still
+ * > 1e4: T_R = -99, W = 0, [4] root search stopped at 100 evaluations */
+#define ARTIS_RADFIELD_COUNT_TRMIN 0
+#define ARTIS_RADFIELD_COUNT_TRMAX 1
+#define ARTIS_RADFIELD_COUNT_RETRIED 2
+#define ARTIS_RADFIELD_COUNT_ZEROED 3
+#define ARTIS_RADFIELD_COUNT_NOTCONVERGED 4
+#define ARTIS_RADFIELD_NCOUNTS 5
+typedef struct artis_radfield_config {
+  int64_t struct_size;                /* sizeof(artis_radfield_config) */
+  double prev_mid;                    /* globals::timesteps[nts_prev].mid */
+  double deltat;                      /* globals::timesteps[nts_prev].width, > 0 */
+  int32_t nprocs;                     /* globals::nprocs, >= 1 */
+  int32_t lte_iteration;              /* globals::lte_iteration */
+  const double *assocvolume_tmin;     /* [npts_nonempty] grid::get_modelcell_assocvolume_tmin(mgi), > 0 */
+  const float *bfrate_normed_seed;    /* [npts_nonempty*nbfestim] or NULL: copied into the engine's block first */
+} artis_radfield_config;
+typedef struct artis_radfield {
+  int64_t struct_size; /* sizeof(artis_radfield) */
+  /* host arrays to fill; NULL: skip. An array this build does not make (bins, bf or line estimators) is an ARTIS_ERR_ARG. */
+  double *J, *nuJ, *J_normfactor;     /* [npts_nonempty] */
+  float *TJ, *TR, *Te, *W;            /* [npts_nonempty] */
+  int32_t *flags;                     /* [npts_nonempty] ARTIS_RADFIELD_* bits */
+  int32_t *cell_counts;               /* [npts_nonempty][ARTIS_RADFIELD_NCOUNTS] */
+  float *radfieldbin_T_R, *radfieldbin_W; /* [npts_nonempty*nbins] */
+  float *bfrate_normed;               /* [npts_nonempty*nbfestim] */
+  double *Jb_lu_normed;               /* [npts_nonempty*detailed_linecount] */
+  int64_t *Jb_lu_contribcount;
+  /* reported */
+  int64_t totals[ARTIS_RADFIELD_NCOUNTS];
+  int32_t npts_nonempty, nbins, nbfestim, detailed_linecount; /* 0 where the build has none */
+  double kernel_ms[2]; /* HIP-event time of the last fit: [0] the per-cell kernel, [1] the per-bin kernel */
+} artis_radfield;
+/* Fit into the engine's result block (allocated at the first call, all of it at once). Synchronous on hip_stream. */
+int artis_amd_radfield_fit(artis_amd_engine *eng, const artis_radfield_config *cfg, void *hip_stream);
+/* Copy the results of the last fit to the host (sizes in the reported fields even when every pointer is NULL). */
+int artis_amd_radfield_download(artis_amd_engine *eng, artis_radfield *out);
+
 #ifdef __cplusplus
 }
 #endif
