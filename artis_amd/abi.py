@@ -17,6 +17,16 @@ NSCALARS = 11  # ARTIS_SCALAR_* of include/artis_amd.h
 SCALAR_NAMES = ["gamma_dep_discrete", "nt_energy_deposited", "pellet_decays", "gamma_emission", "positron_emission",
                 "electron_emission", "alpha_emission", "spfission_dep_discrete", "electron_dep_discrete",
                 "positron_dep_discrete", "alpha_dep_discrete"]
+# artis_amd_last_estimator_forms(): how the kernels of the last call added to the per-cell estimators (include/artis_amd.h ARTIS_AMD_EST_*)
+EST_FORMS = {"RPKT_LDS_CONT": 1, "RPKT_LDS_NOCONT": 2, "RPKT_LDS_LINE": 32768, "RPKT_WAVECACHE": 4, "RPKT_GLOBAL": 8,
+             "THERMAL_LDS": 16, "THERMAL_WAVECACHE": 32, "THERMAL_GLOBAL": 64, "GAMMA_LDS": 128, "GAMMA_GLOBAL": 256,
+             "BF_INPLACE": 512, "BF_DENSE_CONTLDS": 1024, "BF_DENSE_HBM": 2048, "BF_LPR16": 4096, "BF_LPR32": 8192, "BF_LPR64": 16384}
+
+
+def est_form_names(mask: int) -> list:
+    return [k for k, v in EST_FORMS.items() if mask & v]
+
+
 STAT_COUNT = 34
 STAT_X_RPKT_STEPS = 34
 STAT_X_KPKT_STEPS = 35

@@ -1223,6 +1223,11 @@ __device__ inline void scalars_flush(const Env &env) {  // after a __syncthreads
   if (env.scalars_lds != nullptr && threadIdx.x < ARTIS_NSCALARS && env.scalars_lds[threadIdx.x] != 0.)
     unsafeAtomicAdd(&env.E.scalars[threadIdx.x], env.scalars_lds[threadIdx.x]);
 }
+// the estimator form k_thermal<.., TABLES_LDS> takes (its own choice at the top of the kernel): artis_amd_last_estimator_forms
+inline int32_t thermal_est_form(const Env &env, int tables_lds) {
+  if (env.cellest_n_t > 0) return ARTIS_AMD_EST_THERMAL_LDS;
+  return (tables_lds != 2 && env.estcache_on) ? ARTIS_AMD_EST_THERMAL_WAVECACHE : ARTIS_AMD_EST_THERMAL_GLOBAL;
+}
 // call after a __syncthreads(): the workgroup's sums of one estimator go to the global array
 __device__ inline void cellest_flush(const Env &env, int kind, double *global_array, int nthreads) {
   for (int c = threadIdx.x; c < env.cellest_n; c += nthreads) {
@@ -2743,6 +2748,7 @@ struct artis_amd_engine {
   int tq_low = 48;              // ... its low-water mark of walking lanes (ARTIS_AMD_TQ_LOW)
   bool tq_attr_set = false;     // ... its dynamic-LDS attribute has been set on this engine's device
   int32_t thermal_variants = 0; // which instantiations of the thermal kernel the last call launched (artis_amd_last_thermal_variants)
+  int32_t est_forms = 0;        // how its kernels added to the per-cell estimators (artis_amd_last_estimator_forms)
   bool ma_tables_lds = true;  // k_thermal<1024, true>: the static target tables in LDS when they fit (ARTIS_AMD_MATABLES_LDS=0: in HBM)
   // the population's scratch: the collisional-excitation cooling terms of `pop_batch` cells at a time (k_matrans writes them,
   // k_cooling_chain turns them into running sums, k_collexc_filter into the records' cooling filters; nothing of it is kept)
@@ -3943,6 +3949,8 @@ int sort_by_key(artis_amd_engine *e, hipStream_t s, const int32_t *list, const i
 // the estimator updates the propagation launch before it recorded (the cells' cache rows are still resident)
 static int launch_bfest_dense(artis_amd_engine *e, const Env &env, hipStream_t s) {
   const bool lds = e->dense_cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX;
+  e->est_forms |= (lds ? ARTIS_AMD_EST_BF_DENSE_CONTLDS : ARTIS_AMD_EST_BF_DENSE_HBM) |
+                  (e->dense_lpr == 64 ? ARTIS_AMD_EST_BF_LPR64 : (e->dense_lpr == 16 ? ARTIS_AMD_EST_BF_LPR16 : ARTIS_AMD_EST_BF_LPR32));
 #define DENSE_LAUNCH(LPR)                                                                                        \
   if (lds)                                                                                                       \
     hipLaunchKernelGGL((k_bfest_dense<true, DENSE_TB, LPR>), dim3(e->ncu * ARTIS_DENSE_WGS), dim3(DENSE_TB), 0, s, env); \
@@ -3974,6 +3982,7 @@ int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_stream) {
   e->last_parked = 0;
   e->last_pool_resets = 0;
   e->thermal_variants = 0;
+  e->est_forms = 0;
   e->last_fill_ms = 0.;
   for (int k = 0; k < NEXT_NKINDS; k++) {
     e->kms[k] = 0.;
@@ -4067,17 +4076,24 @@ int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_stream) {
         const int grid = (int)std::min<int64_t>(((int64_t)nk + ARTIS_RPKT_TB - 1) / ARTIS_RPKT_TB, (int64_t)e->ncu * ARTIS_RPKT_WGS);  // persistent: every block resident
         const int bud_r = (e->budget_r_small > 0 && nk < e->small_list) ? std::min(e->budget_r_small, e->budget_r) : e->budget_r;
         const int nch = e->wave_chunks_r ? chunks_for(nk, grid * (ARTIS_RPKT_TB / 64)) : 8;
-        if (e->line_lds && e->Mh.nlines <= LINE_LDS_MAX && e->Mh.nlines > 0 && !(env.cellest_n_r > RPKT_CELLEST_CAP))
+        const bool rpkt_line_lds = e->line_lds && e->Mh.nlines <= LINE_LDS_MAX && e->Mh.nlines > 0 && !(env.cellest_n_r > RPKT_CELLEST_CAP);
+        const bool rpkt_cont_lds = !rpkt_line_lds && e->cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX && e->Mh.nbfcontinua > 0 &&
+                                   !(env.cellest_n_r > RPKT_CELLEST_CAP);
+        // (the kernel's own choice, k_rpkt: the workgroup's array for cellest_n_r > 0, else the waves' caches except in the LINE_LDS form)
+        e->est_forms |= env.cellest_n_r > 0 ? (rpkt_line_lds ? ARTIS_AMD_EST_RPKT_LDS_LINE
+                                                             : (rpkt_cont_lds ? ARTIS_AMD_EST_RPKT_LDS_CONT : ARTIS_AMD_EST_RPKT_LDS_NOCONT))
+                                            : ((!rpkt_line_lds && env.estcache_on) ? ARTIS_AMD_EST_RPKT_WAVECACHE : ARTIS_AMD_EST_RPKT_GLOBAL);
+        if (rpkt_line_lds)
           hipLaunchKernelGGL((k_rpkt<false, ARTIS_RPKT_TB, true>), dim3(grid), dim3(ARTIS_RPKT_TB), 0, st, env, lst, nk, next, e->d_stats, bud_r, cursors, nch,
                              (e->drain_r > 0 && nk >= e->drain_min_list) ? e->drain_r : bud_r);
-        else if (e->cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX && e->Mh.nbfcontinua > 0 &&
-            !(env.cellest_n_r > RPKT_CELLEST_CAP))
+        else if (rpkt_cont_lds)
           hipLaunchKernelGGL((k_rpkt<true, ARTIS_RPKT_TB>), dim3(grid), dim3(ARTIS_RPKT_TB), 0, st, env, lst, nk, next, e->d_stats, bud_r, cursors, nch,
                              (e->drain_r > 0 && nk >= e->drain_min_list) ? e->drain_r : bud_r);
         else
           hipLaunchKernelGGL((k_rpkt<false, ARTIS_RPKT_TB>), dim3(grid), dim3(ARTIS_RPKT_TB), 0, st, env, lst, nk, next, e->d_stats, bud_r, cursors, nch,
                              (e->drain_r > 0 && nk >= e->drain_min_list) ? e->drain_r : bud_r);
 #if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
+        if (env.bfev == nullptr) e->est_forms |= ARTIS_AMD_EST_BF_INPLACE;
         if (env.bfev != nullptr) {  // the estimator updates the launch recorded (the cells' cache rows are still resident)
           {
             const int rcd = launch_bfest_dense(e, env, st);
@@ -4110,6 +4126,7 @@ int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_stream) {
           if (cold) e->thermal_variants |= ARTIS_AMD_THERMAL_COLD;
           if (e->thermal_refill && ARTIS_THERMAL_SPLIT_EXACT && env.cellest_n_t == 0 && tq_bytes <= 160 * 1024 - 1024 && nk >= 4096 && e->Mh.nlevels < 32768) {
             e->thermal_variants |= ARTIS_AMD_THERMAL_REFILL;
+            e->est_forms |= ARTIS_AMD_EST_THERMAL_GLOBAL;  // (k_thermal_q keeps no per-cell sums in LDS)
             if (!e->tq_attr_set) {  // (per engine, i.e. per device: the attribute is the device'st, not the process's -- ADVICE r05)
               HIP_TRY(hipFuncSetAttribute((const void *)k_thermal_q<TQ_TB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
               HIP_TRY(hipFuncSetAttribute((const void *)k_thermal_q<TQ_TB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
@@ -4125,13 +4142,16 @@ int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_stream) {
           } else if (e->ma_tables_lds && e->Mh.nlevels <= MA_LDS_LEVELS && e->Mh.nalltrans <= MA_LDS_TRANS && nk >= 4096) {
             const int grid1 = (int)std::min<int64_t>(((int64_t)nk + 1023) / 1024, (int64_t)e->ncu);
             e->thermal_variants |= ARTIS_AMD_THERMAL_LDS_TABLES;
+            e->est_forms |= thermal_est_form(env, 1);
             LAUNCH_T2(k_thermal, 1024, 1, grid1, 1024, 0, env, lst, nk, next, e->d_stats, bud_t, cursors, e->wave_chunks_t ? chunks_for(nk, grid1 * 16) : 8, 0, drain);
           } else if (e->ma_tables_lds && e->Mh.nlevels <= MA_LDS_LEVELS2 && nk >= 4096 && env.cellest_n_t == 0) {
             const int grid1 = (int)std::min<int64_t>(((int64_t)nk + 1023) / 1024, (int64_t)e->ncu);
             e->thermal_variants |= ARTIS_AMD_THERMAL_LDS_LEVELPACK;
+            e->est_forms |= thermal_est_form(env, 2);
             LAUNCH_T2(k_thermal, 1024, 2, grid1, 1024, 0, env, lst, nk, next, e->d_stats, bud_t, cursors, e->wave_chunks_t ? chunks_for(nk, grid1 * 16) : 8, 0, drain);
           } else {
             e->thermal_variants |= ARTIS_AMD_THERMAL_PLAIN;
+            e->est_forms |= thermal_est_form(env, 0);
             LAUNCH_T2(k_thermal, ARTIS_THERMAL_TB, 0, grid, ARTIS_THERMAL_TB, 0, env, lst, nk, next, e->d_stats, bud_t, cursors,
                       per_cu ? 256 : (e->wave_chunks_t ? chunks_for(nk, grid * (ARTIS_THERMAL_TB / 64)) : 8), per_cu ? 2 : 0, drain);
           }
@@ -4318,6 +4338,7 @@ int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_stream) {
         if (rc != ARTIS_OK) return rc;
       } else if (kind == NEXT_GAMMA) {
         const int grid = std::min(nblocks(nk), e->ncu * ARTIS_GAMMA_WAVES);
+        e->est_forms |= env.cellest_n_g > 0 ? ARTIS_AMD_EST_GAMMA_LDS : ARTIS_AMD_EST_GAMMA_GLOBAL;
         hipLaunchKernelGGL(k_gamma, dim3(grid), dim3(BLOCK), 0, s, env, lst, nk, next, e->d_stats, e->budget_g, e->d_cursors,
                            e->wave_chunks_r ? chunks_for(nk, grid * (BLOCK / 64)) : 8);
       } else if (kind == NEXT_MA) {
@@ -4593,6 +4614,11 @@ int artis_amd_last_pool_usage(artis_amd_engine *e, int64_t *units_used, int64_t 
 int artis_amd_last_thermal_variants(artis_amd_engine *e, int32_t *mask) {
   if (!e || !mask) return ARTIS_ERR_ARG;
   *mask = e->thermal_variants;
+  return ARTIS_OK;
+}
+int artis_amd_last_estimator_forms(artis_amd_engine *e, int32_t *mask) {
+  if (!e || !mask) return ARTIS_ERR_ARG;
+  *mask = e->est_forms;
   return ARTIS_OK;
 }
 int artis_amd_last_tiling_parked(artis_amd_engine *e, int64_t *parked) {

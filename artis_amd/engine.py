@@ -80,7 +80,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_last_kernel_table",
     "artis_amd_options_preset",
     "artis_amd_allreduce_estimators", "artis_amd_comm_unique_id", "artis_amd_comm_init", "artis_amd_comm_count",
-    "artis_amd_cache_tiles", "artis_amd_last_tiling", "artis_amd_last_tiling_fills", "artis_amd_last_tiling_parked", "artis_amd_last_pool_resets", "artis_amd_record_tiers", "artis_amd_last_thermal_variants", "artis_amd_last_pool_usage",
+    "artis_amd_cache_tiles", "artis_amd_last_tiling", "artis_amd_last_tiling_fills", "artis_amd_last_tiling_parked", "artis_amd_last_pool_resets", "artis_amd_record_tiers", "artis_amd_last_thermal_variants", "artis_amd_last_estimator_forms", "artis_amd_last_pool_usage",
     "artis_amd_spectra_compute", "artis_amd_spectra_devptr", "artis_amd_spectra_download",
     "artis_amd_radfield_fit", "artis_amd_radfield_download",
 ]
@@ -266,6 +266,13 @@ class Engine:
         m = C.c_int32()
         self.L.artis_amd_last_thermal_variants.argtypes = [C.c_void_p] * 2
         self._check(self.L.artis_amd_last_thermal_variants(self.h, C.byref(m)))
+        return int(m.value)
+
+    def last_estimator_forms(self) -> int:
+        """mask of the ways the last step()'s kernels added to the per-cell estimators (abi.EST_FORMS, include/artis_amd.h ARTIS_AMD_EST_*)"""
+        m = C.c_int32()
+        self.L.artis_amd_last_estimator_forms.argtypes = [C.c_void_p] * 2
+        self._check(self.L.artis_amd_last_estimator_forms(self.h, C.byref(m)))
         return int(m.value)
 
     def last_tiling(self):

@@ -587,6 +587,27 @@ int artis_amd_last_pool_usage(artis_amd_engine *eng, int64_t *units_used, int64_
 #define ARTIS_AMD_THERMAL_COLD 16         /* ... instantiated with the on-demand records' look-ups (the model has cold levels) */
 #define ARTIS_AMD_THERMAL_TAIL 32         /* k_tail took the population's last packets */
 int artis_amd_last_thermal_variants(artis_amd_engine *eng, int32_t *mask);
+/* How the kernels of the last artis_amd_update_packets_device call added to the per-cell estimators, as a mask: the form follows from the
+ * number of non-empty cells (few-cells caps: k_rpkt 512 with the continuum table in LDS, 3072 without it; k_thermal 4096; k_gamma 2048),
+ * the kernel form and the ARTIS_AMD_* switches, and a parity test has to know that the path it means to check is the one that ran.
+ * (k_slow and k_tail always add with device-wide atomics and are not reported.) (ABI 6) */
+#define ARTIS_AMD_EST_RPKT_LDS_CONT 1          /* k_rpkt<true>: the workgroup's LDS array of per-cell sums, continuum table in LDS */
+#define ARTIS_AMD_EST_RPKT_LDS_NOCONT 2        /* k_rpkt<false>: the workgroup's LDS array (up to 3072 cells) without the table */
+#define ARTIS_AMD_EST_RPKT_LDS_LINE 32768      /* k_rpkt<false, .., true> (ARTIS_AMD_LINELDS=1): the LDS array, up to 512 cells */
+#define ARTIS_AMD_EST_RPKT_WAVECACHE 4         /* k_rpkt: every wave's direct-mapped cache of per-cell sums (physics.h est_cache_add) */
+#define ARTIS_AMD_EST_RPKT_GLOBAL 8            /* k_rpkt: device-wide atomics (the LINE_LDS form has no room for the caches) */
+#define ARTIS_AMD_EST_THERMAL_LDS 16           /* k_thermal: the workgroup's LDS array of colheatingestimator sums */
+#define ARTIS_AMD_EST_THERMAL_WAVECACHE 32     /* k_thermal: every wave's cache (est_cache_add_one) */
+#define ARTIS_AMD_EST_THERMAL_GLOBAL 64        /* k_thermal<1024, 2> / k_thermal_q / switched off: device-wide atomics */
+#define ARTIS_AMD_EST_GAMMA_LDS 128            /* k_gamma: the workgroup's LDS array of dep_estimator_gamma sums */
+#define ARTIS_AMD_EST_GAMMA_GLOBAL 256         /* k_gamma: device-wide atomics */
+#define ARTIS_AMD_EST_BF_INPLACE 512           /* detailed bound-free estimators added inside k_rpkt (ARTIS_AMD_BFDEFER=0) */
+#define ARTIS_AMD_EST_BF_DENSE_CONTLDS 1024    /* ... deferred to k_bfest_dense<true>: continuum table in LDS */
+#define ARTIS_AMD_EST_BF_DENSE_HBM 2048        /* ... deferred to k_bfest_dense<false>: continuum table in HBM */
+#define ARTIS_AMD_EST_BF_LPR16 4096            /* k_bfest_dense with 16, 32 or 64 lanes per record (ARTIS_AMD_DENSE_LPR) */
+#define ARTIS_AMD_EST_BF_LPR32 8192
+#define ARTIS_AMD_EST_BF_LPR64 16384
+int artis_amd_last_estimator_forms(artis_amd_engine *eng, int32_t *mask);
 
 /* Per-kernel split of the last artis_amd_update_packets_device call: summed launch durations [ms] and summed
  * packet counts of the r-packet kernel (k_rpkt) and of the thermal kernels (k_ma + k_kpkt). */

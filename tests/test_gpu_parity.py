@@ -5,7 +5,8 @@ Bar: every integer field of every packet (type, cell, next line, emission/absorp
 per-packet RNG state and all event counters are IDENTICAL; floating-point fields agree to FLOAT_RTOL. The only
 source of float differences is the device math library (exp/log/sin/cos/expm1/atan2/pow are not bit-identical to
 glibc); with the same libm the kernel bodies are bit-exact (tests/test_kernel_bodies_vs_oracle.py).
-Estimators are atomic float sums, compared to EST_RTOL of each array's maximum.
+Estimators are atomic float sums, compared to EST_RTOL of each array's maximum AND entry by entry to EST_RTOL of the entry's own
+value, with the same entries zero on both sides (parity.compare_estimators: a dim cell's sums are held to their own size).
 """
 import os
 
@@ -44,7 +45,8 @@ BIG_CASES = {
     # (ARTIS_AMD_CELLEST_LDS=0: a model with few cells keeps its per-cell estimators in the workgroup's LDS, which that form of the kernel
     # leaves to the level table since round 6 -- the 50^3 grid has no such accumulators either)
     "w7big_5cubed_6e3": dict(build=dict(preset="w7big", ncoord=5), npk=6000, pkw=dict(kpkt_fraction=0.8), dense_cells=0,
-                             expect_variants="LDS_LEVELPACK", env={"ARTIS_AMD_CELLEST_LDS": "0"}),
+                             expect_variants="LDS_LEVELPACK", env={"ARTIS_AMD_CELLEST_LDS": "0"},
+                             expect_est_forms="THERMAL_GLOBAL"),  # (k_thermal<1024, 2> keeps no per-cell sums in LDS: device-wide atomics)
     # `cd23like` (406 132 lines, 8 457 levels, directions of hundreds of transitions: k_mafilter_long) with the record tiers the ENGINE chooses
     # when its static rows do not fit the cache budget (forced here to 0.7 of them on a 5^3 grid): static records for the lowest levels of every
     # ion, the rest filled on demand in the shared pool by the slow-path kernel's waves, k_thermal<256, 0, COLD>; 3.2e8 transitions
@@ -266,6 +268,9 @@ def test_engine_matches_oracle_large_cases(engine_mod, oracle_big, name, monkeyp
         got = eng.last_thermal_variants()
         assert got & want == want, f"{name}: thermal kernel forms launched {got:#x}, expected {want:#x} among them"
         print(f"{name}: thermal kernel forms {got:#x}, pool resets {eng.last_tiling()['pool_resets']}")
+    if "expect_est_forms" in case:
+        got = eng.last_estimator_forms()
+        assert got & abi.EST_FORMS[case["expect_est_forms"]], f"{name}: estimator forms {abi.est_form_names(got)}"
     rep = parity.compare_packets(pb, pa, FLOAT_RTOL, f"{name}: HIP engine vs oracle")
     parity.compare_stats(eb, ea, f"{name}: HIP engine vs oracle", same_libm=False)
     parity.compare_estimators(eb, ea, EST_RTOL, f"{name}: HIP engine vs oracle")
