@@ -501,3 +501,50 @@ def radfield_config(prev_mid: float, deltat: float, nprocs: int, assocvolume_tmi
                          lte_iteration=int(bool(lte_iteration)), assocvolume_tmin=vol.ctypes.data_as(_F64P),
                          bfrate_normed_seed=seed.ctypes.data_as(_F32P) if seed is not None else None)
     return cfg, (vol, seed)
+
+
+# ionisation balance and hand-over of the grid update (include/artis_amd.h artis_amd_grid_update*)
+IONBAL_NEUTRAL, IONBAL_MAXIT, IONBAL_PHI_OVERFLOW, IONBAL_FRAC_ZEROED = 1, 2, 4, 8
+IONBAL_NOT_BRACKETED, IONBAL_INVALID_U, IONBAL_NONFINITE, IONBAL_FORCED_SAHA = 16, 32, 64, 128
+IONBAL_FLAGS = ["neutral", "maxit", "phi_overflow", "frac_zeroed", "not_bracketed", "invalid_u", "nonfinite", "forced_saha"]
+IONBAL_NTIMES = 4
+
+
+class GridUpdate(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("use_fit", C.c_int32), ("TJ", _F32P), ("TR", _F32P), ("W", _F32P), ("Te", _F32P),
+                ("rho", _F32P), ("elem_massfracs", _F32P), ("elem_meanweight", _F32P), ("thick", _I32P), ("kappagrey", _F32P),
+                ("clumpfactor", _F32P), ("ffegrp", _F32P)]
+
+
+class GridUpdateResult(C.Structure):
+    _fields_ = [("struct_size", C.c_int64)] + [(k, _F32P) for k in ("Te", "TJ", "TR", "W", "nne", "nnetot", "rho", "ion_partfuncts",
+                                                                      "ion_groundlevelpops")] + \
+               [("uppermost_ion", _I32P), ("gamma_normed", _F64P), ("phi", _F64P), ("nne_root", _F32P), ("flags", _I32P), ("evals", _I32P),
+                ("ncells_flagged", C.c_int64 * 8), ("total_evals", C.c_int64), ("npts_nonempty", C.c_int32), ("nions", C.c_int32),
+                ("nelements", C.c_int32), ("nbfcontinua_ground", C.c_int32), ("kernel_ms", C.c_double * IONBAL_NTIMES)]
+
+
+def grid_update_arrays(ncell: int, nions: int, nelements: int, nbfg: int) -> dict:
+    """zeroed host arrays for every output of artis_grid_update_result (the keys are its field names)"""
+    out = {k: np.zeros(ncell, np.float32) for k in ("Te", "TJ", "TR", "W", "nne", "nnetot", "rho", "nne_root")}
+    out.update(ion_partfuncts=np.zeros(ncell * nions, np.float32), ion_groundlevelpops=np.zeros(ncell * nions, np.float32),
+               uppermost_ion=np.zeros(ncell * nelements, np.int32), gamma_normed=np.zeros(max(ncell * nbfg, 1)), phi=np.zeros(ncell * nions),
+               flags=np.zeros(ncell, np.int32), evals=np.zeros(ncell, np.int32))
+    return out
+
+
+def grid_update_config(use_fit: bool, rho, elem_massfracs, thick, elem_meanweight=None, TJ=None, TR=None, W=None, Te=None,
+                       kappagrey=None, clumpfactor=None, ffegrp=None):
+    """(GridUpdate, the arrays it points into: keep them alive while it is used); None: a NULL pointer"""
+    keep = {}
+    u = GridUpdate(struct_size=C.sizeof(GridUpdate), use_fit=int(bool(use_fit)))
+    for k, v, dt, pt in (("TJ", TJ, np.float32, _F32P), ("TR", TR, np.float32, _F32P), ("W", W, np.float32, _F32P),
+                         ("Te", Te, np.float32, _F32P), ("rho", rho, np.float32, _F32P), ("elem_massfracs", elem_massfracs, np.float32, _F32P),
+                         ("elem_meanweight", elem_meanweight, np.float32, _F32P), ("thick", thick, np.int32, _I32P),
+                         ("kappagrey", kappagrey, np.float32, _F32P), ("clumpfactor", clumpfactor, np.float32, _F32P),
+                         ("ffegrp", ffegrp, np.float32, _F32P)):
+        if v is None:
+            continue
+        keep[k] = np.ascontiguousarray(v, dtype=dt)
+        setattr(u, k, keep[k].ctypes.data_as(pt))
+    return u, keep

@@ -26,6 +26,7 @@
 #include "model_build.h"
 #include "physics.h"
 #include "radfield_fit.h"
+#include "ion_balance.h"
 #include "spectra.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -2553,6 +2554,8 @@ void spec_free_scratch(SpecState *st) {
 
 struct RfState;  // artis_amd_radfield_*: defined with them at the end of this file
 void rf_free(RfState *st);
+struct IbState;  // artis_amd_grid_update*: likewise
+void ib_free(IbState *st);
 
 void spec_free(SpecState *st) {
   if (!st) return;
@@ -2570,6 +2573,8 @@ struct artis_amd_engine {
   int device = 0;
   SpecState *spec = nullptr;  // artis_amd_spectra_*: nothing until the first call
   RfState *rf = nullptr;      // artis_amd_radfield_*: nothing until the first call
+  IbState *ib = nullptr;      // artis_amd_grid_update*: nothing until the first call
+  bool fit_since_step = false;  // an artis_amd_radfield_fit since the last propagation call (artis_amd_grid_update use_fit)
   ModelOwned own;
   std::vector<void *> model_allocs;
   std::vector<void *> cell_allocs;
@@ -3464,6 +3469,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   free_packet_buffers(e);
   spec_free(e->spec);
   rf_free(e->rf);
+  ib_free(e->ib);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->d_krow, e->d_fill_cells, e->d_waiting,
                   e->d_bfrate_kept, e->d_collexc_terms, e->d_visit_counts};
@@ -3974,6 +3980,7 @@ int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_stream) {
     return ARTIS_ERR_ARG;
   }
   HIP_TRY(hipSetDevice(e->device));
+  e->fit_since_step = false;
   hipStream_t s = (hipStream_t)hip_stream;
   e->last_propagate_ms = 0.;
   e->last_nlaunches = 0;
@@ -5080,6 +5087,8 @@ struct RfState {
   unsigned long long *d_totals = nullptr;
   hipEvent_t ev[3] = {};
   bool valid = false;
+  double prev_mid = 0., deltat = 0.;  // the normalisation of the last fit (artis_amd_grid_update reads it)
+  int32_t nprocs = 1, lte = 0;
   unsigned long long totals[ARTIS_RADFIELD_NCOUNTS] = {};
   double kernel_ms[2] = {};
 };
@@ -5238,7 +5247,12 @@ int artis_amd_radfield_fit(artis_amd_engine *e, const artis_radfield_config *cfg
   HIP_TRY(hipEventElapsedTime(&ms1, st->ev[1], st->ev[2]));
   st->kernel_ms[0] = ms0;
   st->kernel_ms[1] = ms1;
+  st->prev_mid = cfg->prev_mid;
+  st->deltat = cfg->deltat;
+  st->nprocs = cfg->nprocs;
+  st->lte = a.lte;
   st->valid = true;
+  e->fit_since_step = true;
   return ARTIS_OK;
 }
 
@@ -5281,6 +5295,463 @@ int artis_amd_radfield_download(artis_amd_engine *e, artis_radfield *out) {
   out->detailed_linecount = (int32_t)st->nline;
   out->kernel_ms[0] = st->kernel_ms[0];
   out->kernel_ms[1] = st->kernel_ms[1];
+  return ARTIS_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ ionisation balance and hand-over (ion_balance.h)
+// Kernels on the caller's stream, every output element with one writer: k_ib_alpha_sp (first call: the [nions][TABLESIZE]
+// ion_alpha_sp table and each ion's ground-continuum index), k_ib_cells (one lane per cell: temperatures, nnetot), k_ib_gamma (one
+// lane per (cell, ground continuum): the normalised gamma estimator), k_ib_partfunct (one lane per (cell, ion), levels summed in
+// order), k_ib_phi (one lane per (cell, ion): phi once, into a [cell][ion] array), k_ib_solve (one lane per cell: uppermost ions,
+// n_e root search, ground populations, final n_e). Flags are integer ORs. Nothing reaches the engine's cell state until every
+// cell has been balanced; then the arrays are copied over and the cell cache is filled.
+namespace {
+
+struct IbArgs {
+  artis::DevModel M;
+  int64_t ncell;
+  int32_t use_fit, lte, nbfg;
+  // inputs
+  const float *fit_TJ, *fit_TR, *fit_W, *fit_Te;  // the fit's (use_fit) or the host's (uploaded)
+  const int32_t *fit_flags;                       // the fit's per-cell flags (use_fit)
+  const float *host_Te;                           // Te override of fitted cells, or null
+  const float *cur_ground;                        // the cell state's ground populations (for the partition functions)
+  const int32_t *cur_thick;                       // ... thickness (the balance's Saha switch)
+  const double *gamma_raw;                        // [cell][ground continuum][2]{gamma, bfheating} of the estimator block
+  const double *assocvol;
+  double prev_mid, tmin, deltat;
+  int32_t nprocs;
+  const float *rho, *massfrac, *meanweight_cell, *meanweight_model, *clump;
+  // scratch / outputs
+  float *alpha_sp;
+  int32_t *gci;
+  float *TJ, *TR, *W, *Te, *nnetot, *U, *ground, *nne, *nne_root;
+  double *gamma, *phi;
+  int32_t *uppermost, *flags, *evals;
+};
+
+__global__ void __launch_bounds__(BLOCK) k_ib_alpha_sp(IbArgs a) {
+  const artis::DevModel &M = a.M;
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= (int64_t)M.nions * ARTIS_OPT_TABLESIZE) return;
+  const int ui = (int)(i / ARTIS_OPT_TABLESIZE);
+  const int tempindex = (int)(i - (int64_t)ui * ARTIS_OPT_TABLESIZE);
+  const int element = M.ion_element[ui];
+  const int ion = ui - M.elem_uniqueionindexstart[element];
+  float v = 0.f;
+  if (ion < M.elem_nions[element] - 1) {
+    const auto T_e = static_cast<float>(M.temperature_grid[tempindex]);
+    v = static_cast<float>(artis_ib::ionrecombcoeff_lte_targetpop(M, T_e, element, ion + 1));
+  }
+  a.alpha_sp[i] = v;
+  if (tempindex == 0) a.gci[ui] = artis_ib::ion_groundcontindex(M, element, ion);
+}
+
+__device__ inline const float *ib_meanweight(const IbArgs &a, int64_t c) {
+  return a.meanweight_cell ? a.meanweight_cell + c * a.M.nelements : a.meanweight_model;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_ib_cells(IbArgs a) {
+  const int64_t c = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (c >= a.ncell) return;
+  float Te = a.fit_Te[c];
+  if (a.use_fit && a.host_Te && (a.fit_flags[c] & ARTIS_RADFIELD_FITTED)) Te = a.host_Te[c];
+  a.Te[c] = Te;
+  a.TJ[c] = a.fit_TJ[c];
+  a.TR[c] = a.fit_TR[c];
+  a.W[c] = a.fit_W[c];
+  a.nnetot[c] = artis_ib::nnetot(a.M, a.massfrac + c * a.M.nelements, ib_meanweight(a, c), a.rho[c]);
+  a.flags[c] = (a.lte || a.cur_thick[c] == ARTIS_CELL_THICK) ? artis_ib::FORCED_SAHA : 0;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_ib_gamma(IbArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.ncell * a.nbfg) return;
+  double g = 0.;
+  if (a.use_fit) {
+    const int64_t c = i / a.nbfg;
+    double estimator_normfactor, over4pi;
+    artis_rf::cell_normfactors(a.assocvol[c], a.prev_mid, a.tmin, a.deltat, a.nprocs, &estimator_normfactor, &over4pi);
+    g = a.gamma_raw[2 * i] * (estimator_normfactor / artis_rf::H);
+  }
+  a.gamma[i] = g;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_ib_partfunct(IbArgs a) {
+  const artis::DevModel &M = a.M;
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.ncell * M.nions) return;
+  const int64_t c = i / M.nions;
+  const int ui = (int)(i - c * M.nions);
+  const int element = M.ion_element[ui];
+  const int ion = ui - M.elem_uniqueionindexstart[element];
+  const float T_exc = ARTIS_OPT_LTEPOP_EXCITATION_USE_TJ ? a.TJ[c] : a.Te[c];
+  int32_t flags = 0;
+  a.U[i] = artis_ib::partfunct(M, element, ion, a.cur_ground[i], a.massfrac[c * M.nelements + element], T_exc, &flags);
+  if (flags) atomicOr(&a.flags[c], flags);
+}
+
+__global__ void __launch_bounds__(BLOCK) k_ib_phi(IbArgs a) {
+  const artis::DevModel &M = a.M;
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= a.ncell * M.nions) return;
+  const int64_t c = i / M.nions;
+  const int ui = (int)(i - c * M.nions);
+  const int element = M.ion_element[ui];
+  const int ion = ui - M.elem_uniqueionindexstart[element];
+  double phi = 0.;
+  if (ion < M.elem_nions[element] - 1) {
+    const bool force_saha = (a.flags[c] & artis_ib::FORCED_SAHA) != 0;
+    if (artis_ib::use_phi_saha(force_saha)) {
+      phi = artis_ib::phi_saha(M, element, ion, a.U[i], a.U[i + 1], a.Te[c]);
+    } else {
+      const int g = a.gci[ui];
+      phi = artis_ib::phi_rate_balance(M, a.alpha_sp, element, ion, a.U[i], a.Te[c], a.clump[c], g >= 0 ? a.gamma[c * a.nbfg + g] : 0.);
+    }
+  }
+  a.phi[i] = phi;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_ib_solve(IbArgs a) {
+  const artis::DevModel &M = a.M;
+  const int64_t c = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (c >= a.ncell) return;
+  int32_t flags = a.flags[c];
+  const artis_ib::Cell cell{a.rho[c], a.massfrac + c * M.nelements, ib_meanweight(a, c), a.U + c * M.nions, a.phi + c * M.nions,
+                            a.gamma + c * a.nbfg, a.gci, a.uppermost + c * M.nelements};
+  float nne_root = 0.f;
+  int evals = 0;
+  float nne = 0.f;
+  float *ground = a.ground + c * M.nions;
+  if (flags & artis_ib::REFUSED) {  // an invalid partition function: nothing to balance
+    for (int i = 0; i < M.nions; i++) ground[i] = 0.f;
+    for (int e = 0; e < M.nelements; e++) cell.uppermost[e] = -1;
+  } else {
+    nne = artis_ib::ion_balance_nne(M, cell, (flags & artis_ib::FORCED_SAHA) != 0, ground, &nne_root, &evals, &flags);
+    if (flags & artis_ib::REFUSED)
+      for (int i = 0; i < M.nions; i++) ground[i] = 0.f;
+  }
+  a.nne[c] = nne;
+  a.nne_root[c] = nne_root;
+  a.evals[c] = evals;
+  a.flags[c] = flags;
+}
+
+// corrphotoionrenorm = 1 in the cells balanced with forced Saha (update_grid.cc:539-543)
+__global__ void __launch_bounds__(BLOCK) k_ib_renorm(double *renorm, const int32_t *flags, int64_t ncell, int32_t nbfg) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= ncell * nbfg) return;
+  if (flags[i / nbfg] & artis_ib::FORCED_SAHA) renorm[i] = 1.;
+}
+
+// the scratch of artis_amd_grid_update*: one block, made at the first call
+struct IbState {
+  void *d_block = nullptr;
+  size_t bytes = 0;
+  int64_t ncell = 0, nions = 0, nelements = 0, nbfg = 0;
+  float *d_alpha_sp = nullptr, *d_hTJ = nullptr, *d_hTR = nullptr, *d_hW = nullptr, *d_hTe = nullptr;
+  int32_t *d_gci = nullptr, *d_thick = nullptr;
+  float *d_rho = nullptr, *d_massfrac = nullptr, *d_meanweight = nullptr, *d_kappagrey = nullptr, *d_clump = nullptr, *d_ffegrp = nullptr;
+  float *d_TJ = nullptr, *d_TR = nullptr, *d_W = nullptr, *d_Te = nullptr, *d_nnetot = nullptr, *d_U = nullptr, *d_ground = nullptr;
+  float *d_nne = nullptr, *d_nne_root = nullptr;
+  double *d_gamma = nullptr, *d_phi = nullptr;
+  int32_t *d_uppermost = nullptr, *d_flags = nullptr, *d_evals = nullptr;
+  hipEvent_t ev[ARTIS_IONBAL_NTIMES + 1] = {};
+  bool have_alpha_sp = false, valid = false;
+  int64_t ncells_flagged[8] = {}, total_evals = 0;
+  double kernel_ms[ARTIS_IONBAL_NTIMES] = {};
+};
+
+void ib_free(IbState *st) {
+  if (!st) return;
+  if (st->d_block) (void)hipFree(st->d_block);
+  for (hipEvent_t ev : st->ev)
+    if (ev) (void)hipEventDestroy(ev);
+  delete st;
+}
+
+int ib_error(int rc, const std::string &msg) {
+  g_last_error = "grid_update: " + msg;
+  return rc;
+}
+
+size_t ib_layout(IbState *st, char *base) {
+  size_t off = 0;
+  auto take = [&](auto **p, int64_t count, size_t elem) {
+    const size_t sz = ((size_t)(count > 0 ? count : 0) * elem + 255) & ~(size_t)255;
+    if (base) *p = count > 0 ? (std::remove_reference_t<decltype(*p)>)(base + off) : nullptr;
+    off += sz;
+  };
+  const int64_t n = st->ncell, ni = st->nions, ne = st->nelements;
+  take(&st->d_alpha_sp, ni * ARTIS_OPT_TABLESIZE, sizeof(float));
+  take(&st->d_gci, ni, sizeof(int32_t));
+  for (float **p : {&st->d_hTJ, &st->d_hTR, &st->d_hW, &st->d_hTe, &st->d_rho, &st->d_kappagrey, &st->d_clump, &st->d_ffegrp, &st->d_TJ,
+                    &st->d_TR, &st->d_W, &st->d_Te, &st->d_nnetot, &st->d_nne, &st->d_nne_root})
+    take(p, n, sizeof(float));
+  take(&st->d_thick, n, sizeof(int32_t));
+  take(&st->d_massfrac, n * ne, sizeof(float));
+  take(&st->d_meanweight, n * ne, sizeof(float));
+  take(&st->d_U, n * ni, sizeof(float));
+  take(&st->d_ground, n * ni, sizeof(float));
+  take(&st->d_gamma, n * st->nbfg, sizeof(double));
+  take(&st->d_phi, n * ni, sizeof(double));
+  take(&st->d_uppermost, n * ne, sizeof(int32_t));
+  take(&st->d_flags, n, sizeof(int32_t));
+  take(&st->d_evals, n, sizeof(int32_t));
+  return off;
+}
+
+int ib_init(artis_amd_engine *e) {
+  if (e->ib) return ARTIS_OK;
+  const DevModel &h = e->Mh;
+  // the per-cell solve holds one element's ion fractions in registers / scratch of MAXIONS entries
+  std::vector<int32_t> nions((size_t)(h.nelements > 0 ? h.nelements : 1));
+  if (h.nelements > 0)
+    HIP_TRY(hipMemcpy(nions.data(), e->M.elem_nions, sizeof(int32_t) * (size_t)h.nelements, hipMemcpyDeviceToHost));
+  for (int el = 0; el < h.nelements; el++)
+    if (nions[(size_t)el] > artis_ib::MAXIONS)
+      return ib_error(ARTIS_ERR_UNSUPPORTED, "an element has more than " + std::to_string(artis_ib::MAXIONS) + " ions");
+  IbState *st = new IbState();
+  st->ncell = h.npts_nonempty;
+  st->nions = h.nions;
+  st->nelements = h.nelements;
+  st->nbfg = h.nbfcontinua_ground;
+  st->bytes = ib_layout(st, nullptr);
+  size_t free_b = 0, total_b = 0;
+  hipError_t err = hipMemGetInfo(&free_b, &total_b);
+  if (err == hipSuccess && (double)st->bytes > 0.9 * (double)free_b) {
+    delete st;
+    return ib_error(ARTIS_ERR_ARG, "the scratch does not fit the free device memory");
+  }
+  if (err == hipSuccess) err = hipMalloc(&st->d_block, st->bytes);
+  if (err == hipSuccess) err = hipMemset(st->d_block, 0, st->bytes);
+  for (hipEvent_t &ev : st->ev)
+    if (err == hipSuccess) err = hipEventCreate(&ev);
+  if (err != hipSuccess) {
+    ib_free(st);
+    return ib_error(ARTIS_ERR_HIP, std::string("allocation of the scratch: ") + hipGetErrorString(err));
+  }
+  ib_layout(st, (char *)st->d_block);
+  e->ib = st;
+  return ARTIS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int artis_amd_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream) {
+  if (!e || !u || !ts_next) return ib_error(ARTIS_ERR_ARG, "null engine, update or timestep");
+#ifdef ARTIS_PRESET_NLTENEBULAR
+  return ib_error(ARTIS_ERR_UNSUPPORTED, "this build has NLTE populations (the nebular family): the ion balance is the host's");
+#endif
+  if (u->struct_size != (int64_t)sizeof(artis_grid_update)) return ib_error(ARTIS_ERR_ARG, "artis_grid_update.struct_size does not match");
+  if (!e->have_cells) return ib_error(ARTIS_ERR_ARG, "no cell state (artis_amd_set_cellstate)");
+  if (u->use_fit != 0 && u->use_fit != 1) return ib_error(ARTIS_ERR_ARG, "use_fit must be 0 or 1");
+  if (u->use_fit && (!e->rf || !e->rf->valid || !e->fit_since_step))
+    return ib_error(ARTIS_ERR_ARG, "use_fit = 1 needs an artis_amd_radfield_fit since the last propagation call");
+  if (!u->use_fit && (!u->TJ || !u->TR || !u->W || !u->Te)) return ib_error(ARTIS_ERR_ARG, "use_fit = 0 needs TJ, TR, W and Te");
+  if (!u->rho || !u->elem_massfracs || !u->thick) return ib_error(ARTIS_ERR_ARG, "rho, elem_massfracs and thick are required");
+  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !u->elem_meanweight)
+    return ib_error(ARTIS_ERR_ARG, "this build has USE_CALCULATED_MEANATOMICWEIGHT: elem_meanweight is required");
+  if (!ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !e->M.elem_meannucmass)
+    return ib_error(ARTIS_ERR_ARG, "the element number densities need artis_model.elem_meannucmass");
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = ib_init(e);
+  if (rc != ARTIS_OK) return rc;
+  IbState *st = e->ib;
+  st->valid = false;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const int64_t n = st->ncell, ni = st->nions, ne = st->nelements;
+  auto put = [&](void *dst, const void *src, int64_t count, size_t elem) -> hipError_t {
+    if (!src || count <= 0) return hipSuccess;
+    return hipMemcpyAsync(dst, src, elem * (size_t)count, hipMemcpyHostToDevice, s);
+  };
+  HIP_TRY(put(st->d_rho, u->rho, n, sizeof(float)));
+  HIP_TRY(put(st->d_massfrac, u->elem_massfracs, n * ne, sizeof(float)));
+  HIP_TRY(put(st->d_thick, u->thick, n, sizeof(int32_t)));
+  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT) HIP_TRY(put(st->d_meanweight, u->elem_meanweight, n * ne, sizeof(float)));
+  HIP_TRY(put(st->d_kappagrey, u->kappagrey, n, sizeof(float)));
+  HIP_TRY(put(st->d_clump, u->clumpfactor, n, sizeof(float)));
+  HIP_TRY(put(st->d_ffegrp, u->ffegrp, n, sizeof(float)));
+  if (!u->use_fit) {
+    HIP_TRY(put(st->d_hTJ, u->TJ, n, sizeof(float)));
+    HIP_TRY(put(st->d_hTR, u->TR, n, sizeof(float)));
+    HIP_TRY(put(st->d_hW, u->W, n, sizeof(float)));
+  }
+  if (u->Te) HIP_TRY(put(st->d_hTe, u->Te, n, sizeof(float)));
+  IbArgs a{};
+  a.M = e->M;
+  a.ncell = n;
+  a.use_fit = u->use_fit;
+  a.lte = u->use_fit ? e->rf->lte : 1;
+  a.nbfg = (int32_t)st->nbfg;
+  a.fit_TJ = u->use_fit ? e->rf->d_TJ : st->d_hTJ;
+  a.fit_TR = u->use_fit ? e->rf->d_TR : st->d_hTR;
+  a.fit_W = u->use_fit ? e->rf->d_W : st->d_hW;
+  a.fit_Te = u->use_fit ? e->rf->d_Te : st->d_hTe;
+  a.fit_flags = u->use_fit ? e->rf->d_flags : nullptr;
+  a.host_Te = (u->use_fit && u->Te) ? st->d_hTe : nullptr;
+  a.cur_ground = e->C.ion_groundlevelpops;
+  a.cur_thick = e->C.thick;
+  a.gamma_raw = e->E.gammaestimator;
+  if (u->use_fit) {
+    a.assocvol = e->rf->d_assocvol;
+    a.prev_mid = e->rf->prev_mid;
+    a.deltat = e->rf->deltat;
+    a.nprocs = e->rf->nprocs;
+  }
+  a.tmin = e->model_copy.tmin;
+  a.rho = st->d_rho;
+  a.massfrac = st->d_massfrac;
+  a.meanweight_cell = ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT ? st->d_meanweight : nullptr;
+  a.meanweight_model = e->M.elem_meannucmass;
+  a.clump = u->clumpfactor ? st->d_clump : e->C.clumpfactor;
+  a.alpha_sp = st->d_alpha_sp;
+  a.gci = st->d_gci;
+  a.TJ = st->d_TJ;
+  a.TR = st->d_TR;
+  a.W = st->d_W;
+  a.Te = st->d_Te;
+  a.nnetot = st->d_nnetot;
+  a.U = st->d_U;
+  a.ground = st->d_ground;
+  a.nne = st->d_nne;
+  a.nne_root = st->d_nne_root;
+  a.gamma = st->d_gamma;
+  a.phi = st->d_phi;
+  a.uppermost = st->d_uppermost;
+  a.flags = st->d_flags;
+  a.evals = st->d_evals;
+  // every kernel is checked where it ends, so that an error names it (the calls are few and the kernels short)
+  auto done = [&](const char *kernel) -> int {
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    if (err != hipSuccess) return ib_error(ARTIS_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(err));
+    return ARTIS_OK;
+  };
+  if (!st->have_alpha_sp && ni > 0) {  // kept for the engine's lifetime
+    hipLaunchKernelGGL(k_ib_alpha_sp, dim3(nblocks(ni * ARTIS_OPT_TABLESIZE)), dim3(BLOCK), 0, s, a);
+    if ((rc = done("k_ib_alpha_sp")) != ARTIS_OK) return rc;
+    st->have_alpha_sp = true;
+  }
+  HIP_TRY(hipEventRecord(st->ev[0], s));
+  if (n > 0) {
+    hipLaunchKernelGGL(k_ib_cells, dim3(nblocks(n)), dim3(BLOCK), 0, s, a);
+    if ((rc = done("k_ib_cells")) != ARTIS_OK) return rc;
+    if (st->nbfg > 0) hipLaunchKernelGGL(k_ib_gamma, dim3(nblocks(n * st->nbfg)), dim3(BLOCK), 0, s, a);
+    if ((rc = done("k_ib_gamma")) != ARTIS_OK) return rc;
+    if (ni > 0) hipLaunchKernelGGL(k_ib_partfunct, dim3(nblocks(n * ni)), dim3(BLOCK), 0, s, a);
+    if ((rc = done("k_ib_partfunct")) != ARTIS_OK) return rc;
+  }
+  HIP_TRY(hipEventRecord(st->ev[1], s));
+  if (n > 0 && ni > 0) hipLaunchKernelGGL(k_ib_phi, dim3(nblocks(n * ni)), dim3(BLOCK), 0, s, a);
+  if ((rc = done("k_ib_phi")) != ARTIS_OK) return rc;
+  HIP_TRY(hipEventRecord(st->ev[2], s));
+  if (n > 0) hipLaunchKernelGGL(k_ib_solve, dim3(nblocks(n)), dim3(BLOCK), 0, s, a);
+  if ((rc = done("k_ib_solve")) != ARTIS_OK) return rc;
+  HIP_TRY(hipEventRecord(st->ev[3], s));
+  std::vector<int32_t> flags((size_t)n), evals((size_t)n);
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(flags.data(), st->d_flags, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(evals.data(), st->d_evals, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int k = 0; k < 3; k++) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, st->ev[k], st->ev[k + 1]));
+    st->kernel_ms[k] = ms;
+  }
+  st->kernel_ms[3] = 0.;
+  int64_t refused = 0;
+  std::fill(std::begin(st->ncells_flagged), std::end(st->ncells_flagged), 0);
+  st->total_evals = 0;
+  for (int64_t c = 0; c < n; c++) {
+    for (int k = 0; k < 8; k++)
+      if (flags[(size_t)c] & (1 << k)) st->ncells_flagged[k]++;
+    if (flags[(size_t)c] & artis_ib::REFUSED) refused++;
+    st->total_evals += evals[(size_t)c];
+  }
+  st->valid = true;
+  if (refused > 0)
+    return ib_error(ARTIS_ERR_NOTCONVERGED, std::to_string(refused) + " cells unbracketed, non-finite or with an invalid partition function (" +
+                                                std::to_string(st->ncells_flagged[4]) + " / " + std::to_string(st->ncells_flagged[6]) + " / " +
+                                                std::to_string(st->ncells_flagged[5]) + "); the previous cell state stays");
+  // the hand-over: the engine's cell state becomes the result (artis_amd_set_cellstate), then the cell cache is filled
+  auto d2d = [&](const void *dst, const void *src, int64_t count, size_t elem) -> hipError_t {
+    if (!dst || !src || count <= 0) return hipSuccess;
+    return hipMemcpyAsync(const_cast<void *>(dst), src, elem * (size_t)count, hipMemcpyDeviceToDevice, s);
+  };
+  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !e->C.elem_meanweight && n * ne > 0) {
+    float *d = nullptr;
+    HIP_TRY(hipMalloc((void **)&d, sizeof(float) * (size_t)(n * ne)));
+    e->cell_allocs.push_back(d);
+    e->C.elem_meanweight = d;
+  }
+  HIP_TRY(d2d(e->C.rho, st->d_rho, n, sizeof(float)));
+  HIP_TRY(d2d(e->C.Te, st->d_Te, n, sizeof(float)));
+  HIP_TRY(d2d(e->C.TJ, st->d_TJ, n, sizeof(float)));
+  HIP_TRY(d2d(e->C.TR, st->d_TR, n, sizeof(float)));
+  HIP_TRY(d2d(e->C.W, st->d_W, n, sizeof(float)));
+  HIP_TRY(d2d(e->C.nne, st->d_nne, n, sizeof(float)));
+  HIP_TRY(d2d(e->C.nnetot, st->d_nnetot, n, sizeof(float)));
+  HIP_TRY(d2d(e->C.ion_partfuncts, st->d_U, n * ni, sizeof(float)));
+  HIP_TRY(d2d(e->C.ion_groundlevelpops, st->d_ground, n * ni, sizeof(float)));
+  HIP_TRY(d2d(e->C.elem_massfracs, st->d_massfrac, n * ne, sizeof(float)));
+  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT) HIP_TRY(d2d(e->C.elem_meanweight, st->d_meanweight, n * ne, sizeof(float)));
+  if (u->kappagrey) HIP_TRY(d2d(e->C.kappagrey, st->d_kappagrey, n, sizeof(float)));
+  if (u->clumpfactor) HIP_TRY(d2d(e->C.clumpfactor, st->d_clump, n, sizeof(float)));
+  if (u->ffegrp) HIP_TRY(d2d(e->C.ffegrp, st->d_ffegrp, n, sizeof(float)));
+  if (ARTIS_OPT_USE_LUT_PHOTOION && n > 0 && st->nbfg > 0) {
+    hipLaunchKernelGGL(k_ib_renorm, dim3(nblocks(n * st->nbfg)), dim3(BLOCK), 0, s, const_cast<double *>(e->C.corrphotoionrenorm),
+                       st->d_flags, n, (int32_t)st->nbfg);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(d2d(e->C.thick, st->d_thick, n, sizeof(int32_t)));  // (after the balance and the renormalisation, which read the current ones)
+  HIP_TRY(hipStreamSynchronize(s));
+  e->S = make_step(*ts_next);
+  const auto t0 = std::chrono::steady_clock::now();
+  rc = artis_amd_populate_cellcache(e, hip_stream);
+  st->kernel_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+int artis_amd_grid_update_download(artis_amd_engine *e, artis_grid_update_result *out) {
+  if (!e || !out) return ib_error(ARTIS_ERR_ARG, "null argument");
+  if (out->struct_size != (int64_t)sizeof(artis_grid_update_result))
+    return ib_error(ARTIS_ERR_ARG, "artis_grid_update_result.struct_size does not match");
+  if (!e->ib || !e->ib->valid) return ib_error(ARTIS_ERR_ARG, "nothing balanced (artis_amd_grid_update)");
+  IbState *st = e->ib;
+  HIP_TRY(hipSetDevice(e->device));
+  const int64_t n = st->ncell, ni = st->nions, ne = st->nelements;
+  auto get = [&](void *dst, const void *src, int64_t count, size_t elem) -> hipError_t {
+    if (!dst || count <= 0) return hipSuccess;
+    return hipMemcpy(dst, src, elem * (size_t)count, hipMemcpyDeviceToHost);
+  };
+  HIP_TRY(get(out->Te, st->d_Te, n, sizeof(float)));
+  HIP_TRY(get(out->TJ, st->d_TJ, n, sizeof(float)));
+  HIP_TRY(get(out->TR, st->d_TR, n, sizeof(float)));
+  HIP_TRY(get(out->W, st->d_W, n, sizeof(float)));
+  HIP_TRY(get(out->nne, st->d_nne, n, sizeof(float)));
+  HIP_TRY(get(out->nnetot, st->d_nnetot, n, sizeof(float)));
+  HIP_TRY(get(out->rho, st->d_rho, n, sizeof(float)));
+  HIP_TRY(get(out->ion_partfuncts, st->d_U, n * ni, sizeof(float)));
+  HIP_TRY(get(out->ion_groundlevelpops, st->d_ground, n * ni, sizeof(float)));
+  HIP_TRY(get(out->uppermost_ion, st->d_uppermost, n * ne, sizeof(int32_t)));
+  HIP_TRY(get(out->gamma_normed, st->d_gamma, n * st->nbfg, sizeof(double)));
+  HIP_TRY(get(out->phi, st->d_phi, n * ni, sizeof(double)));
+  HIP_TRY(get(out->nne_root, st->d_nne_root, n, sizeof(float)));
+  HIP_TRY(get(out->flags, st->d_flags, n, sizeof(int32_t)));
+  HIP_TRY(get(out->evals, st->d_evals, n, sizeof(int32_t)));
+  for (int k = 0; k < 8; k++) out->ncells_flagged[k] = st->ncells_flagged[k];
+  out->total_evals = st->total_evals;
+  out->npts_nonempty = (int32_t)n;
+  out->nions = (int32_t)ni;
+  out->nelements = (int32_t)ne;
+  out->nbfcontinua_ground = (int32_t)st->nbfg;
+  for (int k = 0; k < ARTIS_IONBAL_NTIMES; k++) out->kernel_ms[k] = st->kernel_ms[k];
   return ARTIS_OK;
 }
 

@@ -59,6 +59,8 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_spectra_download.argtypes = [C.c_void_p, C.POINTER(abi.Spectra)]
     L.artis_amd_radfield_fit.argtypes = [C.c_void_p, C.POINTER(abi.RadfieldConfig), C.c_void_p]
     L.artis_amd_radfield_download.argtypes = [C.c_void_p, C.POINTER(abi.Radfield)]
+    L.artis_amd_grid_update.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
+    L.artis_amd_grid_update_download.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdateResult)]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -83,6 +85,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_cache_tiles", "artis_amd_last_tiling", "artis_amd_last_tiling_fills", "artis_amd_last_tiling_parked", "artis_amd_last_pool_resets", "artis_amd_record_tiers", "artis_amd_last_thermal_variants", "artis_amd_last_estimator_forms", "artis_amd_last_pool_usage",
     "artis_amd_spectra_compute", "artis_amd_spectra_devptr", "artis_amd_spectra_download",
     "artis_amd_radfield_fit", "artis_amd_radfield_download",
+    "artis_amd_grid_update", "artis_amd_grid_update_download",
 ]
 
 
@@ -226,6 +229,41 @@ class Engine:
             out["radfieldbin_W"] = out["radfieldbin_W"].reshape(info.npts_nonempty, info.nbins)
         out["totals"] = {k: int(info.totals[i]) for i, k in enumerate(abi.RADFIELD_COUNTS)}
         out["kernel_ms"] = (float(info.kernel_ms[0]), float(info.kernel_ms[1]))
+        return out
+
+    # ionisation balance and hand-over of the grid update (include/artis_amd.h artis_amd_grid_update*)
+    def grid_update(self, ts_next: abi.Timestep, rho, elem_massfracs, thick, use_fit: bool = True, elem_meanweight=None, TJ=None,
+                    TR=None, W=None, Te=None, kappagrey=None, clumpfactor=None, ffegrp=None, stream: int = 0) -> dict:
+        """Partition functions and ion balance of every cell on the device, from the last radiation-field fit (use_fit) or the host's
+        temperatures; the result becomes the engine's cell state for ts_next and the cell cache is filled. Returns the download
+        (grid_update_download). A refused state raises EngineError; its flags stay downloadable."""
+        u, keep = abi.grid_update_config(use_fit, rho, elem_massfracs, thick, elem_meanweight, TJ, TR, W, Te, kappagrey, clumpfactor,
+                                         ffegrp)
+        self._ts = ts_next
+        self._check(self.L.artis_amd_grid_update(self.h, C.byref(u), C.cast(ts_next.ref(), C.c_void_p), C.c_void_p(stream)))
+        del keep
+        return self.grid_update_download()
+
+    def grid_update_download(self) -> dict:
+        """numpy arrays under the field names of artis_grid_update_result ([ncell, nions] / [ncell, nelements] /
+        [ncell, nbfcontinua_ground] for the per-ion, per-element and per-continuum ones), "ncells_flagged" as a dict over
+        abi.IONBAL_FLAGS, "total_evals" and "kernel_ms" (gamma + partition functions, phi, per-cell solve, cell-cache fill)."""
+        info = abi.GridUpdateResult(struct_size=C.sizeof(abi.GridUpdateResult))
+        self._check(self.L.artis_amd_grid_update_download(self.h, C.byref(info)))  # sizes first
+        n, ni, ne, g = info.npts_nonempty, info.nions, info.nelements, info.nbfcontinua_ground
+        out = abi.grid_update_arrays(n, ni, ne, g)
+        types = dict(abi.GridUpdateResult._fields_)
+        for k, v in out.items():
+            setattr(info, k, v.ctypes.data_as(types[k]))
+        self._check(self.L.artis_amd_grid_update_download(self.h, C.byref(info)))
+        out["ion_partfuncts"] = out["ion_partfuncts"].reshape(n, ni)
+        out["ion_groundlevelpops"] = out["ion_groundlevelpops"].reshape(n, ni)
+        out["phi"] = out["phi"].reshape(n, ni)
+        out["uppermost_ion"] = out["uppermost_ion"].reshape(n, ne)
+        out["gamma_normed"] = out["gamma_normed"][: n * g].reshape(n, g)
+        out["ncells_flagged"] = {k: int(info.ncells_flagged[i]) for i, k in enumerate(abi.IONBAL_FLAGS)}
+        out["total_evals"] = int(info.total_evals)
+        out["kernel_ms"] = tuple(float(x) for x in info.kernel_ms)
         return out
 
     def debug_cellcache(self, c: int) -> dict:

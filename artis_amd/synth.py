@@ -756,6 +756,40 @@ def evolve_cellstate(cs: abi.CellState, t0: float, t1: float, tfloor: float = 25
     return abi.CellState(d)
 
 
+def next_matter(model: abi.Model, cs: abi.CellState, t0: float, t1: float, options: str = "classic", seed: int = 7) -> dict:
+    """The new timestep's matter for artis_amd_grid_update / Engine.grid_update on a grid made by build(): what the host's decay and
+    abundance update leaves at t1 (update_grid.cc:714-720) for a state given at t0. rho thins homologously as (t0/t1)^3 (the scaling
+    of evolve_cellstate); a fixed small share of every cell's iron-group mass (elements with Z >= 26) moves from the last such element
+    to the first (a decay-chain-like shift, deterministic in t1), renormalised to the cell's total. With USE_CALCULATED_MEANATOMICWEIGHT
+    (kilonova_lte and its variants) also elem_meanweight: the elements' mean nuclear masses scattered by a few per cent per cell, as
+    for ci_kilonova_xcom. Keys: rho, elem_massfracs, thick (unchanged), elem_meanweight (or None)."""
+    f3 = (t0 / t1) ** 3
+    rho = (np.asarray(cs["rho"], dtype=np.float64) * f3).astype(np.float32)
+    ne = int(model["nelements"])
+    mf = np.asarray(cs["elem_massfracs"], dtype=np.float64).reshape(-1, ne).copy()
+    Z = np.asarray(model["elem_anumber"])
+    ig = np.nonzero(Z >= 26)[0]
+    if len(ig) >= 2:
+        move = mf[:, ig[-1]] * min(0.2, 0.05 * np.log(t1 / t0 + 1.0))
+        mf[:, ig[-1]] -= move
+        mf[:, ig[0]] += move
+    meanweight = None
+    if abi.inputs_like(options).startswith("kilonova"):
+        rng = np.random.default_rng(seed)
+        amass = np.array([_AMASS.get(int(z), 2.0 * int(z)) for z in Z]) * MH
+        meanweight = (amass[None, :] * rng.uniform(0.97, 1.05, (len(rho), ne))).astype(np.float32).ravel()
+    return dict(rho=rho, elem_massfracs=mf.astype(np.float32).ravel(), thick=np.asarray(cs["thick"], dtype=np.int32).copy(),
+                elem_meanweight=meanweight)
+
+
+def with_meannucmass(model: abi.Model) -> abi.Model:
+    """The model with artis_model.elem_meannucmass (the elements' stable mean nuclear masses, as nonthermal_model_inputs gives
+    them), which the element number densities of artis_amd_grid_update read in builds without USE_CALCULATED_MEANATOMICWEIGHT."""
+    md = dict(model.d)
+    md["elem_meannucmass"] = (np.array([_AMASS.get(int(z), 2.0 * int(z)) for z in model["elem_anumber"]]) * MH).astype(np.float32)
+    return abi.Model(md)
+
+
 def vpkt_config(expopac: bool = False) -> dict:
     """What read_vpktparameterfile() (vpkt.cc:673) leaves of a vpkt.txt like tests/classicmode_3d_inputfiles/vpkt.txt: three
     observers near +z, on the equator and towards -z (not ON the axis as in that file: there the meridian frame of the

@@ -745,6 +745,73 @@ int artis_amd_radfield_fit(artis_amd_engine *eng, const artis_radfield_config *c
 /* Copy the results of the last fit to the host (sizes in the reported fields even when every pointer is NULL). */
 int artis_amd_radfield_download(artis_amd_engine *eng, artis_radfield *out);
 
+/* ---- ionisation balance and hand-over of the grid update ------------------------------
+ * The rest of the reference's grid update of an LTE timestep or a THICK cell (update_grid_cell, update_grid.cc:504-510 and
+ * :530-549), and calculate_ion_balance_nne (ltepop.cc:475) after the host's T_e solve, on the device, in builds without NLTE
+ * populations. In order:
+ *   1. the new timestep's rho and composition; nnetot (grid.cc:1719)
+ *   2. the temperatures: T_J, T_R, W, T_e of the last artis_amd_radfield_fit (use_fit = 1; Te[] overrides the cells it fitted,
+ *      whose T_e the fit leaves), or the host's (use_fit = 0: forced Saha in every cell, the initial timestep)
+ *   3. the normalised gamma estimator: the engine's raw block (after the all-reduce) x estimator_normfactor / H with the
+ *      normfactor of the last fit (update_grid.cc:358); use_fit = 0: not formed (zero)
+ *   4. per non-empty cell: partition functions (ltepop.cc:204, T_exc = T_J with LTEPOP_EXCITATION_USE_TJ, else T_e) and the ion
+ *      balance: forced Saha where lte_iteration holds or the cell is THICK, otherwise Saha or rate balance as
+ *      FORCE_SAHA_ION_BALANCE says; n_e from a TOMS 748 root in [0, rho / MH] (RelTol 1e-3, 50 evaluations), the ground
+ *      populations, then n_e again from the stored floats (set_calculated_nne ltepop.cc:242)
+ *   5. corrphotoionrenorm = 1 in LTE and THICK cells (USE_LUT_PHOTOION builds, update_grid.cc:539-543)
+ *   6. the result becomes the engine's cell state and the cell cache is filled, as artis_amd_set_cellstate followed by
+ *      artis_amd_populate_cellcache would (a tiled cache forgets its rows)
+ * A cell flagged NOT_BRACKETED, NONFINITE or INVALID_U refuses the whole state: ARTIS_ERR_NOTCONVERGED, the previous state stays
+ * resident. Builds with NLTE populations (the nebular family): ARTIS_ERR_UNSUPPORTED. The result is bitwise reproducible (one
+ * writer per output element, no float atomics). Scratch is allocated at the first call, all of it at once. */
+#define ARTIS_IONBAL_NEUTRAL 1        /* every element at its lowest stage: set_groundlevelpops_neutral (ltepop.cc:254) */
+#define ARTIS_IONBAL_MAXIT 2          /* the n_e root search stopped at 50 evaluations */
+#define ARTIS_IONBAL_PHI_OVERFLOW 4   /* an uppermost ion limited by the overflow of nne_max x phi (ltepop.cc:336) */
+#define ARTIS_IONBAL_FRAC_ZEROED 8    /* a non-finite ion fraction set to 0 (ltepop.cc:377) */
+#define ARTIS_IONBAL_NOT_BRACKETED 16 /* the residual has one sign at 0 and at rho / MH (refused) */
+#define ARTIS_IONBAL_INVALID_U 32     /* a partition function <= 0 or non-finite (refused) */
+#define ARTIS_IONBAL_NONFINITE 64     /* a non-finite n_e (refused) */
+#define ARTIS_IONBAL_FORCED_SAHA 128  /* the cell was balanced with forced Saha (lte_iteration or THICK) */
+#define ARTIS_IONBAL_NTIMES 4
+typedef struct artis_grid_update {
+  int64_t struct_size;      /* sizeof(artis_grid_update) */
+  int32_t use_fit;          /* 1: T_J, T_R, W, T_e and lte_iteration of the last artis_amd_radfield_fit (ARTIS_ERR_ARG if none
+                               since the last step); 0: the host's TJ/TR/W/Te below and forced Saha in every cell (the initial
+                               timestep, update_grid.cc:504-510, which is always an LTE iteration: update_grid.cc:684) */
+  const float *TJ, *TR, *W; /* [npts_nonempty], required when use_fit == 0 */
+  const float *Te;          /* [npts_nonempty] or NULL: T_e of cells the fit did not set (its fitted cells: the host's T_e
+                               solve); NULL keeps the cell's current T_e. use_fit == 0: required */
+  /* the new timestep's matter, which the host's decay / abundance update (update_grid.cc:714-720) still produces */
+  const float *rho;               /* [npts_nonempty] */
+  const float *elem_massfracs;    /* [npts_nonempty*nelements] */
+  const float *elem_meanweight;   /* [npts_nonempty*nelements]: USE_CALCULATED_MEANATOMICWEIGHT builds only (elsewhere the
+                                     element number densities use artis_model.elem_meannucmass, then required) */
+  const int32_t *thick;     /* [npts_nonempty] flags for the NEXT step's packets (update_grid.cc:618-627); the balance uses the
+                               current ones */
+  const float *kappagrey, *clumpfactor, *ffegrp; /* [npts_nonempty] or NULL: keep the engine's */
+} artis_grid_update;
+typedef struct artis_grid_update_result {
+  int64_t struct_size; /* sizeof(artis_grid_update_result) */
+  /* host arrays to fill; NULL: skip */
+  float *Te, *TJ, *TR, *W, *nne, *nnetot, *rho; /* [npts_nonempty] the cell state written */
+  float *ion_partfuncts, *ion_groundlevelpops;  /* [npts_nonempty*nions] */
+  int32_t *uppermost_ion;                       /* [npts_nonempty*nelements] (ltepop.cc:308) */
+  double *gamma_normed;                         /* [npts_nonempty*nbfcontinua_ground] the normalised gamma estimator */
+  double *phi;                                  /* [npts_nonempty*nions] phi of every ion below its element's top ion (0 there) */
+  float *nne_root;                              /* [npts_nonempty] the root search's n_e (0: neutral fallback) */
+  int32_t *flags;                               /* [npts_nonempty] ARTIS_IONBAL_* bits */
+  int32_t *evals;                               /* [npts_nonempty] evaluations of the n_e residual */
+  /* reported */
+  int64_t ncells_flagged[8];                    /* cells with bit k of ARTIS_IONBAL_* set */
+  int64_t total_evals;
+  int32_t npts_nonempty, nions, nelements, nbfcontinua_ground;
+  double kernel_ms[ARTIS_IONBAL_NTIMES];        /* HIP-event time: [0] gamma + partition functions, [1] phi, [2] per-cell solve,
+                                                   [3] the cell-cache fill */
+} artis_grid_update_result;
+int artis_amd_grid_update(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream);
+/* Copy the result of the last artis_amd_grid_update to the host (also after a refused call: its flags and counts). */
+int artis_amd_grid_update_download(artis_amd_engine *eng, artis_grid_update_result *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -293,6 +293,15 @@
 #ifndef ARTIS_OPT_LTEPOP_EXCITATION_USE_TJ
 #define ARTIS_OPT_LTEPOP_EXCITATION_USE_TJ 1 /* artisoptions_classic.h:24 */
 #endif
+/* FORCE_SAHA_ION_BALANCE(Z) (artisoptions_classic.h:27): a constant in every options file of the reference, true only in
+ * artisoptions_kilonova_lte.h:27 (read by the ion balance of artis_amd_grid_update) */
+#ifndef ARTIS_OPT_FORCE_SAHA_ION_BALANCE
+#ifdef ARTIS_PRESET_KILONOVA_LTE
+#define ARTIS_OPT_FORCE_SAHA_ION_BALANCE 1
+#else
+#define ARTIS_OPT_FORCE_SAHA_ION_BALANCE 0
+#endif
+#endif
 #ifndef ARTIS_OPT_DIRECT_COL_HEAT
 #define ARTIS_OPT_DIRECT_COL_HEAT 0 /* artisoptions_classic.h:35 */
 #endif
