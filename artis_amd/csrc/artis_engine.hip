@@ -2393,178 +2393,13 @@ __global__ void __launch_bounds__(TB, (CONT_LDS ? 1 : ARTIS_VPKT_WGS)) k_vpkt(En
 
 inline int nblocks(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
 
-// ------------------------------------------------------------------ spectra and light curves (spectra.h)
-// Every output element is the sequential sum of its contributions in the caller's packet order, whatever slots the packets
-// sit in and in whatever order the threads run. k_spec_prep first brings the packets into caller order (the SpecPkt of caller
-// packet perm[slot] from record slot); then per family of outputs (spectra.h SpecFamily):
-//   k_spec_keys      entry e -> key = output element (or the sentinel: no contribution), value = e; entries are in caller order
-//   radix sort       (rocPRIM, stable): the entries of one element side by side, still in caller order
-//   k_spec_heads     the first entry of every element's run
-// and per array of the family (I, Q, U):
-//   k_spec_values    the contribution of every sorted entry, side by side in sorted order
-//   k_spec_runsum    one wave per run: the lanes load the run 512 entries at a time (the next 512 while the current ones are
-//                    added), and every lane adds them in order (v_readlane), so each lane holds the same sequential sum.
-__global__ void __launch_bounds__(BLOCK) k_spec_prep(PktStore P, const int32_t *perm, artis_spec::SpecRules R, artis_spec::SpecPkt *out,
-                                                    unsigned long long *counts) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  int kind = 0;
-  if (i < P.n) {
-    artis_packet a;
-    rec_to_aos(P, i, a);
-    const artis_spec::SpecPkt s = artis_spec::classify(a, R);
-    out[perm ? perm[i] : i] = s;
-    kind = s.kind;
-  }
-  // escaped r-packets and gamma packets: one atomic per wave and kind
-  const unsigned long long nr = __ballot(kind == 1), ng = __ballot(kind == 2);
-  if ((threadIdx.x & 63) == 0) {
-    if (nr) atomicAdd(&counts[0], (unsigned long long)__popcll(nr));
-    if (ng) atomicAdd(&counts[1], (unsigned long long)__popcll(ng));
-  }
-}
-__global__ void __launch_bounds__(BLOCK) k_spec_bfcols(DevModel M, int max_nions, int32_t *bf_col) {
-  const int ui = blockIdx.x * BLOCK + threadIdx.x;
-  if (ui >= M.nions) return;
-  artis_spec::fill_bf_columns_of_ion(ui, M.ion_element, M.elem_uniqueionindexstart, M.ion_uniquelevelindexstart, M.ion_nlevels_ionising,
-                                     M.level_nphixstargets, M.level_bflist_start, max_nions, M.nbfcontinua, bf_col);
-}
-__global__ void __launch_bounds__(BLOCK) k_spec_keys(const artis_spec::SpecPkt *pk, int64_t n, int64_t nent, int fam, artis_spec::SpecShape S,
-                                                    uint32_t sentinel, uint32_t *keys, uint32_t *ents) {
-  const int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (e >= nent) return;
-  const int half = e >= n;
-  int64_t slot;
-  double saf;
-  keys[e] = artis_spec::family_entry(fam, S, pk[half ? e - n : e], half, &slot, &saf) ? (uint32_t)slot : sentinel;
-  ents[e] = (uint32_t)e;
-}
-__global__ void __launch_bounds__(BLOCK) k_spec_heads(const uint32_t *keys, int64_t nent, uint32_t sentinel, uint32_t *heads, uint32_t *nheads) {
-  const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (j >= nent) return;
-  const uint32_t k = keys[j];
-  if (k != sentinel && (j == 0 || keys[j - 1] != k)) heads[atomicAdd(nheads, 1u)] = (uint32_t)j;
-}
-__global__ void __launch_bounds__(BLOCK) k_spec_values(const artis_spec::SpecPkt *pk, int64_t n, artis_spec::SpecRules R, artis_spec::SpecShape S,
-                                                      int fam, int comp, const uint32_t *keys, const uint32_t *ents, int64_t nent,
-                                                      uint32_t sentinel, double *vals) {
-  const int64_t j = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (j >= nent || keys[j] == sentinel) return;  // (k_spec_runsum reads no value of an entry without a contribution)
-  const int64_t e = ents[j];
-  const int half = e >= n;
-  const artis_spec::SpecPkt s = pk[half ? e - n : e];
-  int64_t slot;
-  double saf;
-  (void)artis_spec::family_entry(fam, S, s, half, &slot, &saf);
-  vals[j] = artis_spec::family_value(fam, comp, s, R, saf);
-}
-__device__ inline double readlane_f64(double v, int lane) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-constexpr int SPEC_RUN_K = 8;  // entries per lane per round: 512 per wave
-// entries base + k * 64 + lane of a round (order within the round: k-major, lane-minor); past the end: a key that is not `key`
-__device__ inline void spec_round_load(const uint32_t *keys, const double *vals, int64_t nent, int64_t base, int lane, uint32_t key,
-                                       uint32_t kk[SPEC_RUN_K], double vv[SPEC_RUN_K]) {
-#pragma unroll
-  for (int k = 0; k < SPEC_RUN_K; k++) {
-    const int64_t j = base + k * 64 + lane;
-    kk[k] = j < nent ? keys[j] : ~key;
-    vv[k] = j < nent ? vals[j] : 0.;
-  }
-}
-__global__ void __launch_bounds__(BLOCK) k_spec_runsum(const uint32_t *keys, const double *vals, int64_t nent, const uint32_t *heads,
-                                                      const uint32_t *nheads, double *out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nwaves = (int64_t)gridDim.x * (BLOCK / 64);
-  const uint32_t nruns = *nheads;
-  for (int64_t r = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); r < nruns; r += nwaves) {
-    const int64_t j0 = heads[r];
-    const uint32_t key = keys[j0];
-    uint32_t kk[SPEC_RUN_K], kn[SPEC_RUN_K];
-    double vv[SPEC_RUN_K], vn[SPEC_RUN_K];
-    spec_round_load(keys, vals, nent, j0, lane, key, kk, vv);
-    double s = 0.;
-    for (int64_t base = j0;; base += SPEC_RUN_K * 64) {
-      int cnt[SPEC_RUN_K];
-      bool full = true;
-#pragma unroll
-      for (int k = 0; k < SPEC_RUN_K; k++) {
-        cnt[k] = __popcll(__ballot(kk[k] == key));  // the run's entries are a prefix of the round (keys sorted)
-        full = full && cnt[k] == 64;
-      }
-      if (full) spec_round_load(keys, vals, nent, base + SPEC_RUN_K * 64, lane, key, kn, vn);  // in flight while this round is added
-#pragma unroll
-      for (int k = 0; k < SPEC_RUN_K; k++) {
-        if (cnt[k] == 64) {
-#pragma unroll
-          for (int l = 0; l < 64; l++) s += readlane_f64(vv[k], l);
-        } else {
-          for (int l = 0; l < cnt[k]; l++) s += readlane_f64(vv[k], l);
-        }
-      }
-      if (!full) break;
-#pragma unroll
-      for (int k = 0; k < SPEC_RUN_K; k++) {
-        kk[k] = kn[k];
-        vv[k] = vn[k];
-      }
-    }
-    if (lane == 0) out[key] = s;
-  }
-}
-
-// scratch and outputs of artis_amd_spectra_* (allocated at the first call, grown when needed: spec_reserve)
-struct SpecState {
-  // grown together by spec_reserve(): after a failed allocation all of them are freed and every capacity is 0
-  artis_spec::SpecPkt *d_pk = nullptr;  // [pk_cap]
-  uint32_t *d_keys = nullptr, *d_keys2 = nullptr, *d_ents = nullptr, *d_ents2 = nullptr, *d_heads = nullptr;  // [ent_cap]
-  double *d_vals = nullptr;             // [ent_cap]
-  void *d_sort_tmp = nullptr;           // [sort_tmp_bytes]
-  double *d_block = nullptr;            // [block_cap]
-  double *d_times = nullptr;            // [2 * times_cap] starts, widths
-  int64_t pk_cap = 0, ent_cap = 0, block_cap = 0, times_cap = 0;
-  size_t sort_tmp_bytes = 0;
-  // made once (spec_init)
-  unsigned long long *d_counts = nullptr;  // [2] escaped r-packets, gamma packets; then the run count (uint32)
-  float *d_grid = nullptr;                 // delta_freq of the r-packet and of the gamma grid
-  float h_lower[2][artis_spec::MNUBINS], h_delta[2][artis_spec::MNUBINS];
-  artis_spec::SpecGrid grid_r{}, grid_g{};
-  int32_t *d_bfcol = nullptr;
-  int32_t max_nions = 0;
-  // the last compute
-  bool valid = false;
-  int64_t off[artis_spec::NOUT] = {}, size[artis_spec::NOUT] = {};
-  int64_t ndoubles = 0;
-  artis_spec::SpecShape shape{};
-  unsigned long long counts[2] = {};
-};
-
-void spec_free_scratch(SpecState *st) {
-  void **ptrs[] = {(void **)&st->d_pk, (void **)&st->d_keys, (void **)&st->d_keys2, (void **)&st->d_ents, (void **)&st->d_ents2,
-                   (void **)&st->d_heads, (void **)&st->d_vals, &st->d_sort_tmp, (void **)&st->d_block, (void **)&st->d_times};
-  for (void **q : ptrs) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
-  st->pk_cap = st->ent_cap = st->block_cap = st->times_cap = 0;
-  st->sort_tmp_bytes = 0;
-}
-
-struct RfState;  // artis_amd_radfield_*: defined with them at the end of this file
+// the timestep-end stages (stage_*.h, included at the end of this file); the engine holds each one's state from its first call on
+struct SpecState;
+void spec_free(SpecState *st);
+struct RfState;
 void rf_free(RfState *st);
-struct IbState;  // artis_amd_grid_update*: likewise
+struct IbState;
 void ib_free(IbState *st);
-
-void spec_free(SpecState *st) {
-  if (!st) return;
-  spec_free_scratch(st);
-  void *ptrs[] = {st->d_counts, st->d_grid, st->d_bfcol};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  delete st;
-}
 
 }  // namespace
 
@@ -4751,1008 +4586,8 @@ int artis_amd_debug_cellcache(artis_amd_engine *e, int c, double *levelpops, dou
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ spectra and light curves: C-ABI
-namespace {
-int spec_arg_error(const char *msg) {
-  g_last_error = msg;
-  return ARTIS_ERR_ARG;
-}
-int spec_end_bit(uint32_t sentinel) {  // radix-sort bits that hold every key of a family, the sentinel included
-  int end_bit = 1;
-  while (end_bit < 32 && ((uint64_t)1 << end_bit) <= (uint64_t)sentinel) end_bit++;
-  return end_bit;
-}
-// Scratch for n packets, nent entries, the output block and the time grid. When any of it is too small, all of it is freed and
-// allocated anew at the larger of old and new size; when an allocation fails, all of it is freed and every capacity is 0, so that
-// no later call finds a capacity without its buffer. The new bytes must fit 90 % of the free device memory (ARTIS_ERR_ARG).
-int spec_reserve(SpecState *st, int64_t n, int64_t nent, int64_t ndoubles, int64_t ntimesteps, size_t sort_tmp) {
-  if (st->d_pk && st->pk_cap >= n && st->ent_cap >= nent && st->block_cap >= ndoubles && st->times_cap >= ntimesteps &&
-      st->sort_tmp_bytes >= sort_tmp)
-    return ARTIS_OK;
-  const int64_t npk = std::max(st->pk_cap, n), nen = std::max(st->ent_cap, nent), nbl = std::max(st->block_cap, ndoubles),
-                nts = std::max(st->times_cap, ntimesteps);
-  const size_t ntmp = std::max(st->sort_tmp_bytes, sort_tmp);
-  auto bytes = [](int64_t pk, int64_t en, int64_t bl, int64_t ts, size_t tmp) {
-    return (double)sizeof(artis_spec::SpecPkt) * pk + (5. * sizeof(uint32_t) + sizeof(double)) * en + (double)sizeof(double) * bl +
-           2. * sizeof(double) * ts + (double)tmp;
-  };
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  const double held = st->d_pk ? bytes(st->pk_cap, st->ent_cap, st->block_cap, st->times_cap, st->sort_tmp_bytes) : 0.;
-  if (bytes(npk, nen, nbl, nts, ntmp) - held > 0.9 * (double)free_b)
-    return spec_arg_error("spectra: the output arrays and the scratch do not fit the free device memory");
-  spec_free_scratch(st);
-  auto one = [](int64_t c) { return (size_t)(c > 0 ? c : 1); };
-  hipError_t err = hipMalloc((void **)&st->d_pk, sizeof(artis_spec::SpecPkt) * one(npk));
-  for (uint32_t **q : {&st->d_keys, &st->d_keys2, &st->d_ents, &st->d_ents2, &st->d_heads})
-    if (err == hipSuccess) err = hipMalloc((void **)q, sizeof(uint32_t) * one(nen));
-  if (err == hipSuccess) err = hipMalloc((void **)&st->d_vals, sizeof(double) * one(nen));
-  if (err == hipSuccess) err = hipMalloc(&st->d_sort_tmp, ntmp > 0 ? ntmp : 1);
-  if (err == hipSuccess) err = hipMalloc((void **)&st->d_block, sizeof(double) * one(nbl));
-  if (err == hipSuccess) err = hipMalloc((void **)&st->d_times, 2 * sizeof(double) * one(nts));
-  if (err != hipSuccess) {
-    spec_free_scratch(st);
-    g_last_error = std::string("spectra: hipMalloc of the scratch: ") + hipGetErrorString(err);
-    return ARTIS_ERR_HIP;
-  }
-  st->pk_cap = npk;
-  st->ent_cap = nen;
-  st->block_cap = nbl;
-  st->times_cap = nts;
-  st->sort_tmp_bytes = ntmp;
-  return ARTIS_OK;
-}
-// once per engine: the frequency grids (init_spectra, on the host as the reference does) and the column maps
-int spec_init(artis_amd_engine *e) {
-  if (e->spec) return ARTIS_OK;
-  SpecState *st = new SpecState();
-  e->spec = st;
-  using namespace artis_spec;
-  st->grid_r = make_grid(ARTIS_OPT_NU_MIN_R, ARTIS_OPT_NU_MAX_R, st->h_lower[0], st->h_delta[0]);
-  st->grid_g = make_grid(NU_MIN_GAMMA, NU_MAX_GAMMA, st->h_lower[1], st->h_delta[1]);
-  HIP_TRY(hipMalloc((void **)&st->d_grid, sizeof(float) * 2 * MNUBINS));
-  HIP_TRY(hipMemcpy(st->d_grid, st->h_delta[0], sizeof(float) * MNUBINS, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(st->d_grid + MNUBINS, st->h_delta[1], sizeof(float) * MNUBINS, hipMemcpyHostToDevice));
-  st->grid_r.delta_freq = st->d_grid;
-  st->grid_g.delta_freq = st->d_grid + MNUBINS;
-  HIP_TRY(hipMalloc((void **)&st->d_counts, sizeof(unsigned long long) * 4));
-  std::vector<int32_t> nions(e->Mh.nelements > 0 ? e->Mh.nelements : 1, 0);
-  if (e->Mh.nelements > 0)
-    HIP_TRY(hipMemcpy(nions.data(), e->M.elem_nions, sizeof(int32_t) * (size_t)e->Mh.nelements, hipMemcpyDeviceToHost));
-  st->max_nions = *std::max_element(nions.begin(), nions.end());
-  const int nbf = e->Mh.nbfcontinua;
-  HIP_TRY(hipMalloc((void **)&st->d_bfcol, sizeof(int32_t) * (size_t)(nbf > 0 ? nbf : 1)));
-  HIP_TRY(hipMemset(st->d_bfcol, 0xFF, sizeof(int32_t) * (size_t)(nbf > 0 ? nbf : 1)));  // -1: an entry no level fills
-  if (e->Mh.nions > 0) {
-    hipLaunchKernelGGL(k_spec_bfcols, dim3(nblocks(e->Mh.nions)), dim3(BLOCK), 0, nullptr, e->M, st->max_nions, st->d_bfcol);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  return ARTIS_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int artis_amd_spectra_compute(artis_amd_engine *e, const artis_spectra_config *cfg, void *hip_stream) {
-  using namespace artis_spec;
-  if (!e || !cfg) return spec_arg_error("spectra: null engine or config");
-  if (cfg->struct_size != (int64_t)sizeof(artis_spectra_config)) return spec_arg_error("spectra: artis_spectra_config.struct_size does not match");
-  if (cfg->ntimesteps < 1) return spec_arg_error("spectra: ntimesteps < 1");
-  if (!cfg->ts_start || !cfg->ts_width) return spec_arg_error("spectra: null ts_start or ts_width");
-  for (int i = 1; i < cfg->ntimesteps; i++)
-    if (!(cfg->ts_start[i] > cfg->ts_start[i - 1])) return spec_arg_error("spectra: timestep starts do not increase");
-  if (!(cfg->dirbin == -1 || cfg->dirbin == ARTIS_SPEC_ALL_DIRBINS || (cfg->dirbin >= 0 && cfg->dirbin < MABINS)))
-    return spec_arg_error("spectra: dirbin out of range (-1, 0..MABINS-1 or ARTIS_SPEC_ALL_DIRBINS)");
-  if (e->npackets < 0 || !e->d_pkt) return spec_arg_error("spectra: no resident packets");
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = spec_init(e);
-  if (rc != ARTIS_OK) {
-    spec_free(e->spec);
-    e->spec = nullptr;
-    return rc;
-  }
-  SpecState *st = e->spec;
-  st->valid = false;
-  hipStream_t s = (hipStream_t)hip_stream;
-
-  SpecShape S{};
-  S.dirbin = cfg->dirbin;
-  S.ndirslots = cfg->dirbin == ARTIS_SPEC_ALL_DIRBINS ? 1 + MABINS : 1;
-  S.ntimesteps = cfg->ntimesteps;
-  S.nabscols = e->Mh.nelements * st->max_nions;
-  S.proccount = 2 * S.nabscols + 1;
-  S.emission_absorption = cfg->emission_absorption != 0;
-  S.stokes = cfg->stokes != 0;
-  S.gamma = cfg->gamma != 0;
-  // the output block, and the keys: an output element's index must fit 32 bits beside the sentinel
-  int64_t ndoubles = 0;
-  for (int o = 0; o < NOUT; o++) st->size[o] = 0;
-  for (int fam = 0; fam < NFAM; fam++) {
-    if (!family_on(fam, S)) continue;
-    const int64_t sz = family_size(fam, S);
-    if (sz >= (int64_t)0xFFFFFFFFLL)
-      return spec_arg_error(S.ndirslots > 1 ? "spectra: the arrays of all direction bins do not fit 32-bit indices (emission_absorption)"
-                                            : "spectra: the arrays do not fit 32-bit indices");
-    for (int c = 0; c < family_ncomp(fam, S); c++) st->size[family_output(fam, c)] = sz;
-  }
-  for (int o = 0; o < NOUT; o++) {
-    st->off[o] = ndoubles;
-    ndoubles += st->size[o];
-  }
-  const int64_t n = e->npackets;
-  const int64_t nent = n * (S.ndirslots > 1 ? 2 : 1);
-  if (nent >= (int64_t)0xFFFFFFFFLL) return spec_arg_error("spectra: too many packets for 32-bit entry indices");
-  size_t sort_tmp = 0;  // the largest rocPRIM scratch of the families (a size query: no buffer is touched)
-  for (int fam = 0; fam < NFAM; fam++) {
-    if (!family_on(fam, S)) continue;
-    size_t tmp = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                      (size_t)nent, 0, spec_end_bit((uint32_t)family_size(fam, S)), s));
-    sort_tmp = std::max(sort_tmp, tmp);
-  }
-  rc = spec_reserve(st, n, nent, ndoubles, cfg->ntimesteps, sort_tmp);
-  if (rc != ARTIS_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(st->d_times, cfg->ts_start, sizeof(double) * (size_t)cfg->ntimesteps, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(st->d_times + cfg->ntimesteps, cfg->ts_width, sizeof(double) * (size_t)cfg->ntimesteps, hipMemcpyHostToDevice, s));
-
-  SpecRules R{};
-  R.T.ntimesteps = cfg->ntimesteps;
-  R.T.start = st->d_times;
-  R.T.width = st->d_times + cfg->ntimesteps;
-  R.T.tmin = cfg->tmin;
-  R.T.tmax = cfg->tmax;
-  R.r = st->grid_r;
-  R.g = st->grid_g;
-  R.cols.nelements = e->Mh.nelements;
-  R.cols.max_nions = st->max_nions;
-  R.cols.nlines = e->Mh.nlines;
-  R.cols.nbfcontinua = e->Mh.nbfcontinua;
-  R.cols.line_elementindex = e->M.line_elementindex;
-  R.cols.line_ionindex = e->M.line_ionindex;
-  R.cols.bf_col = st->d_bfcol;
-  R.inverse_gamma = std::sqrt(1. - (e->model_copy.vmax * e->model_copy.vmax / (artis_spec::CLIGHT * artis_spec::CLIGHT)));  // :703
-  R.want_columns = S.emission_absorption;
-
-  HIP_TRY(hipMemsetAsync(st->d_block, 0, sizeof(double) * (size_t)(ndoubles > 0 ? ndoubles : 1), s));
-  HIP_TRY(hipMemsetAsync(st->d_counts, 0, sizeof(unsigned long long) * 4, s));
-  if (n > 0) {
-    hipLaunchKernelGGL(k_spec_prep, dim3(nblocks(n)), dim3(BLOCK), 0, s, e->P, e->use_perm ? e->d_perm : nullptr, R, st->d_pk, st->d_counts);
-    HIP_TRY(hipGetLastError());
-    uint32_t *nheads = (uint32_t *)(st->d_counts + 2);
-    for (int fam = 0; fam < NFAM; fam++) {
-      if (!family_on(fam, S)) continue;
-      const uint32_t sentinel = (uint32_t)family_size(fam, S);
-      const int end_bit = spec_end_bit(sentinel);
-      hipLaunchKernelGGL(k_spec_keys, dim3(nblocks(nent)), dim3(BLOCK), 0, s, st->d_pk, n, nent, fam, S, sentinel, st->d_keys, st->d_ents);
-      HIP_TRY(hipGetLastError());
-      size_t tmp = st->sort_tmp_bytes;
-      HIP_TRY(rocprim::radix_sort_pairs(st->d_sort_tmp, tmp, st->d_keys, st->d_keys2, st->d_ents, st->d_ents2, (size_t)nent, 0, end_bit, s));
-      HIP_TRY(hipMemsetAsync(nheads, 0, sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_spec_heads, dim3(nblocks(nent)), dim3(BLOCK), 0, s, st->d_keys2, nent, sentinel, st->d_heads, nheads);
-      HIP_TRY(hipGetLastError());
-      for (int c = 0; c < family_ncomp(fam, S); c++) {
-        hipLaunchKernelGGL(k_spec_values, dim3(nblocks(nent)), dim3(BLOCK), 0, s, st->d_pk, n, R, S, fam, c, st->d_keys2, st->d_ents2, nent,
-                           sentinel, st->d_vals);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_spec_runsum, dim3(2048), dim3(BLOCK), 0, s, st->d_keys2, st->d_vals, nent, st->d_heads, nheads,
-                           st->d_block + st->off[family_output(fam, c)]);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(st->counts, st->d_counts, sizeof(unsigned long long) * 2, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  st->ndoubles = ndoubles;
-  st->shape = S;
-  st->valid = true;
-  return ARTIS_OK;
-}
-
-int artis_amd_spectra_devptr(artis_amd_engine *e, void **dptr, int64_t *ndoubles) {
-  if (!e || !dptr || !ndoubles) return spec_arg_error("spectra: null argument");
-  if (!e->spec || !e->spec->valid) return spec_arg_error("spectra: nothing computed (artis_amd_spectra_compute)");
-  *dptr = e->spec->d_block;
-  *ndoubles = e->spec->ndoubles;
-  return ARTIS_OK;
-}
-
-int artis_amd_spectra_download(artis_amd_engine *e, artis_spectra *out) {
-  using namespace artis_spec;
-  if (!e || !out) return spec_arg_error("spectra: null argument");
-  if (out->struct_size != (int64_t)sizeof(artis_spectra)) return spec_arg_error("spectra: artis_spectra.struct_size does not match");
-  if (!e->spec || !e->spec->valid) return spec_arg_error("spectra: nothing computed (artis_amd_spectra_compute)");
-  SpecState *st = e->spec;
-  double *dst[NOUT] = {out->lum, out->lumcmf, out->flux, out->flux_q, out->flux_u, out->emission, out->emission_q, out->emission_u,
-                       out->trueemission, out->absorption, out->absorption_q, out->absorption_u, out->gamma_lum, out->gamma_lumcmf,
-                       out->gamma_flux};
-  for (int o = 0; o < NOUT; o++)
-    if (dst[o] && st->size[o] == 0) return spec_arg_error("spectra: an array was asked for that the last compute did not produce");
-  HIP_TRY(hipSetDevice(e->device));
-  for (int o = 0; o < NOUT; o++)
-    if (dst[o]) HIP_TRY(hipMemcpy(dst[o], st->d_block + st->off[o], sizeof(double) * (size_t)st->size[o], hipMemcpyDeviceToHost));
-  if (out->lower_freq) std::memcpy(out->lower_freq, st->h_lower[0], sizeof(float) * MNUBINS);
-  if (out->delta_freq) std::memcpy(out->delta_freq, st->h_delta[0], sizeof(float) * MNUBINS);
-  if (out->gamma_lower_freq) std::memcpy(out->gamma_lower_freq, st->h_lower[1], sizeof(float) * MNUBINS);
-  if (out->gamma_delta_freq) std::memcpy(out->gamma_delta_freq, st->h_delta[1], sizeof(float) * MNUBINS);
-  out->nescaped_rpkt = (int64_t)st->counts[0];
-  out->nescaped_gamma = (int64_t)st->counts[1];
-  out->ntimesteps = st->shape.ntimesteps;
-  out->ndirslots = st->shape.ndirslots;
-  out->nelements = e->Mh.nelements;
-  out->max_nions = st->max_nions;
-  out->proccount = st->shape.proccount;
-  return ARTIS_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------ radiation-field fit (radfield_fit.h)
-// Two kernels on the caller's stream. k_rf_cell: one wave per cell; lane 0 normalises J (and nuJ) and fits T_J, T_R, W
-// (artis_rf::fit_cell), the wave's lanes normalise the cell's bound-free and line estimators and carry the bins of a cell
-// that is not fitted over from the cell state. k_rf_bins: one lane per (cell, bin), a cell's bins on neighbouring lanes so that
-// a wave's residuals have similar x; the estimators are read in place ([cell][bin]{J, nuJ}). Nothing is added with float
-// atomics: every output element has one writer. The bin counts are integer atomics (per cell, only for a bin that has the
-// bit) and one ballot per wave and count for the totals.
-namespace {
-
-struct RfArgs {
-  int64_t ncell;
-  // inputs: the estimator block (J, nuJ with stride 8), the cell state, the caller's volumes
-  const double *J_raw, *nuJ_raw, *bin_est, *bfrate_raw, *Jb_raw, *Jb_count;
-  const double *assocvol;
-  const int32_t *thick;
-  const float *TJ, *TR, *Te, *W, *prev_bin_T_R, *prev_bin_W;
-  double prev_mid, tmin, deltat;
-  int32_t nprocs, lte, nbf, nline;
-  // outputs
-  double *J, *nuJ, *normfactor;
-  float *oTJ, *oTR, *oTe, *oW;
-  int32_t *flags, *counts;
-  float *bin_T_R, *bin_W, *bf;
-  double *Jb, *Jbcount;
-  unsigned long long *totals;
-};
-
-__global__ void __launch_bounds__(BLOCK) k_rf_cell(RfArgs a) {
-  using namespace artis_rf;
-  const int64_t c = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) / 64;
-  const int lane = (int)(threadIdx.x & 63);
-  if (c >= a.ncell) return;  // whole waves
-  const int32_t thick = a.thick[c];
-  if (lane == 0) {
-    const CellIn in{a.J_raw[c * 8], a.nuJ_raw[c * 8], a.assocvol[c], a.prev_mid, a.tmin, a.deltat, a.nprocs, a.lte, thick,
-                    a.TJ[c], a.TR[c], a.Te[c], a.W[c]};
-    const CellOut o = fit_cell(in);
-    a.J[c] = o.J;
-    a.nuJ[c] = o.nuJ;
-    a.normfactor[c] = o.J_normfactor;
-    a.oTJ[c] = o.TJ;
-    a.oTR[c] = o.TR;
-    a.oTe[c] = o.Te;
-    a.oW[c] = o.W;
-    a.flags[c] = o.flags;
-    for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) a.counts[c * ARTIS_RADFIELD_NCOUNTS + k] = 0;
-  }
-  double estimator_normfactor, over4pi;
-  cell_normfactors(a.assocvol[c], a.prev_mid, a.tmin, a.deltat, a.nprocs, &estimator_normfactor, &over4pi);
-  if (a.bin_T_R && !cell_is_fitted(a.lte, thick)) {
-    for (int b = lane; b < NBINS; b += 64) {
-      a.bin_T_R[c * NBINS + b] = a.prev_bin_T_R[c * NBINS + b];
-      a.bin_W[c * NBINS + b] = a.prev_bin_W[c * NBINS + b];
-    }
-  }
-  if (a.bf && !a.lte && thick != ARTIS_CELL_THICK) {
-    for (int i = lane; i < a.nbf; i += 64) a.bf[c * a.nbf + i] = bfrate_normed(a.bfrate_raw[c * a.nbf + i], estimator_normfactor);
-  }
-  if (a.Jb) {
-    for (int i = lane; i < a.nline; i += 64) {
-      a.Jb[c * a.nline + i] = a.Jb_raw[c * a.nline + i] * over4pi;
-      a.Jbcount[c * a.nline + i] = a.Jb_count[c * a.nline + i];
-    }
-  }
-}
-
-__global__ void __launch_bounds__(BLOCK) k_rf_bins(RfArgs a) {
-  using namespace artis_rf;
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  int bits = 0;
-  if (i < a.ncell * NBINS) {
-    const int64_t c = i / NBINS;
-    const int b = (int)(i - c * NBINS);
-    if (a.flags[c] & ARTIS_RADFIELD_FITTED) {
-      float T_R, W;
-      bits = fit_bin(a.bin_est[2 * i], a.bin_est[2 * i + 1], a.normfactor[c], b, a.Te[c], &T_R, &W);
-      a.bin_T_R[i] = T_R;
-      a.bin_W[i] = W;
-      for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++)
-        if (bits & (1 << k)) atomicAdd(&a.counts[c * ARTIS_RADFIELD_NCOUNTS + k], 1);
-    }
-  }
-  for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) {  // the bit k of a bin is count k (artis_rf::BIN_*)
-    const unsigned long long m = __ballot((bits >> k) & 1);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.totals[k], (unsigned long long)__popcll(m));
-  }
-}
-
-// the result block of artis_amd_radfield_*: one allocation, made at the first call, zeroed then (the bound-free block keeps
-// its values from call to call for the THICK cells, as the reference's prev_bfrate_normed does)
-struct RfState {
-  void *d_block = nullptr;
-  size_t bytes = 0;
-  int64_t ncell = 0, nbins = 0, nbf = 0, nline = 0;
-  double *d_J = nullptr, *d_nuJ = nullptr, *d_normfactor = nullptr, *d_assocvol = nullptr, *d_Jb = nullptr, *d_Jbcount = nullptr;
-  float *d_TJ = nullptr, *d_TR = nullptr, *d_Te = nullptr, *d_W = nullptr, *d_bin_T_R = nullptr, *d_bin_W = nullptr, *d_bf = nullptr;
-  int32_t *d_flags = nullptr, *d_counts = nullptr;
-  unsigned long long *d_totals = nullptr;
-  hipEvent_t ev[3] = {};
-  bool valid = false;
-  double prev_mid = 0., deltat = 0.;  // the normalisation of the last fit (artis_amd_grid_update reads it)
-  int32_t nprocs = 1, lte = 0;
-  unsigned long long totals[ARTIS_RADFIELD_NCOUNTS] = {};
-  double kernel_ms[2] = {};
-};
-
-void rf_free(RfState *st) {
-  if (!st) return;
-  if (st->d_block) (void)hipFree(st->d_block);
-  for (hipEvent_t ev : st->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete st;
-}
-
-int rf_arg_error(const char *msg) {
-  g_last_error = msg;
-  return ARTIS_ERR_ARG;
-}
-
-// carve every array out of one block (256-byte aligned pieces); with base == nullptr only the size is counted
-size_t rf_layout(RfState *st, char *base) {
-  size_t off = 0;
-  auto take = [&](auto **p, int64_t count, size_t elem) {
-    const size_t sz = ((size_t)(count > 0 ? count : 0) * elem + 255) & ~(size_t)255;
-    if (base) *p = count > 0 ? (std::remove_reference_t<decltype(*p)>)(base + off) : nullptr;
-    off += sz;
-  };
-  const int64_t n = st->ncell;
-  take(&st->d_J, n, sizeof(double));
-  take(&st->d_nuJ, n, sizeof(double));
-  take(&st->d_normfactor, n, sizeof(double));
-  take(&st->d_assocvol, n, sizeof(double));
-  take(&st->d_TJ, n, sizeof(float));
-  take(&st->d_TR, n, sizeof(float));
-  take(&st->d_Te, n, sizeof(float));
-  take(&st->d_W, n, sizeof(float));
-  take(&st->d_flags, n, sizeof(int32_t));
-  take(&st->d_counts, n * ARTIS_RADFIELD_NCOUNTS, sizeof(int32_t));
-  take(&st->d_totals, ARTIS_RADFIELD_NCOUNTS, sizeof(unsigned long long));
-  take(&st->d_bin_T_R, n * st->nbins, sizeof(float));
-  take(&st->d_bin_W, n * st->nbins, sizeof(float));
-  take(&st->d_bf, n * st->nbf, sizeof(float));
-  take(&st->d_Jb, n * st->nline, sizeof(double));
-  take(&st->d_Jbcount, n * st->nline, sizeof(double));
-  return off;
-}
-
-int rf_init(artis_amd_engine *e) {
-  if (e->rf) return ARTIS_OK;
-  RfState *st = new RfState();
-  st->ncell = e->Mh.npts_nonempty;
-  st->nbins = ARTIS_OPT_MULTIBIN_RADFIELD_MODEL_ON ? ARTIS_OPT_RADFIELDBINCOUNT : 0;
-  st->nbf = e->E.bfrate_raw ? e->Mh.nbfestim : 0;
-  st->nline = e->E.Jb_lu_raw ? e->Mh.detailed_linecount : 0;
-  st->bytes = rf_layout(st, nullptr);
-  size_t free_b = 0, total_b = 0;
-  hipError_t err = hipMemGetInfo(&free_b, &total_b);
-  if (err == hipSuccess && (double)st->bytes > 0.9 * (double)free_b) {
-    delete st;
-    return rf_arg_error("radfield: the result block does not fit the free device memory");
-  }
-  if (err == hipSuccess) err = hipMalloc(&st->d_block, st->bytes);
-  if (err == hipSuccess) err = hipMemset(st->d_block, 0, st->bytes);
-  for (hipEvent_t &ev : st->ev)
-    if (err == hipSuccess) err = hipEventCreate(&ev);
-  if (err != hipSuccess) {
-    rf_free(st);
-    g_last_error = std::string("radfield: allocation of the result block: ") + hipGetErrorString(err);
-    return ARTIS_ERR_HIP;
-  }
-  rf_layout(st, (char *)st->d_block);
-  e->rf = st;
-  return ARTIS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int artis_amd_radfield_fit(artis_amd_engine *e, const artis_radfield_config *cfg, void *hip_stream) {
-  if (!e || !cfg) return rf_arg_error("radfield: null engine or config");
-  if (cfg->struct_size != (int64_t)sizeof(artis_radfield_config))
-    return rf_arg_error("radfield: artis_radfield_config.struct_size does not match");
-  if (!e->have_cells) return rf_arg_error("radfield: no cell state (artis_amd_set_cellstate)");
-  if (!(cfg->deltat > 0) || !std::isfinite(cfg->deltat)) return rf_arg_error("radfield: deltat must be positive and finite");
-  if (!(cfg->prev_mid > 0) || !std::isfinite(cfg->prev_mid)) return rf_arg_error("radfield: prev_mid must be positive and finite");
-  if (cfg->nprocs < 1) return rf_arg_error("radfield: nprocs < 1");
-  if (!cfg->assocvolume_tmin) return rf_arg_error("radfield: null assocvolume_tmin");
-  const int64_t ncell = e->Mh.npts_nonempty;
-  for (int64_t c = 0; c < ncell; c++)
-    if (!(cfg->assocvolume_tmin[c] > 0) || !std::isfinite(cfg->assocvolume_tmin[c]))
-      return rf_arg_error("radfield: assocvolume_tmin must be positive and finite in every cell");
-  if (e->E.bfrate_raw && e->bfrate_kept_dirty)
-    return rf_arg_error("radfield: the last propagation call ended in an error, the bound-free estimators are incomplete");
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = rf_init(e);
-  if (rc != ARTIS_OK) return rc;
-  RfState *st = e->rf;
-  st->valid = false;
-  hipStream_t s = (hipStream_t)hip_stream;
-  HIP_TRY(hipMemcpyAsync(st->d_assocvol, cfg->assocvolume_tmin, sizeof(double) * (size_t)ncell, hipMemcpyHostToDevice, s));
-  if (cfg->bfrate_normed_seed && st->nbf > 0)
-    HIP_TRY(hipMemcpyAsync(st->d_bf, cfg->bfrate_normed_seed, sizeof(float) * (size_t)(ncell * st->nbf), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(st->d_totals, 0, sizeof(unsigned long long) * ARTIS_RADFIELD_NCOUNTS, s));
-  RfArgs a{};
-  a.ncell = ncell;
-  a.J_raw = e->E.J;
-  a.nuJ_raw = e->E.nuJ;
-  a.bin_est = e->E.radfieldbin_J;
-  a.bfrate_raw = e->E.bfrate_raw;
-  a.Jb_raw = e->E.Jb_lu_raw;
-  a.Jb_count = e->E.Jb_lu_contribcount;
-  a.assocvol = st->d_assocvol;
-  a.thick = e->C.thick;
-  a.TJ = e->C.TJ;
-  a.TR = e->C.TR;
-  a.Te = e->C.Te;
-  a.W = e->C.W;
-  a.prev_bin_T_R = e->C.radfieldbin_T_R;
-  a.prev_bin_W = e->C.radfieldbin_W;
-  a.prev_mid = cfg->prev_mid;
-  a.tmin = e->model_copy.tmin;
-  a.deltat = cfg->deltat;
-  a.nprocs = cfg->nprocs;
-  a.lte = cfg->lte_iteration != 0;
-  a.nbf = (int32_t)st->nbf;
-  a.nline = (int32_t)st->nline;
-  a.J = st->d_J;
-  a.nuJ = st->d_nuJ;
-  a.normfactor = st->d_normfactor;
-  a.oTJ = st->d_TJ;
-  a.oTR = st->d_TR;
-  a.oTe = st->d_Te;
-  a.oW = st->d_W;
-  a.flags = st->d_flags;
-  a.counts = st->d_counts;
-  a.bin_T_R = st->d_bin_T_R;
-  a.bin_W = st->d_bin_W;
-  a.bf = st->d_bf;
-  a.Jb = st->d_Jb;
-  a.Jbcount = st->d_Jbcount;
-  a.totals = st->d_totals;
-  HIP_TRY(hipEventRecord(st->ev[0], s));
-  if (ncell > 0) {
-    hipLaunchKernelGGL(k_rf_cell, dim3(nblocks(ncell * 64)), dim3(BLOCK), 0, s, a);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipEventRecord(st->ev[1], s));
-  if (ncell > 0 && st->nbins > 0) {
-    hipLaunchKernelGGL(k_rf_bins, dim3(nblocks(ncell * st->nbins)), dim3(BLOCK), 0, s, a);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipEventRecord(st->ev[2], s));
-  HIP_TRY(hipMemcpyAsync(st->totals, st->d_totals, sizeof(st->totals), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  float ms0 = 0.f, ms1 = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms0, st->ev[0], st->ev[1]));
-  HIP_TRY(hipEventElapsedTime(&ms1, st->ev[1], st->ev[2]));
-  st->kernel_ms[0] = ms0;
-  st->kernel_ms[1] = ms1;
-  st->prev_mid = cfg->prev_mid;
-  st->deltat = cfg->deltat;
-  st->nprocs = cfg->nprocs;
-  st->lte = a.lte;
-  st->valid = true;
-  e->fit_since_step = true;
-  return ARTIS_OK;
-}
-
-int artis_amd_radfield_download(artis_amd_engine *e, artis_radfield *out) {
-  if (!e || !out) return rf_arg_error("radfield: null argument");
-  if (out->struct_size != (int64_t)sizeof(artis_radfield)) return rf_arg_error("radfield: artis_radfield.struct_size does not match");
-  if (!e->rf || !e->rf->valid) return rf_arg_error("radfield: nothing fitted (artis_amd_radfield_fit)");
-  RfState *st = e->rf;
-  if (((out->radfieldbin_T_R || out->radfieldbin_W) && st->nbins == 0) || (out->bfrate_normed && st->nbf == 0) ||
-      ((out->Jb_lu_normed || out->Jb_lu_contribcount) && st->nline == 0))
-    return rf_arg_error("radfield: an array was asked for that this build does not make");
-  HIP_TRY(hipSetDevice(e->device));
-  const int64_t n = st->ncell;
-  auto get = [&](void *dst, const void *src, int64_t count, size_t elem) -> hipError_t {
-    if (!dst || count <= 0) return hipSuccess;
-    return hipMemcpy(dst, src, elem * (size_t)count, hipMemcpyDeviceToHost);
-  };
-  HIP_TRY(get(out->J, st->d_J, n, sizeof(double)));
-  HIP_TRY(get(out->nuJ, st->d_nuJ, n, sizeof(double)));
-  HIP_TRY(get(out->J_normfactor, st->d_normfactor, n, sizeof(double)));
-  HIP_TRY(get(out->TJ, st->d_TJ, n, sizeof(float)));
-  HIP_TRY(get(out->TR, st->d_TR, n, sizeof(float)));
-  HIP_TRY(get(out->Te, st->d_Te, n, sizeof(float)));
-  HIP_TRY(get(out->W, st->d_W, n, sizeof(float)));
-  HIP_TRY(get(out->flags, st->d_flags, n, sizeof(int32_t)));
-  HIP_TRY(get(out->cell_counts, st->d_counts, n * ARTIS_RADFIELD_NCOUNTS, sizeof(int32_t)));
-  HIP_TRY(get(out->radfieldbin_T_R, st->d_bin_T_R, n * st->nbins, sizeof(float)));
-  HIP_TRY(get(out->radfieldbin_W, st->d_bin_W, n * st->nbins, sizeof(float)));
-  HIP_TRY(get(out->bfrate_normed, st->d_bf, n * st->nbf, sizeof(float)));
-  HIP_TRY(get(out->Jb_lu_normed, st->d_Jb, n * st->nline, sizeof(double)));
-  if (out->Jb_lu_contribcount && st->nline > 0) {
-    std::vector<double> cnt((size_t)(n * st->nline));
-    HIP_TRY(get(cnt.data(), st->d_Jbcount, n * st->nline, sizeof(double)));
-    for (size_t i = 0; i < cnt.size(); i++) out->Jb_lu_contribcount[i] = (int64_t)cnt[i];
-  }
-  for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) out->totals[k] = (int64_t)st->totals[k];
-  out->npts_nonempty = (int32_t)n;
-  out->nbins = (int32_t)st->nbins;
-  out->nbfestim = (int32_t)st->nbf;
-  out->detailed_linecount = (int32_t)st->nline;
-  out->kernel_ms[0] = st->kernel_ms[0];
-  out->kernel_ms[1] = st->kernel_ms[1];
-  return ARTIS_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------ ionisation balance and hand-over (ion_balance.h)
-// Kernels on the caller's stream, every output element with one writer: k_ib_alpha_sp (first call: the [nions][TABLESIZE]
-// ion_alpha_sp table and each ion's ground-continuum index), k_ib_cells (one lane per cell: temperatures, nnetot), k_ib_gamma (one
-// lane per (cell, ground continuum): the normalised gamma estimator), k_ib_partfunct (one lane per (cell, ion), levels summed in
-// order), k_ib_phi (one lane per (cell, ion): phi once, into a [cell][ion] array), k_ib_solve (one lane per cell: uppermost ions,
-// n_e root search, ground populations, final n_e). Flags are integer ORs. Nothing reaches the engine's cell state until every
-// cell has been balanced; then the arrays are copied over and the cell cache is filled.
-namespace {
-
-struct IbArgs {
-  artis::DevModel M;
-  int64_t ncell;
-  int32_t use_fit, lte, nbfg;
-  // inputs
-  const float *fit_TJ, *fit_TR, *fit_W, *fit_Te;  // the fit's (use_fit) or the host's (uploaded)
-  const int32_t *fit_flags;                       // the fit's per-cell flags (use_fit)
-  const float *host_Te;                           // Te override of fitted cells, or null
-  const float *cur_ground;                        // the cell state's ground populations (for the partition functions)
-  const int32_t *cur_thick;                       // ... thickness (the balance's Saha switch)
-  const double *gamma_raw;                        // [cell][ground continuum][2]{gamma, bfheating} of the estimator block
-  const double *assocvol;
-  double prev_mid, tmin, deltat;
-  int32_t nprocs;
-  const float *rho, *massfrac, *meanweight_cell, *meanweight_model, *clump;
-  // scratch / outputs
-  float *alpha_sp;
-  int32_t *gci;
-  float *TJ, *TR, *W, *Te, *nnetot, *U, *ground, *nne, *nne_root;
-  double *gamma, *phi;
-  int32_t *uppermost, *flags, *evals;
-};
-
-__global__ void __launch_bounds__(BLOCK) k_ib_alpha_sp(IbArgs a) {
-  const artis::DevModel &M = a.M;
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= (int64_t)M.nions * ARTIS_OPT_TABLESIZE) return;
-  const int ui = (int)(i / ARTIS_OPT_TABLESIZE);
-  const int tempindex = (int)(i - (int64_t)ui * ARTIS_OPT_TABLESIZE);
-  const int element = M.ion_element[ui];
-  const int ion = ui - M.elem_uniqueionindexstart[element];
-  float v = 0.f;
-  if (ion < M.elem_nions[element] - 1) {
-    const auto T_e = static_cast<float>(M.temperature_grid[tempindex]);
-    v = static_cast<float>(artis_ib::ionrecombcoeff_lte_targetpop(M, T_e, element, ion + 1));
-  }
-  a.alpha_sp[i] = v;
-  if (tempindex == 0) a.gci[ui] = artis_ib::ion_groundcontindex(M, element, ion);
-}
-
-__device__ inline const float *ib_meanweight(const IbArgs &a, int64_t c) {
-  return a.meanweight_cell ? a.meanweight_cell + c * a.M.nelements : a.meanweight_model;
-}
-
-__global__ void __launch_bounds__(BLOCK) k_ib_cells(IbArgs a) {
-  const int64_t c = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (c >= a.ncell) return;
-  float Te = a.fit_Te[c];
-  if (a.use_fit && a.host_Te && (a.fit_flags[c] & ARTIS_RADFIELD_FITTED)) Te = a.host_Te[c];
-  a.Te[c] = Te;
-  a.TJ[c] = a.fit_TJ[c];
-  a.TR[c] = a.fit_TR[c];
-  a.W[c] = a.fit_W[c];
-  a.nnetot[c] = artis_ib::nnetot(a.M, a.massfrac + c * a.M.nelements, ib_meanweight(a, c), a.rho[c]);
-  a.flags[c] = (a.lte || a.cur_thick[c] == ARTIS_CELL_THICK) ? artis_ib::FORCED_SAHA : 0;
-}
-
-__global__ void __launch_bounds__(BLOCK) k_ib_gamma(IbArgs a) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a.ncell * a.nbfg) return;
-  double g = 0.;
-  if (a.use_fit) {
-    const int64_t c = i / a.nbfg;
-    double estimator_normfactor, over4pi;
-    artis_rf::cell_normfactors(a.assocvol[c], a.prev_mid, a.tmin, a.deltat, a.nprocs, &estimator_normfactor, &over4pi);
-    g = a.gamma_raw[2 * i] * (estimator_normfactor / artis_rf::H);
-  }
-  a.gamma[i] = g;
-}
-
-__global__ void __launch_bounds__(BLOCK) k_ib_partfunct(IbArgs a) {
-  const artis::DevModel &M = a.M;
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a.ncell * M.nions) return;
-  const int64_t c = i / M.nions;
-  const int ui = (int)(i - c * M.nions);
-  const int element = M.ion_element[ui];
-  const int ion = ui - M.elem_uniqueionindexstart[element];
-  const float T_exc = ARTIS_OPT_LTEPOP_EXCITATION_USE_TJ ? a.TJ[c] : a.Te[c];
-  int32_t flags = 0;
-  a.U[i] = artis_ib::partfunct(M, element, ion, a.cur_ground[i], a.massfrac[c * M.nelements + element], T_exc, &flags);
-  if (flags) atomicOr(&a.flags[c], flags);
-}
-
-__global__ void __launch_bounds__(BLOCK) k_ib_phi(IbArgs a) {
-  const artis::DevModel &M = a.M;
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= a.ncell * M.nions) return;
-  const int64_t c = i / M.nions;
-  const int ui = (int)(i - c * M.nions);
-  const int element = M.ion_element[ui];
-  const int ion = ui - M.elem_uniqueionindexstart[element];
-  double phi = 0.;
-  if (ion < M.elem_nions[element] - 1) {
-    const bool force_saha = (a.flags[c] & artis_ib::FORCED_SAHA) != 0;
-    if (artis_ib::use_phi_saha(force_saha)) {
-      phi = artis_ib::phi_saha(M, element, ion, a.U[i], a.U[i + 1], a.Te[c]);
-    } else {
-      const int g = a.gci[ui];
-      phi = artis_ib::phi_rate_balance(M, a.alpha_sp, element, ion, a.U[i], a.Te[c], a.clump[c], g >= 0 ? a.gamma[c * a.nbfg + g] : 0.);
-    }
-  }
-  a.phi[i] = phi;
-}
-
-__global__ void __launch_bounds__(BLOCK) k_ib_solve(IbArgs a) {
-  const artis::DevModel &M = a.M;
-  const int64_t c = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (c >= a.ncell) return;
-  int32_t flags = a.flags[c];
-  const artis_ib::Cell cell{a.rho[c], a.massfrac + c * M.nelements, ib_meanweight(a, c), a.U + c * M.nions, a.phi + c * M.nions,
-                            a.gamma + c * a.nbfg, a.gci, a.uppermost + c * M.nelements};
-  float nne_root = 0.f;
-  int evals = 0;
-  float nne = 0.f;
-  float *ground = a.ground + c * M.nions;
-  if (flags & artis_ib::REFUSED) {  // an invalid partition function: nothing to balance
-    for (int i = 0; i < M.nions; i++) ground[i] = 0.f;
-    for (int e = 0; e < M.nelements; e++) cell.uppermost[e] = -1;
-  } else {
-    nne = artis_ib::ion_balance_nne(M, cell, (flags & artis_ib::FORCED_SAHA) != 0, ground, &nne_root, &evals, &flags);
-    if (flags & artis_ib::REFUSED)
-      for (int i = 0; i < M.nions; i++) ground[i] = 0.f;
-  }
-  a.nne[c] = nne;
-  a.nne_root[c] = nne_root;
-  a.evals[c] = evals;
-  a.flags[c] = flags;
-}
-
-// corrphotoionrenorm = 1 in the cells balanced with forced Saha (update_grid.cc:539-543)
-__global__ void __launch_bounds__(BLOCK) k_ib_renorm(double *renorm, const int32_t *flags, int64_t ncell, int32_t nbfg) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= ncell * nbfg) return;
-  if (flags[i / nbfg] & artis_ib::FORCED_SAHA) renorm[i] = 1.;
-}
-
-// the scratch of artis_amd_grid_update*: one block, made at the first call
-struct IbState {
-  void *d_block = nullptr;
-  size_t bytes = 0;
-  int64_t ncell = 0, nions = 0, nelements = 0, nbfg = 0;
-  float *d_alpha_sp = nullptr, *d_hTJ = nullptr, *d_hTR = nullptr, *d_hW = nullptr, *d_hTe = nullptr;
-  int32_t *d_gci = nullptr, *d_thick = nullptr;
-  float *d_rho = nullptr, *d_massfrac = nullptr, *d_meanweight = nullptr, *d_kappagrey = nullptr, *d_clump = nullptr, *d_ffegrp = nullptr;
-  float *d_TJ = nullptr, *d_TR = nullptr, *d_W = nullptr, *d_Te = nullptr, *d_nnetot = nullptr, *d_U = nullptr, *d_ground = nullptr;
-  float *d_nne = nullptr, *d_nne_root = nullptr;
-  double *d_gamma = nullptr, *d_phi = nullptr;
-  int32_t *d_uppermost = nullptr, *d_flags = nullptr, *d_evals = nullptr;
-  hipEvent_t ev[ARTIS_IONBAL_NTIMES + 1] = {};
-  bool have_alpha_sp = false, valid = false;
-  int64_t ncells_flagged[8] = {}, total_evals = 0;
-  double kernel_ms[ARTIS_IONBAL_NTIMES] = {};
-};
-
-void ib_free(IbState *st) {
-  if (!st) return;
-  if (st->d_block) (void)hipFree(st->d_block);
-  for (hipEvent_t ev : st->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete st;
-}
-
-int ib_error(int rc, const std::string &msg) {
-  g_last_error = "grid_update: " + msg;
-  return rc;
-}
-
-size_t ib_layout(IbState *st, char *base) {
-  size_t off = 0;
-  auto take = [&](auto **p, int64_t count, size_t elem) {
-    const size_t sz = ((size_t)(count > 0 ? count : 0) * elem + 255) & ~(size_t)255;
-    if (base) *p = count > 0 ? (std::remove_reference_t<decltype(*p)>)(base + off) : nullptr;
-    off += sz;
-  };
-  const int64_t n = st->ncell, ni = st->nions, ne = st->nelements;
-  take(&st->d_alpha_sp, ni * ARTIS_OPT_TABLESIZE, sizeof(float));
-  take(&st->d_gci, ni, sizeof(int32_t));
-  for (float **p : {&st->d_hTJ, &st->d_hTR, &st->d_hW, &st->d_hTe, &st->d_rho, &st->d_kappagrey, &st->d_clump, &st->d_ffegrp, &st->d_TJ,
-                    &st->d_TR, &st->d_W, &st->d_Te, &st->d_nnetot, &st->d_nne, &st->d_nne_root})
-    take(p, n, sizeof(float));
-  take(&st->d_thick, n, sizeof(int32_t));
-  take(&st->d_massfrac, n * ne, sizeof(float));
-  take(&st->d_meanweight, n * ne, sizeof(float));
-  take(&st->d_U, n * ni, sizeof(float));
-  take(&st->d_ground, n * ni, sizeof(float));
-  take(&st->d_gamma, n * st->nbfg, sizeof(double));
-  take(&st->d_phi, n * ni, sizeof(double));
-  take(&st->d_uppermost, n * ne, sizeof(int32_t));
-  take(&st->d_flags, n, sizeof(int32_t));
-  take(&st->d_evals, n, sizeof(int32_t));
-  return off;
-}
-
-int ib_init(artis_amd_engine *e) {
-  if (e->ib) return ARTIS_OK;
-  const DevModel &h = e->Mh;
-  // the per-cell solve holds one element's ion fractions in registers / scratch of MAXIONS entries
-  std::vector<int32_t> nions((size_t)(h.nelements > 0 ? h.nelements : 1));
-  if (h.nelements > 0)
-    HIP_TRY(hipMemcpy(nions.data(), e->M.elem_nions, sizeof(int32_t) * (size_t)h.nelements, hipMemcpyDeviceToHost));
-  for (int el = 0; el < h.nelements; el++)
-    if (nions[(size_t)el] > artis_ib::MAXIONS)
-      return ib_error(ARTIS_ERR_UNSUPPORTED, "an element has more than " + std::to_string(artis_ib::MAXIONS) + " ions");
-  IbState *st = new IbState();
-  st->ncell = h.npts_nonempty;
-  st->nions = h.nions;
-  st->nelements = h.nelements;
-  st->nbfg = h.nbfcontinua_ground;
-  st->bytes = ib_layout(st, nullptr);
-  size_t free_b = 0, total_b = 0;
-  hipError_t err = hipMemGetInfo(&free_b, &total_b);
-  if (err == hipSuccess && (double)st->bytes > 0.9 * (double)free_b) {
-    delete st;
-    return ib_error(ARTIS_ERR_ARG, "the scratch does not fit the free device memory");
-  }
-  if (err == hipSuccess) err = hipMalloc(&st->d_block, st->bytes);
-  if (err == hipSuccess) err = hipMemset(st->d_block, 0, st->bytes);
-  for (hipEvent_t &ev : st->ev)
-    if (err == hipSuccess) err = hipEventCreate(&ev);
-  if (err != hipSuccess) {
-    ib_free(st);
-    return ib_error(ARTIS_ERR_HIP, std::string("allocation of the scratch: ") + hipGetErrorString(err));
-  }
-  ib_layout(st, (char *)st->d_block);
-  e->ib = st;
-  return ARTIS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int artis_amd_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream) {
-  if (!e || !u || !ts_next) return ib_error(ARTIS_ERR_ARG, "null engine, update or timestep");
-#ifdef ARTIS_PRESET_NLTENEBULAR
-  return ib_error(ARTIS_ERR_UNSUPPORTED, "this build has NLTE populations (the nebular family): the ion balance is the host's");
-#endif
-  if (u->struct_size != (int64_t)sizeof(artis_grid_update)) return ib_error(ARTIS_ERR_ARG, "artis_grid_update.struct_size does not match");
-  if (!e->have_cells) return ib_error(ARTIS_ERR_ARG, "no cell state (artis_amd_set_cellstate)");
-  if (u->use_fit != 0 && u->use_fit != 1) return ib_error(ARTIS_ERR_ARG, "use_fit must be 0 or 1");
-  if (u->use_fit && (!e->rf || !e->rf->valid || !e->fit_since_step))
-    return ib_error(ARTIS_ERR_ARG, "use_fit = 1 needs an artis_amd_radfield_fit since the last propagation call");
-  if (!u->use_fit && (!u->TJ || !u->TR || !u->W || !u->Te)) return ib_error(ARTIS_ERR_ARG, "use_fit = 0 needs TJ, TR, W and Te");
-  if (!u->rho || !u->elem_massfracs || !u->thick) return ib_error(ARTIS_ERR_ARG, "rho, elem_massfracs and thick are required");
-  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !u->elem_meanweight)
-    return ib_error(ARTIS_ERR_ARG, "this build has USE_CALCULATED_MEANATOMICWEIGHT: elem_meanweight is required");
-  if (!ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !e->M.elem_meannucmass)
-    return ib_error(ARTIS_ERR_ARG, "the element number densities need artis_model.elem_meannucmass");
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = ib_init(e);
-  if (rc != ARTIS_OK) return rc;
-  IbState *st = e->ib;
-  st->valid = false;
-  hipStream_t s = (hipStream_t)hip_stream;
-  const int64_t n = st->ncell, ni = st->nions, ne = st->nelements;
-  auto put = [&](void *dst, const void *src, int64_t count, size_t elem) -> hipError_t {
-    if (!src || count <= 0) return hipSuccess;
-    return hipMemcpyAsync(dst, src, elem * (size_t)count, hipMemcpyHostToDevice, s);
-  };
-  HIP_TRY(put(st->d_rho, u->rho, n, sizeof(float)));
-  HIP_TRY(put(st->d_massfrac, u->elem_massfracs, n * ne, sizeof(float)));
-  HIP_TRY(put(st->d_thick, u->thick, n, sizeof(int32_t)));
-  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT) HIP_TRY(put(st->d_meanweight, u->elem_meanweight, n * ne, sizeof(float)));
-  HIP_TRY(put(st->d_kappagrey, u->kappagrey, n, sizeof(float)));
-  HIP_TRY(put(st->d_clump, u->clumpfactor, n, sizeof(float)));
-  HIP_TRY(put(st->d_ffegrp, u->ffegrp, n, sizeof(float)));
-  if (!u->use_fit) {
-    HIP_TRY(put(st->d_hTJ, u->TJ, n, sizeof(float)));
-    HIP_TRY(put(st->d_hTR, u->TR, n, sizeof(float)));
-    HIP_TRY(put(st->d_hW, u->W, n, sizeof(float)));
-  }
-  if (u->Te) HIP_TRY(put(st->d_hTe, u->Te, n, sizeof(float)));
-  IbArgs a{};
-  a.M = e->M;
-  a.ncell = n;
-  a.use_fit = u->use_fit;
-  a.lte = u->use_fit ? e->rf->lte : 1;
-  a.nbfg = (int32_t)st->nbfg;
-  a.fit_TJ = u->use_fit ? e->rf->d_TJ : st->d_hTJ;
-  a.fit_TR = u->use_fit ? e->rf->d_TR : st->d_hTR;
-  a.fit_W = u->use_fit ? e->rf->d_W : st->d_hW;
-  a.fit_Te = u->use_fit ? e->rf->d_Te : st->d_hTe;
-  a.fit_flags = u->use_fit ? e->rf->d_flags : nullptr;
-  a.host_Te = (u->use_fit && u->Te) ? st->d_hTe : nullptr;
-  a.cur_ground = e->C.ion_groundlevelpops;
-  a.cur_thick = e->C.thick;
-  a.gamma_raw = e->E.gammaestimator;
-  if (u->use_fit) {
-    a.assocvol = e->rf->d_assocvol;
-    a.prev_mid = e->rf->prev_mid;
-    a.deltat = e->rf->deltat;
-    a.nprocs = e->rf->nprocs;
-  }
-  a.tmin = e->model_copy.tmin;
-  a.rho = st->d_rho;
-  a.massfrac = st->d_massfrac;
-  a.meanweight_cell = ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT ? st->d_meanweight : nullptr;
-  a.meanweight_model = e->M.elem_meannucmass;
-  a.clump = u->clumpfactor ? st->d_clump : e->C.clumpfactor;
-  a.alpha_sp = st->d_alpha_sp;
-  a.gci = st->d_gci;
-  a.TJ = st->d_TJ;
-  a.TR = st->d_TR;
-  a.W = st->d_W;
-  a.Te = st->d_Te;
-  a.nnetot = st->d_nnetot;
-  a.U = st->d_U;
-  a.ground = st->d_ground;
-  a.nne = st->d_nne;
-  a.nne_root = st->d_nne_root;
-  a.gamma = st->d_gamma;
-  a.phi = st->d_phi;
-  a.uppermost = st->d_uppermost;
-  a.flags = st->d_flags;
-  a.evals = st->d_evals;
-  // every kernel is checked where it ends, so that an error names it (the calls are few and the kernels short)
-  auto done = [&](const char *kernel) -> int {
-    hipError_t err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(s);
-    if (err != hipSuccess) return ib_error(ARTIS_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(err));
-    return ARTIS_OK;
-  };
-  if (!st->have_alpha_sp && ni > 0) {  // kept for the engine's lifetime
-    hipLaunchKernelGGL(k_ib_alpha_sp, dim3(nblocks(ni * ARTIS_OPT_TABLESIZE)), dim3(BLOCK), 0, s, a);
-    if ((rc = done("k_ib_alpha_sp")) != ARTIS_OK) return rc;
-    st->have_alpha_sp = true;
-  }
-  HIP_TRY(hipEventRecord(st->ev[0], s));
-  if (n > 0) {
-    hipLaunchKernelGGL(k_ib_cells, dim3(nblocks(n)), dim3(BLOCK), 0, s, a);
-    if ((rc = done("k_ib_cells")) != ARTIS_OK) return rc;
-    if (st->nbfg > 0) hipLaunchKernelGGL(k_ib_gamma, dim3(nblocks(n * st->nbfg)), dim3(BLOCK), 0, s, a);
-    if ((rc = done("k_ib_gamma")) != ARTIS_OK) return rc;
-    if (ni > 0) hipLaunchKernelGGL(k_ib_partfunct, dim3(nblocks(n * ni)), dim3(BLOCK), 0, s, a);
-    if ((rc = done("k_ib_partfunct")) != ARTIS_OK) return rc;
-  }
-  HIP_TRY(hipEventRecord(st->ev[1], s));
-  if (n > 0 && ni > 0) hipLaunchKernelGGL(k_ib_phi, dim3(nblocks(n * ni)), dim3(BLOCK), 0, s, a);
-  if ((rc = done("k_ib_phi")) != ARTIS_OK) return rc;
-  HIP_TRY(hipEventRecord(st->ev[2], s));
-  if (n > 0) hipLaunchKernelGGL(k_ib_solve, dim3(nblocks(n)), dim3(BLOCK), 0, s, a);
-  if ((rc = done("k_ib_solve")) != ARTIS_OK) return rc;
-  HIP_TRY(hipEventRecord(st->ev[3], s));
-  std::vector<int32_t> flags((size_t)n), evals((size_t)n);
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(flags.data(), st->d_flags, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(evals.data(), st->d_evals, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  for (int k = 0; k < 3; k++) {
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, st->ev[k], st->ev[k + 1]));
-    st->kernel_ms[k] = ms;
-  }
-  st->kernel_ms[3] = 0.;
-  int64_t refused = 0;
-  std::fill(std::begin(st->ncells_flagged), std::end(st->ncells_flagged), 0);
-  st->total_evals = 0;
-  for (int64_t c = 0; c < n; c++) {
-    for (int k = 0; k < 8; k++)
-      if (flags[(size_t)c] & (1 << k)) st->ncells_flagged[k]++;
-    if (flags[(size_t)c] & artis_ib::REFUSED) refused++;
-    st->total_evals += evals[(size_t)c];
-  }
-  st->valid = true;
-  if (refused > 0)
-    return ib_error(ARTIS_ERR_NOTCONVERGED, std::to_string(refused) + " cells unbracketed, non-finite or with an invalid partition function (" +
-                                                std::to_string(st->ncells_flagged[4]) + " / " + std::to_string(st->ncells_flagged[6]) + " / " +
-                                                std::to_string(st->ncells_flagged[5]) + "); the previous cell state stays");
-  // the hand-over: the engine's cell state becomes the result (artis_amd_set_cellstate), then the cell cache is filled
-  auto d2d = [&](const void *dst, const void *src, int64_t count, size_t elem) -> hipError_t {
-    if (!dst || !src || count <= 0) return hipSuccess;
-    return hipMemcpyAsync(const_cast<void *>(dst), src, elem * (size_t)count, hipMemcpyDeviceToDevice, s);
-  };
-  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !e->C.elem_meanweight && n * ne > 0) {
-    float *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, sizeof(float) * (size_t)(n * ne)));
-    e->cell_allocs.push_back(d);
-    e->C.elem_meanweight = d;
-  }
-  HIP_TRY(d2d(e->C.rho, st->d_rho, n, sizeof(float)));
-  HIP_TRY(d2d(e->C.Te, st->d_Te, n, sizeof(float)));
-  HIP_TRY(d2d(e->C.TJ, st->d_TJ, n, sizeof(float)));
-  HIP_TRY(d2d(e->C.TR, st->d_TR, n, sizeof(float)));
-  HIP_TRY(d2d(e->C.W, st->d_W, n, sizeof(float)));
-  HIP_TRY(d2d(e->C.nne, st->d_nne, n, sizeof(float)));
-  HIP_TRY(d2d(e->C.nnetot, st->d_nnetot, n, sizeof(float)));
-  HIP_TRY(d2d(e->C.ion_partfuncts, st->d_U, n * ni, sizeof(float)));
-  HIP_TRY(d2d(e->C.ion_groundlevelpops, st->d_ground, n * ni, sizeof(float)));
-  HIP_TRY(d2d(e->C.elem_massfracs, st->d_massfrac, n * ne, sizeof(float)));
-  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT) HIP_TRY(d2d(e->C.elem_meanweight, st->d_meanweight, n * ne, sizeof(float)));
-  if (u->kappagrey) HIP_TRY(d2d(e->C.kappagrey, st->d_kappagrey, n, sizeof(float)));
-  if (u->clumpfactor) HIP_TRY(d2d(e->C.clumpfactor, st->d_clump, n, sizeof(float)));
-  if (u->ffegrp) HIP_TRY(d2d(e->C.ffegrp, st->d_ffegrp, n, sizeof(float)));
-  if (ARTIS_OPT_USE_LUT_PHOTOION && n > 0 && st->nbfg > 0) {
-    hipLaunchKernelGGL(k_ib_renorm, dim3(nblocks(n * st->nbfg)), dim3(BLOCK), 0, s, const_cast<double *>(e->C.corrphotoionrenorm),
-                       st->d_flags, n, (int32_t)st->nbfg);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(d2d(e->C.thick, st->d_thick, n, sizeof(int32_t)));  // (after the balance and the renormalisation, which read the current ones)
-  HIP_TRY(hipStreamSynchronize(s));
-  e->S = make_step(*ts_next);
-  const auto t0 = std::chrono::steady_clock::now();
-  rc = artis_amd_populate_cellcache(e, hip_stream);
-  st->kernel_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return rc;
-}
-
-int artis_amd_grid_update_download(artis_amd_engine *e, artis_grid_update_result *out) {
-  if (!e || !out) return ib_error(ARTIS_ERR_ARG, "null argument");
-  if (out->struct_size != (int64_t)sizeof(artis_grid_update_result))
-    return ib_error(ARTIS_ERR_ARG, "artis_grid_update_result.struct_size does not match");
-  if (!e->ib || !e->ib->valid) return ib_error(ARTIS_ERR_ARG, "nothing balanced (artis_amd_grid_update)");
-  IbState *st = e->ib;
-  HIP_TRY(hipSetDevice(e->device));
-  const int64_t n = st->ncell, ni = st->nions, ne = st->nelements;
-  auto get = [&](void *dst, const void *src, int64_t count, size_t elem) -> hipError_t {
-    if (!dst || count <= 0) return hipSuccess;
-    return hipMemcpy(dst, src, elem * (size_t)count, hipMemcpyDeviceToHost);
-  };
-  HIP_TRY(get(out->Te, st->d_Te, n, sizeof(float)));
-  HIP_TRY(get(out->TJ, st->d_TJ, n, sizeof(float)));
-  HIP_TRY(get(out->TR, st->d_TR, n, sizeof(float)));
-  HIP_TRY(get(out->W, st->d_W, n, sizeof(float)));
-  HIP_TRY(get(out->nne, st->d_nne, n, sizeof(float)));
-  HIP_TRY(get(out->nnetot, st->d_nnetot, n, sizeof(float)));
-  HIP_TRY(get(out->rho, st->d_rho, n, sizeof(float)));
-  HIP_TRY(get(out->ion_partfuncts, st->d_U, n * ni, sizeof(float)));
-  HIP_TRY(get(out->ion_groundlevelpops, st->d_ground, n * ni, sizeof(float)));
-  HIP_TRY(get(out->uppermost_ion, st->d_uppermost, n * ne, sizeof(int32_t)));
-  HIP_TRY(get(out->gamma_normed, st->d_gamma, n * st->nbfg, sizeof(double)));
-  HIP_TRY(get(out->phi, st->d_phi, n * ni, sizeof(double)));
-  HIP_TRY(get(out->nne_root, st->d_nne_root, n, sizeof(float)));
-  HIP_TRY(get(out->flags, st->d_flags, n, sizeof(int32_t)));
-  HIP_TRY(get(out->evals, st->d_evals, n, sizeof(int32_t)));
-  for (int k = 0; k < 8; k++) out->ncells_flagged[k] = st->ncells_flagged[k];
-  out->total_evals = st->total_evals;
-  out->npts_nonempty = (int32_t)n;
-  out->nions = (int32_t)ni;
-  out->nelements = (int32_t)ne;
-  out->nbfcontinua_ground = (int32_t)st->nbfg;
-  for (int k = 0; k < ARTIS_IONBAL_NTIMES; k++) out->kernel_ms[k] = st->kernel_ms[k];
-  return ARTIS_OK;
-}
-
-}  // extern "C"
+// ------------------------------------------------------------------ the timestep-end stages: spectra, radiation-field fit, ion balance
+#include "stage_common.h"
+#include "stage_spectra.h"
+#include "stage_radfield.h"
+#include "stage_ionbal.h"

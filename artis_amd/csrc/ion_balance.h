@@ -2,8 +2,8 @@
 // of the reference's grid update, ltepop.cc; element number densities grid.cc:1693-1730; the ions' total spontaneous
 // recombination coefficients ratecoeff.cc:438, :643, :687-773).
 //
-// The engine's kernels (artis_engine.hip, "ion balance") call these functions per (cell, ion) and per cell;
-// tests/ionbal_host compiles them for x86. Floating-point discipline as physics.h: -ffp-contract=off, and every expression
+// The engine's kernels (stage_ionbal.h) and the loops of tests/ionbal_host (x86) call the same per-element functions at the end
+// of this file. Floating-point discipline as physics.h: -ffp-contract=off, and every expression
 // keeps the reference's order of operations and its float/double mixing (partition functions, populations, n_e and the
 // ion_alpha_sp table are floats; U is summed in double in level order; phi_saha's ratio of partition functions is a float
 // quotient). The reference's assertions and log lines become flag bits (include/artis_amd.h ARTIS_IONBAL_*).
@@ -361,6 +361,117 @@ AHD float ion_balance_nne(const DevModel &M, const Cell &c, const bool force_sah
     for (int element = 0; element < M.nelements; element++) set_groundlevelpops(M, c, element, nne_solution, ground, flags);
   }
   return calculated_nne(M, c, ground);
+}
+
+// ---- one output element each: the bodies of the engine's kernels (stage_ionbal.h) and of the loops of tests/ionbal_host.
+// Whoever calls them keeps one writer per element; a cell's flags are ORed by the caller where several entries share them.
+
+// unique ion index -> (element, ion of the element)
+struct IonOf {
+  int element, ion;
+};
+AHD IonOf ion_of(const DevModel &M, const int ui) {
+  const int element = M.ion_element[ui];
+  return {element, ui - M.elem_uniqueionindexstart[element]};
+}
+
+// entry [ui][tempindex] of the ion_alpha_sp table (0 for an element's top ion: nothing recombines into it from above); the
+// entry of tempindex 0 also writes the ion's ground-continuum index
+AHD void alpha_sp_entry(const DevModel &M, const int ui, const int tempindex, float *alpha_sp, int32_t *gci) {
+  const IonOf k = ion_of(M, ui);
+  float v = 0.f;
+  if (k.ion < M.elem_nions[k.element] - 1) {
+    const auto T_e = static_cast<float>(M.temperature_grid[tempindex]);
+    v = static_cast<float>(ionrecombcoeff_lte_targetpop(M, T_e, k.element, k.ion + 1));
+  }
+  alpha_sp[(int64_t)ui * ARTIS_OPT_TABLESIZE + tempindex] = v;
+  if (tempindex == 0) gci[ui] = ion_groundcontindex(M, k.element, k.ion);
+}
+
+// the per-cell arrays of the set-up and the solve: inputs [ncell] and [ncell][nelements | nions | nbfg], then what solve_cell
+// writes (flags: seeded by cell_setup, ORed into by the partition functions)
+struct CellArrays {
+  const float *rho, *massfrac, *meanweight_cell, *meanweight_model;  // meanweight_cell null: the model's elem_meannucmass
+  const float *U;
+  const double *phi, *gamma;
+  const int32_t *gci;
+  int32_t nbfg;
+  int32_t *uppermost, *flags, *evals;
+  float *ground, *nne, *nne_root;
+};
+AHD const float *cell_meanweight(const DevModel &M, const CellArrays &a, const int64_t c) {
+  return a.meanweight_cell ? a.meanweight_cell + c * M.nelements : a.meanweight_model;
+}
+
+// the set-up of cell c: its T_e (the fit's or the host's; in a cell the fit has fitted -- fit_flags, null without a fit -- the
+// host's override Te_override, null without one), nnetot, and the flags' seed: FORCED_SAHA or nothing
+AHD void cell_setup(const DevModel &M, const int64_t c, const CellArrays &a, const float *Te_in, const float *Te_override,
+                    const int32_t *fit_flags, const bool forced_saha, float *Te, float *nnetot_out) {
+  float T = Te_in[c];
+  if (fit_flags && Te_override && (fit_flags[c] & ARTIS_RADFIELD_FITTED)) T = Te_override[c];
+  Te[c] = T;
+  nnetot_out[c] = nnetot(M, a.massfrac + c * M.nelements, cell_meanweight(M, a, c), a.rho[c]);
+  a.flags[c] = forced_saha ? FORCED_SAHA : 0;
+}
+// an LTE iteration and a THICK cell are balanced with forced Saha: the cells the radiation-field fit does not fit
+AHD bool cell_forced_saha(const int32_t lte_iteration, const int32_t thick) { return !artis_rf::cell_is_fitted(lte_iteration, thick); }
+
+// entry of the normalised gamma estimator (update_grid.cc:358) from the raw one and its cell's volume and timestep
+AHD double gamma_normed_entry(const double gamma_raw, const double assocvolume_tmin, const double prev_mid, const double tmin,
+                              const double deltat, const int32_t nprocs) {
+  double estimator_normfactor, over4pi;
+  artis_rf::cell_normfactors(assocvolume_tmin, prev_mid, tmin, deltat, nprocs, &estimator_normfactor, &over4pi);
+  return gamma_raw * (estimator_normfactor / artis_rf::H);
+}
+
+// U[c][ui] from the current ground populations; *flags gets INVALID_U
+AHD void partfunct_entry(const DevModel &M, const int64_t c, const int ui, const float *TJ, const float *Te, const float *ground_cur,
+                         const float *massfrac, float *U, int32_t *flags) {
+  const IonOf k = ion_of(M, ui);
+  const float T_exc = ARTIS_OPT_LTEPOP_EXCITATION_USE_TJ ? TJ[c] : Te[c];
+  const int64_t i = c * M.nions + ui;
+  U[i] = partfunct(M, k.element, k.ion, ground_cur[i], massfrac[c * M.nelements + k.element], T_exc, flags);
+}
+
+// phi[c][ui]: 0 for an element's top ion, else Saha or rate balance as the cell's flags (FORCED_SAHA) and the build say
+AHD void phi_entry(const DevModel &M, const int64_t c, const int ui, const int32_t cell_flags, const float *U, const float *Te,
+                   const float *clump, const float *alpha_sp, const int32_t *gci, const double *gamma, const int nbfg, double *phi) {
+  const IonOf k = ion_of(M, ui);
+  const int64_t i = c * M.nions + ui;
+  double p = 0.;
+  if (k.ion < M.elem_nions[k.element] - 1) {
+    if (use_phi_saha((cell_flags & FORCED_SAHA) != 0)) {
+      p = phi_saha(M, k.element, k.ion, U[i], U[i + 1], Te[c]);
+    } else {
+      const int g = gci[ui];
+      p = phi_rate_balance(M, alpha_sp, k.element, k.ion, U[i], Te[c], clump[c], g >= 0 ? gamma[c * nbfg + g] : 0.);
+    }
+  }
+  phi[i] = p;
+}
+
+// cell c from its U, phi and flags so far: uppermost ions, the n_e root, ground populations, n_e, evaluations, flags. A cell that
+// is REFUSED (before or by the solve) gets zero ground populations; one refused before it has no uppermost ions either (-1).
+AHD void solve_cell(const DevModel &M, const int64_t c, const CellArrays &a) {
+  int32_t flags = a.flags[c];
+  const Cell cell{a.rho[c], a.massfrac + c * M.nelements, cell_meanweight(M, a, c), a.U + c * M.nions, a.phi + c * M.nions,
+                  a.gamma + c * a.nbfg, a.gci, a.uppermost + c * M.nelements};
+  float nne_root = 0.f;
+  int evals = 0;
+  float nne = 0.f;
+  float *ground = a.ground + c * M.nions;
+  if (flags & REFUSED) {  // an invalid partition function: nothing to balance
+    for (int i = 0; i < M.nions; i++) ground[i] = 0.f;
+    for (int e = 0; e < M.nelements; e++) cell.uppermost[e] = -1;
+  } else {
+    nne = ion_balance_nne(M, cell, (flags & FORCED_SAHA) != 0, ground, &nne_root, &evals, &flags);
+    if (flags & REFUSED)
+      for (int i = 0; i < M.nions; i++) ground[i] = 0.f;
+  }
+  a.nne[c] = nne;
+  a.nne_root[c] = nne_root;
+  a.evals[c] = evals;
+  a.flags[c] = flags;
 }
 
 }  // namespace artis_ib

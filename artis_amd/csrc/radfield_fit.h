@@ -5,8 +5,8 @@
 // (get_T_J_from_J radfield.cc:956), otherwise fit a diluted blackbody to the whole spectrum (set_params_fullspec) and,
 // with the multibin model, one (W, T_R) per frequency bin (fit_parameters, find_bin_T_R: a bracketed TOMS 748 root of
 // the Planck mean frequency minus the bin's nuJ / J). The detailed bound-free and line estimators are normalised too
-// (normalise_bf_estimators radfield.cc:902-925, normalise_J :893-899). The engine's kernels (artis_engine.hip,
-// "radiation-field fit") call these functions per cell and per (cell, bin); tests/radfield_host compiles them for x86.
+// (normalise_bf_estimators radfield.cc:902-925, normalise_J :893-899). The engine's kernels (stage_radfield.h) and the loops of
+// tests/radfield_host (x86) call the same per-element functions at the end of this file.
 //
 // Floating-point discipline as physics.h: -ffp-contract=off, and every expression keeps the reference's order of
 // operations, float/double mixing included (pow4 of a float T_R is a float product, as the reference's auto template).
@@ -471,6 +471,68 @@ AHD CellOut fit_cell(const CellIn &in) {
 // normalise_bf_estimators radfield.cc:920
 AHD float bfrate_normed(const double bfrate_raw, const double estimator_normfactor) {
   return (float)(bfrate_raw * (estimator_normfactor / H));
+}
+// normalise_J on a detailed line's estimator radfield.cc:893-899 (J_normfactor: cell_normfactors' over4pi)
+AHD double Jb_lu_normed(const double Jb_lu_raw, const double J_normfactor) { return Jb_lu_raw * J_normfactor; }
+
+// ---- one output element each: the bodies of the engine's kernels (stage_radfield.h) and of the loops of tests/radfield_host.
+// Whoever calls them keeps one writer per element; the bin counts and the totals are summed by the caller.
+
+// A cell that is not fitted keeps the bins of the cell state; its bound-free block is left as it is (prev_bfrate_normed of a
+// THICK cell, and of every cell in an LTE iteration). Both follow from cell_is_fitted: update_grid_cell's one branch.
+AHD bool cell_bins_carried_over(const int32_t lte_iteration, const int32_t thick) { return !cell_is_fitted(lte_iteration, thick); }
+AHD bool cell_bf_rewritten(const int32_t lte_iteration, const int32_t thick) { return cell_is_fitted(lte_iteration, thick); }
+
+// the per-cell outputs of the fit, [ncell] each; counts [ncell][ARTIS_RADFIELD_NCOUNTS]
+struct CellArrays {
+  double *J, *nuJ, *J_normfactor;
+  float *TJ, *TR, *Te, *W;
+  int32_t *flags, *counts;
+};
+
+// cell c: fit it, store its outputs, zero its bin counts
+AHD void fit_cell_store(const int64_t c, const CellIn &in, const CellArrays &o) {
+  const CellOut r = fit_cell(in);
+  o.J[c] = r.J;
+  o.nuJ[c] = r.nuJ;
+  o.J_normfactor[c] = r.J_normfactor;
+  o.TJ[c] = r.TJ;
+  o.TR[c] = r.TR;
+  o.Te[c] = r.Te;
+  o.W[c] = r.W;
+  o.flags[c] = r.flags;
+  for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) o.counts[c * ARTIS_RADFIELD_NCOUNTS + k] = 0;
+}
+
+// entry i = c * NBINS + b of a cell whose bins are carried over
+AHD void carry_bin(const int64_t i, const float *prev_bin_T_R, const float *prev_bin_W, float *bin_T_R, float *bin_W) {
+  bin_T_R[i] = prev_bin_T_R[i];
+  bin_W[i] = prev_bin_W[i];
+}
+// entry i = c * nbf + k of a cell whose bound-free block is rewritten
+AHD void bf_entry(const int64_t i, const double *bfrate_raw, const double estimator_normfactor, float *bf) {
+  bf[i] = bfrate_normed(bfrate_raw[i], estimator_normfactor);
+}
+// entry i = c * nline + k of the detailed lines (the contribution count is passed on in the caller's types)
+template <class CountIn, class CountOut>
+AHD void line_entry(const int64_t i, const double *Jb_lu_raw, const CountIn *count_in, const double J_normfactor, double *Jb_lu,
+                    CountOut *count_out) {
+  Jb_lu[i] = Jb_lu_normed(Jb_lu_raw[i], J_normfactor);
+  count_out[i] = count_in[i];
+}
+
+// entry i = c * NBINS + b of a fitted cell (flags, J_normfactor: fit_cell_store's; T_e: the cell state's): its (T_R, W) from the
+// bin's raw estimators at *J_raw, *nuJ_raw. Returns the BIN_* bits, bit k being count k; 0 and nothing written in any other cell.
+AHD int fit_bin_store(const int64_t i, const double *J_raw, const double *nuJ_raw, const int32_t *flags, const double *J_normfactor,
+                      const float *T_e, float *bin_T_R, float *bin_W) {
+  const int64_t c = i / NBINS;
+  const int b = (int)(i - c * NBINS);
+  if (!(flags[c] & ARTIS_RADFIELD_FITTED)) return 0;
+  float T_R, W;
+  const int bits = fit_bin(*J_raw, *nuJ_raw, J_normfactor[c], b, T_e[c], &T_R, &W);
+  bin_T_R[i] = T_R;
+  bin_W[i] = W;
+  return bits;
 }
 
 }  // namespace artis_rf

@@ -1,12 +1,11 @@
 """Shared by tests/test_ion_balance_rules.py and tests/test_gpu_ion_balance.py: the x86 build of artis_amd/csrc/ion_balance.h
 (tests/ionbal_host, made on first use) and its per-cell balance applied to host arrays."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
 
+import host_build
 from artis_amd import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -19,10 +18,7 @@ _LIBS = {}
 def lib(preset: str = "classic"):
     if preset in _LIBS:
         return _LIBS[preset]
-    with open(os.path.join(HOSTDIR, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        subprocess.check_call(["make", "-C", HOSTDIR], stdout=subprocess.DEVNULL)
-    L = C.CDLL(os.path.join(HOSTDIR, f"libionbal_host_{preset}.so"))
+    L = host_build.load(HOSTDIR, lambda p: f"libionbal_host_{p}.so", preset)
     L.ib_host_model_new.restype = C.c_void_p
     L.ib_host_model_new.argtypes = [C.c_void_p]
     L.ib_host_model_free.argtypes = [C.c_void_p]

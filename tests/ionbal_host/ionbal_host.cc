@@ -1,7 +1,7 @@
 // ionbal_host.cc -- TEST HARNESS ONLY (never shipped, never loaded by the artis_amd package).
 //
-// The per-(cell, ion) and per-cell functions of artis_amd/csrc/ion_balance.h compiled for x86 with g++ and applied in plain
-// loops (cells split over a few std::threads) to host copies of the inputs: what artis_amd_grid_update computes on the device
+// The per-element bodies of artis_amd/csrc/ion_balance.h -- the ones the engine's kernels call -- compiled for x86 with g++ and
+// applied in plain loops (cells split over a few std::threads) to host copies of the inputs: what artis_amd_grid_update computes on the device
 // once its temperatures, gamma estimators and thickness are resolved. Also exports the pieces (the ion_alpha_sp table, the
 // ground-continuum indices, the n_e residual of one cell) for tests/test_ion_balance_rules.py.
 #define ARTIS_HOST_EMU 1
@@ -57,17 +57,8 @@ void ib_host_temperature_grid(const void *h, double *out) {
 void ib_host_alpha_sp(const void *h, float *alpha_sp, int32_t *gci) {
   const HostModel &hm = *static_cast<const HostModel *>(h);
   const DevModel &M = hm.M;
-  for (int ui = 0; ui < M.nions; ui++) {
-    const int element = M.ion_element[ui];
-    const int ion = ui - M.elem_uniqueionindexstart[element];
-    gci[ui] = artis_ib::ion_groundcontindex(M, element, ion);
-    for (int t = 0; t < ARTIS_OPT_TABLESIZE; t++) {
-      float v = 0.f;
-      if (ion < M.elem_nions[element] - 1)
-        v = static_cast<float>(artis_ib::ionrecombcoeff_lte_targetpop(M, static_cast<float>(M.temperature_grid[t]), element, ion + 1));
-      alpha_sp[(int64_t)ui * ARTIS_OPT_TABLESIZE + t] = v;
-    }
-  }
+  for (int ui = 0; ui < M.nions; ui++)
+    for (int t = 0; t < ARTIS_OPT_TABLESIZE; t++) artis_ib::alpha_sp_entry(M, ui, t, alpha_sp, gci);
 }
 
 // get_ion_spontrecombcoeff of an ion at T_e on a given table
@@ -90,51 +81,16 @@ void ib_host_balance(const void *h, int64_t ncell, const float *TJ, const float 
   std::vector<float> alpha_sp((size_t)M.nions * ARTIS_OPT_TABLESIZE + 1);
   std::vector<int32_t> gci((size_t)M.nions + 1);
   ib_host_alpha_sp(h, alpha_sp.data(), gci.data());
-  const int ni = M.nions, ne = M.nelements, nbfg = M.nbfcontinua_ground;
+  std::vector<float> Te_cell((size_t)ncell + 1);  // (cell_setup's copy of Te: no override here)
+  const artis_ib::CellArrays a{rho, massfrac, meanweight, M.elem_meannucmass, U, phi, gamma, gci.data(), M.nbfcontinua_ground,
+                               uppermost, flags, evals, ground, nne, nne_root};
   parallel_cells(ncell, nthreads, [&](int64_t c0, int64_t c1) {
     for (int64_t c = c0; c < c1; c++) {
-      const float *mw = meanweight ? meanweight + c * ne : M.elem_meannucmass;
-      const float *mf = massfrac + c * ne;
-      nnetot[c] = artis_ib::nnetot(M, mf, mw, rho[c]);
-      int32_t fl = forced[c] ? artis_ib::FORCED_SAHA : 0;
-      const float T_exc = ARTIS_OPT_LTEPOP_EXCITATION_USE_TJ ? TJ[c] : Te[c];
-      float *Uc = U + c * ni;
-      for (int ui = 0; ui < ni; ui++) {
-        const int element = M.ion_element[ui];
-        Uc[ui] = artis_ib::partfunct(M, element, ui - M.elem_uniqueionindexstart[element], ground_cur[c * ni + ui], mf[element], T_exc, &fl);
-      }
-      double *phic = phi + c * ni;
-      const bool force_saha = forced[c] != 0;
-      for (int ui = 0; ui < ni; ui++) {
-        const int element = M.ion_element[ui];
-        const int ion = ui - M.elem_uniqueionindexstart[element];
-        double p = 0.;
-        if (ion < M.elem_nions[element] - 1) {
-          if (artis_ib::use_phi_saha(force_saha)) {
-            p = artis_ib::phi_saha(M, element, ion, Uc[ui], Uc[ui + 1], Te[c]);
-          } else {
-            const int g = gci[(size_t)ui];
-            p = artis_ib::phi_rate_balance(M, alpha_sp.data(), element, ion, Uc[ui], Te[c], clump[c], g >= 0 ? gamma[c * nbfg + g] : 0.);
-          }
-        }
-        phic[ui] = p;
-      }
-      const artis_ib::Cell cell{rho[c], mf, mw, Uc, phic, gamma + c * nbfg, gci.data(), uppermost + c * ne};
-      float *gc = ground + c * ni;
-      int ev = 0;
-      float root = 0.f, n_e = 0.f;
-      if (fl & artis_ib::REFUSED) {
-        for (int i = 0; i < ni; i++) gc[i] = 0.f;
-        for (int e = 0; e < ne; e++) cell.uppermost[e] = -1;
-      } else {
-        n_e = artis_ib::ion_balance_nne(M, cell, force_saha, gc, &root, &ev, &fl);
-        if (fl & artis_ib::REFUSED)
-          for (int i = 0; i < ni; i++) gc[i] = 0.f;
-      }
-      nne[c] = n_e;
-      nne_root[c] = root;
-      evals[c] = ev;
-      flags[c] = fl;
+      artis_ib::cell_setup(M, c, a, Te, nullptr, nullptr, forced[c] != 0, Te_cell.data(), nnetot);
+      for (int ui = 0; ui < M.nions; ui++) artis_ib::partfunct_entry(M, c, ui, TJ, Te_cell.data(), ground_cur, massfrac, U, &flags[c]);
+      for (int ui = 0; ui < M.nions; ui++)
+        artis_ib::phi_entry(M, c, ui, flags[c], U, Te_cell.data(), clump, alpha_sp.data(), gci.data(), gamma, a.nbfg, phi);
+      artis_ib::solve_cell(M, c, a);
     }
   });
 }

@@ -1,8 +1,8 @@
 // radfield_host.cc -- TEST HARNESS ONLY (never shipped, never loaded by the artis_amd package).
 //
-// The per-cell and per-bin functions of artis_amd/csrc/radfield_fit.h compiled for x86 with g++ and applied in plain loops
-// (cells split over a few std::threads) to host copies of the estimators and the cell state: what artis_amd_radfield_fit
-// computes on the device. Also exports the pieces (Planck integrals, mean frequency, TOMS 748 on the bin residual and on a few
+// The per-element bodies of artis_amd/csrc/radfield_fit.h -- the ones the engine's kernels call -- compiled for x86 with g++ and
+// applied in plain loops (cells split over a few std::threads) to host copies of the estimators and the cell state: what
+// artis_amd_radfield_fit computes on the device. Also exports the pieces (Planck integrals, mean frequency, TOMS 748 on the bin residual and on a few
 // analytic functions) for tests/test_radfield_fit_rules.py and tests/golden/make_toms748_golden.py.
 #define ARTIS_HOST_EMU 1
 #include <cmath>
@@ -89,39 +89,27 @@ int rf_host_fit_bin(double J_raw, double nuJ_raw, double J_normfactor, int b, fl
 void rf_host_fit(const artis_radfield_config *cfg, double tmin, int64_t ncell, int nbf, int nline, const artis_cellstate *cs,
                  const artis_estimators *est, float *bf_state, artis_radfield *out, int nthreads) {
   const int nb = rf_host_nbins();
-  std::vector<int64_t> totals((size_t)(ncell * ARTIS_RADFIELD_NCOUNTS), 0);
+  const int32_t lte = cfg->lte_iteration != 0;
+  const CellArrays cell{out->J, out->nuJ, out->J_normfactor, out->TJ, out->TR, out->Te, out->W, out->flags, out->cell_counts};
   auto work = [&](int64_t c0, int64_t c1) {
     for (int64_t c = c0; c < c1; c++) {
       const int32_t thick = cs->thick[c];
-      const CellIn in{est->J[c], est->nuJ[c], cfg->assocvolume_tmin[c], cfg->prev_mid, tmin, cfg->deltat, cfg->nprocs,
-                      cfg->lte_iteration != 0, thick, cs->TJ[c], cs->TR[c], cs->Te[c], cs->W[c]};
-      const CellOut o = fit_cell(in);
-      out->J[c] = o.J;
-      out->nuJ[c] = o.nuJ;
-      out->J_normfactor[c] = o.J_normfactor;
-      out->TJ[c] = o.TJ;
-      out->TR[c] = o.TR;
-      out->Te[c] = o.Te;
-      out->W[c] = o.W;
-      out->flags[c] = o.flags;
-      int32_t *cnt = out->cell_counts + c * ARTIS_RADFIELD_NCOUNTS;
-      for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) cnt[k] = 0;
+      fit_cell_store(c, CellIn{est->J[c], est->nuJ[c], cfg->assocvolume_tmin[c], cfg->prev_mid, tmin, cfg->deltat, cfg->nprocs, lte, thick,
+                               cs->TJ[c], cs->TR[c], cs->Te[c], cs->W[c]},
+                     cell);
+      double estimator_normfactor, over4pi;
+      cell_normfactors(cfg->assocvolume_tmin[c], cfg->prev_mid, tmin, cfg->deltat, cfg->nprocs, &estimator_normfactor, &over4pi);
+      if (cell_bins_carried_over(lte, thick))
+        for (int b = 0; b < nb; b++) carry_bin(c * nb + b, cs->radfieldbin_T_R, cs->radfieldbin_W, out->radfieldbin_T_R, out->radfieldbin_W);
+      if (cell_bf_rewritten(lte, thick))
+        for (int k = 0; k < nbf; k++) bf_entry(c * nbf + k, est->bfrate_raw, estimator_normfactor, bf_state);
+      for (int k = 0; k < nline; k++)
+        line_entry(c * nline + k, est->Jb_lu_raw, est->Jb_lu_contribcount, over4pi, out->Jb_lu_normed, out->Jb_lu_contribcount);
       for (int b = 0; b < nb; b++) {
         const int64_t i = c * nb + b;
-        if (o.flags & ARTIS_RADFIELD_FITTED) {
-          const int bits = fit_bin(est->radfieldbin_J[i], est->radfieldbin_nuJ[i], o.J_normfactor, b, cs->Te[c], &out->radfieldbin_T_R[i],
-                                   &out->radfieldbin_W[i]);
-          for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) cnt[k] += (bits >> k) & 1;
-        } else {
-          out->radfieldbin_T_R[i] = cs->radfieldbin_T_R[i];
-          out->radfieldbin_W[i] = cs->radfieldbin_W[i];
-        }
-      }
-      if (nbf > 0 && !cfg->lte_iteration && thick != ARTIS_CELL_THICK)
-        for (int k = 0; k < nbf; k++) bf_state[c * nbf + k] = bfrate_normed(est->bfrate_raw[c * nbf + k], o.estimator_normfactor);
-      for (int k = 0; k < nline; k++) {
-        out->Jb_lu_normed[c * nline + k] = est->Jb_lu_raw[c * nline + k] * o.J_normfactor;
-        out->Jb_lu_contribcount[c * nline + k] = est->Jb_lu_contribcount[c * nline + k];
+        const int bits = fit_bin_store(i, &est->radfieldbin_J[i], &est->radfieldbin_nuJ[i], out->flags, out->J_normfactor, cs->Te,
+                                       out->radfieldbin_T_R, out->radfieldbin_W);
+        for (int k = 0; k < ARTIS_RADFIELD_NCOUNTS; k++) out->cell_counts[c * ARTIS_RADFIELD_NCOUNTS + k] += (bits >> k) & 1;
       }
     }
   };

@@ -3,15 +3,14 @@ reference's solver (tests/golden/toms748_reference.json), its Planck integrals a
 per-bin rules against a plain-Python restatement of update_grid_cell / set_params_fullspec / fit_parameters, bit for bit, on
 hand-made edge cells."""
 import ctypes as C
-import fcntl
 import json
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 from artis_amd import abi, synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,10 +22,7 @@ T_MIN, T_MAX = 500.0, 250000.0
 
 def lib(preset="nltenebular"):
     if preset not in _LIBS:
-        with open(os.path.join(_HOSTDIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.check_call(["make", "-C", _HOSTDIR], stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(_HOSTDIR, f"libradfield_host_{preset}.so"))
+        L = host_build.load(_HOSTDIR, lambda p: f"libradfield_host_{p}.so", preset)
         d, i, f = C.c_double, C.c_int, C.c_float
         for name, res, args in (("rf_host_partial", d, [d, i]), ("rf_host_planck_integral", d, [d, d, d, i]),
                                 ("rf_host_mean_frequency", d, [d, d, d]), ("rf_host_mean_frequency_tail", d, [d, d, d]),

@@ -1,9 +1,7 @@
 """The per-packet rules of the device spectra (artis_amd/csrc/spectra.h) compiled for x86 (tests/spectra_host) and summed in packet
 order, against the numpy restatements of tools/exspec.py: bit for bit, on oracle-made populations and on hand-made edge packets."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +10,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "tools"))
 import exspec  # noqa: E402
+import host_build  # noqa: E402
 from artis_amd import abi, synth  # noqa: E402
 
 _HOSTDIR = os.path.join(HERE, "spectra_host")
@@ -22,10 +21,7 @@ WIDTH = 0.05
 
 def _lib():
     if not _LIB:
-        with open(os.path.join(_HOSTDIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.check_call(["make", "-C", _HOSTDIR], stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(_HOSTDIR, "libspectra_host.so"))
+        L = host_build.load(_HOSTDIR, lambda p: "libspectra_host.so", "classic")
         L.spec_host_emission_column.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.spec_host_compute.restype = C.c_int64
         L.spec_host_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(abi.SpectraConfig), C.c_double, C.c_double, C.c_int,

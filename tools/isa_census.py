@@ -169,7 +169,7 @@ def main():
                     # action-filter and direction-filter counts, the search, the target decode, the loop's own tests and counters ...)
                     blocks = collections.defaultdict(collections.Counter)
                     for op, f, l in inside:
-                        src = os.path.join(B.CSRC, f) if f in ("physics.h", "tables.h", "artis_engine.hip", "model_build.h") else f
+                        src = os.path.join(B.CSRC, f) if f in B.SOURCES else f
                         blocks[enclosing_function(src, l) if l else "(no line)"][classify(op)] += 1
                     sub.append((name, n + 1, blocks))
                 if os.environ.get("CENSUS_LINES"):  # the body's instructions by source line (to stderr: not part of the table)
