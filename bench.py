@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- packet-steps/sec of the MI355X packet-propagation engine on the synthetic W7-like workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what the headline figure needs: it sets the workload up, warms up, times the K steps, writes the outputs if
+`--dump-outputs` is given and prints the result line. `--full` (off by default) adds what the benchmark measures beside that in
+runs of its own: the CPU baseline (`cpu_baseline`, `gpu_over_cpu_baseline`; `--cpu-sample`, `--cpu-cores`, `--cpu-both` and
+`--no-cpu-baseline` shape that leg and mean nothing without `--full`). The timed steps and every other key of the line are the same
+with and without it.
 
 One "step" = one pass of the hot path over the whole packet population: the reference's update_packets()
 (update_packets.cc:530) for one timestep -- cell-cache population for every non-empty cell, then propagation of
@@ -21,7 +27,8 @@ touches the GPU and exits with the child's code; under torchrun (RANK/WORLD_SIZE
 per artisoptions_*.h: kilonova_lte = BASELINE.json configs[3], nltenebular = configs[4], ...); the headline line is the
 classic build.
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the definitions of roofline and cpu_baseline).
+Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the definitions of roofline and cpu_baseline). Its roofline figures
+take no run of their own (the engine's own events around the timed steps' launches, and committed counters), so every run has them.
 
 `--dump-outputs DIR` writes, after the timed steps, what the last timed step handed its caller: the packets (every field of a
 fixed, seeded sample of them) and the estimators with the event counters, as DIR/<name>.npy (see dump_outputs). The inputs are
@@ -204,7 +211,12 @@ def cpu_baseline(model, cs, ts, pk, sample: int, cores: int, options: str = "cla
     return out
 
 
-def main():
+def cpu_baseline_wanted(args, rank: int, world: int) -> bool:
+    """The CPU leg is a measurement of its own (tens of seconds at the default sample): under --full only, on a single rank."""
+    return bool(args.full) and rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -217,10 +229,13 @@ def main():
     ap.add_argument("--preset", default="w7")
     ap.add_argument("--grid", default="3d", choices=("1d", "2d", "3d"),
                     help="grid geometry (GridType of the reference): 3d = the headline workload; 1d / 2d = --ncoord shells / (r, z) cells")
-    ap.add_argument("--cpu-sample", type=int, default=160_000)
-    ap.add_argument("--cpu-cores", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-both", action="store_true", help="time the CPU port also as the parity checker is compiled (value_checker_flags)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (cpu_baseline, gpu_over_cpu_baseline)")
+    ap.add_argument("--cpu-sample", type=int, default=160_000, help="--full: packets of the CPU baseline's sample")
+    ap.add_argument("--cpu-cores", type=int, default=0, help="--full: processes of the CPU baseline (default: the host's cores, 16 at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline (a plain run has none)")
+    ap.add_argument("--cpu-both", action="store_true",
+                    help="--full: time the CPU port also as the parity checker is compiled (value_checker_flags)")
     ap.add_argument("--options", default="classic", choices=("classic", "kilonova_lte", "nltenebular", "christinenonthermal", "nltephotospheric", "nltewithoutnonthermal",
                                                              "kilonova_expopac", "classic_expopac_therm", "ci_classic_vpkt", "ci_classic_vpkt_expopac"),
                     help="options preset of include/artis_options.h (the reference's artisoptions_*.h; the expansion-opacity builds of "
@@ -230,9 +245,17 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's packets (a seeded sample), estimators and event counters as DIR/<name>.npy "
                          "(rank 0; see dump_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.cpu_both and not args.full:
+        ap.error("--cpu-both times a second CPU leg: it needs --full")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    argv = sys.argv[1:] if argv is None else list(argv)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # start the ranks ourselves: fresh child processes, nothing in this process has touched the GPU
@@ -243,7 +266,7 @@ def main():
             sock.bind(("127.0.0.1", 0))
             port = sock.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
+               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__), *argv]
         raise SystemExit(subprocess.call(cmd))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -265,7 +288,7 @@ def main():
     pk = synth.make_packets(model, aux, args.packets, seed_base=seed_base, kpkt_fraction=0.02, seed=99 + rank)
 
     baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.cpu_sample > 0:
+    if cpu_baseline_wanted(args, rank, world):
         cores = args.cpu_cores or min(os.cpu_count() or 1, 16)
         baseline = cpu_baseline(model, cs, ts, pk, args.cpu_sample, cores, args.options, both=args.cpu_both)  # before any GPU initialisation (fork)
 

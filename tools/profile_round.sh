@@ -2,7 +2,7 @@
 # Everything profiles/<round>/ holds, in one go on the GPU box (outputs under gpurun_out/profile_<round>/):
 #   1. rocprofv3 --kernel-trace --stats of the default bench command           -> kernel_stats / domain_stats
 #   2. the PMC passes (tools/pmc_collect.sh) and their summary                   -> pmc_summary.txt, pmc_traffic.json
-#   3. bench.py with the fresh pmc_traffic.json in place (its roofline.traffic)  -> bench_default.json
+#   3. bench.py --full with the fresh pmc_traffic.json in place (its roofline.traffic, the CPU baseline)  -> bench_default.json
 #   4. the same workload on the other two options builds                         -> bench_kilonova_lte.json, bench_nltenebular.json
 # usage: bash tools/profile_round.sh r02
 T=${1:-r06}
@@ -18,7 +18,7 @@ cd $R && bash tools/pmc_collect.sh 10000000 $T
 cd $R && PMC_TRAFFIC_JSON=$O/pmc_traffic.json python3 tools/pmc_summary.py gpurun_out/pmc_$T/pass* > $O/pmc_summary.txt
 cp $O/pmc_traffic.json $R/profiles/$T/pmc_traffic.json
 rm -rf $R/gpurun_out/pmc_$T
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python3 bench.py --options kilonova_lte --no-cpu-baseline > $O/bench_kilonova_lte.json 2> /dev/null
 bash tools/profile_nltenebular.sh $T
 # round 4: the built paths without a headline of their own, and atomic data of realistic size in one tile
