@@ -20,6 +20,7 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 #include <cmath>
 
@@ -2404,6 +2405,15 @@ void ib_free(IbState *st);
 }  // namespace
 
 // ------------------------------------------------------------------ engine object
+// What one artis_amd_update_packets_device call did: zeroed when the call begins, read by the artis_amd_last_* accessors.
+struct LastCall {
+  double propagate_ms = 0., kms[NEXT_NKINDS] = {}, kms_tail = 0., fill_ms = 0.;  // summed launch durations: all, per kind, the tail kernel's; tile fills'
+  int64_t klaunches[NEXT_NKINDS] = {}, kthreads[NEXT_NKINDS] = {}, nlaunches = 0;
+  // tiled runs: sweeps over the tiles, tile fills (sparse ones, cells filled), packets listed per (sweep, tile), packets parked
+  int64_t sweeps = 0, tile_fills = 0, sparse_fills = 0, cells_filled = 0, listed = 0, parked = 0;
+  int64_t pool_resets = 0;       // times the pool of on-demand records was emptied because it was used up
+  int32_t thermal_variants = 0, est_forms = 0;  // thermal-kernel instantiations launched; how the kernels added to the per-cell estimators (include/artis_amd.h)
+};
 struct artis_amd_engine {
   int device = 0;
   SpecState *spec = nullptr;  // artis_amd_spectra_*: nothing until the first call
@@ -2486,25 +2496,18 @@ struct artis_amd_engine {
   int32_t *d_gamma_n = nullptr;
   int64_t ws_capacity = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-  double last_propagate_ms = 0.;
-  double kms[NEXT_NKINDS] = {};       // summed launch durations per kind of the last update_packets_device call
-  double kms_tail = 0.;               // ... and of the tail kernel
+  LastCall last;  // what the last artis_amd_update_packets_device call did (artis_amd_last_*)
   // (builds with the detailed bound-free estimators -- the nltenebular family -- alternate twice as often between the
   // kernels and their r-packet steps are ~3x as heavy: measured optimum 16384 / 4 / 1024 instead of 4096 / 8 / 2048,
   // nltenebular step 1801 -> 1690 ms, profiles/r03/neb_sweep*.txt)
   int tail_max = ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON ? 16384 : 4096;  // r-packets + thermal packets left at which k_tail takes over (ARTIS_AMD_TAIL; 0 = never)
   bool tail_always = false;           // ... also for a population that starts below it (ARTIS_AMD_TAIL_ALWAYS=1)
-  int64_t klaunches[NEXT_NKINDS] = {};
-  int64_t kthreads[NEXT_NKINDS] = {};
-  int64_t last_nlaunches = 0;
-  // tiled runs: sweeps over the tiles, tile fills and their summed time, packets listed per (sweep, tile) of the last call
   // the cells a fill of a tiled cache works on (make_resident()). Sparse fills: a visit for which few packets wait makes the cells in which they
   // wait (and the cells around those) resident instead of a whole window. ARTIS_AMD_SPARSE_FILL=0: whole windows.
   int32_t *d_fill_cells = nullptr;
   bool sparse_fill = true;
   int64_t sparse_max_listed = 16384;  // ... for visits that list at most this many packets (ARTIS_AMD_SPARSE_MAX; 512 in round 3:
                                       // 4 tiles 3327 / 3205 / 3188 ms at 512 / 4096 / 16384, with parked tails 3222 / 3123 / 2982)
-  int64_t last_sparse_fills = 0, last_cells_filled = 0;
   bool park_tails = true;     // ARTIS_AMD_TILE_PARK=0: every visit of a tile runs its packets to their end (rounds 2-3)
   // ARTIS_AMD_TILE_PARK_AT: packets left of a larger visit at which it parks them (0 / <= tail_max: round 4's rule, at the tail kernel's
   // threshold). Measured on the headline at a quarter of its cache (4 tiles, adaptive windows; profiles/r06/tiling.md): 4096 / 32768 / 131072 /
@@ -2512,9 +2515,7 @@ struct artis_amd_engine {
   // of rows with a quarter of the levels hot): 131072 / 524288 / 2097152 / 3145728 / 4194304 -> 1550 / 1532 / 1504 (1485 on the box of the last two) / 1448 / 1452 ms;
   // three tiles at 11600 MB: 2097152 / 3145728 / 4194304 -> 1590 / 1573 / 1670 ms
   int64_t park_at = 3145728;
-  int64_t last_parked = 0;
-  int64_t last_pool_resets = 0;  // times the pool of on-demand records was emptied because it was used up (this call)
-  int64_t last_pool_used = 0, last_pool_cap = 0;  // units (128 B) of the pool in use at the end of the last call / the pool's size
+  int64_t last_pool_used = 0, last_pool_cap = 0;  // units (128 B) of the pool in use at the end of the last call that had cold levels / its size (no call resets them)
   double ma_hotfrac = 1.;        // the share of every ion's levels that has a static record (given, or chosen by engine_fill from the cache budget)
   bool vpkt_cont_lds = true;  // ARTIS_AMD_VPKT_CONTLDS=0: k_vpkt reads the continuum table from memory (four workgroups of 256 per CU)
   bool tile_zigzag = false;  // ARTIS_AMD_TILE_ZIGZAG=1: sweeps alternate their direction (measured slower: profiles/r03/tiling.md)
@@ -2529,9 +2530,7 @@ struct artis_amd_engine {
   bool pool_keep = true;
   int32_t *d_waiting = nullptr;  // [npts_nonempty + 1] packets waiting per cell; the last entry: packets that need no row
   std::vector<int32_t> h_waiting;
-  int64_t last_visits = 0;
-  int64_t last_sweeps = 0, last_tile_fills = 0, last_listed = 0;
-  double last_fill_ms = 0.;
+  int64_t last_visits = 0;  // visits of the last call that had packets (the driver's own count: adaptive tiles, trace)
   // do_rpkt_step() calls per packet per launch. 8 in rounds 2-3; with the r-packet kernel's reads requested ahead (round 4) the list's order
   // -- sorted by cell and frequency before every launch -- is worth more than the launches saved: 857 / 855 / 851 / 846 / 860 / 881 ms per step
   // at 8 / 6 / 5 / 4 / 3 / 2 (classic; kilonova_lte 859 / 844 / 858 at 8 / 4 / 3; nltenebular, 4 since round 3: 1199 / 1204 / 1235 at 4 / 3 / 2)
@@ -2587,8 +2586,6 @@ struct artis_amd_engine {
   bool thermal_refill = false;  // ARTIS_AMD_REFILL=1: k_thermal_q (walk contexts in per-wave LDS slots, lanes refilled inside the transition loop)
   int tq_low = 48;              // ... its low-water mark of walking lanes (ARTIS_AMD_TQ_LOW)
   bool tq_attr_set = false;     // ... its dynamic-LDS attribute has been set on this engine's device
-  int32_t thermal_variants = 0; // which instantiations of the thermal kernel the last call launched (artis_amd_last_thermal_variants)
-  int32_t est_forms = 0;        // how its kernels added to the per-cell estimators (artis_amd_last_estimator_forms)
   bool ma_tables_lds = true;  // k_thermal<1024, true>: the static target tables in LDS when they fit (ARTIS_AMD_MATABLES_LDS=0: in HBM)
   // the population's scratch: the collisional-excitation cooling terms of `pop_batch` cells at a time (k_matrans writes them,
   // k_cooling_chain turns them into running sums, k_collexc_filter into the records' cooling filters; nothing of it is kept)
@@ -2598,6 +2595,61 @@ struct artis_amd_engine {
   uint32_t *d_visit_counts = nullptr;  // -DARTIS_VISIT_COUNTS builds: [cell][level] transitions drawn per record in the last call
   ncclComm_t comm = nullptr;  // created by artis_amd_comm_init(), owned by the engine
 };
+
+// The ARTIS_AMD_* switches of the fields above (engine_fill). Order: BUDGET before _R / _T, the vpkt builds' tail_max = 0 after TAIL, SORT_CELLSHIFT after SORT_NUMAJOR.
+static void read_switches(artis_amd_engine *e) {
+  if (const char *b = std::getenv("ARTIS_AMD_BUDGET")) {  // tuning / tests: launch budgets never change results
+    e->budget_r = std::max(1, std::atoi(b));
+    e->budget_t = std::max(1, std::atoi(b));
+    e->budget_g = e->budget_r * 8;
+  }
+  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_R")) e->budget_r = std::max(1, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_T")) e->budget_t = std::max(1, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_SMALL_LIST")) e->small_list = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_T_SMALL")) e->budget_t_small = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_R_SMALL")) e->budget_r_small = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_DRAIN_T")) e->drain_t = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_DRAIN_R")) e->drain_r = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_DRAIN_MIN")) e->drain_min_list = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_SLOTSORT")) e->slot_order_by_cell = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_BFDEFER")) e->bf_defer = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_SORT")) e->sort_lists = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_SORT_NU")) e->sort_nu = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_SORT_MA")) e->sort_ma = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TAIL")) e->tail_max = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_TAIL_ALWAYS")) e->tail_always = std::atoi(b) != 0;
+  if (ARTIS_OPT_VPKT_ON) e->tail_max = 0;  // (see the estimator block: the event queue is sized per split launch)
+  if (const char *b = std::getenv("ARTIS_AMD_RPKT_EST_OVER_CONT")) e->rpkt_est_over_cont = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_DENSE_CONTLDS")) e->dense_cont_lds = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_MABINS")) e->ma_bins = (std::atoi(b) > 1) ? SORT_MABINS : 1;
+  if (const char *b = std::getenv("ARTIS_AMD_MAFILTERS")) e->ma_filters = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_DENSE_LPR")) e->dense_lpr = (std::atoi(b) == 64) ? 64 : (std::atoi(b) == 16 ? 16 : 32);
+  if (const char *b = std::getenv("ARTIS_AMD_CELLEST_LDS")) e->cellest_in_lds = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_ESTCACHE")) e->estcache = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_SORT_MAXPC_R")) e->sort_maxpc_r = std::max(1, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_SORT_MAXPC_T")) e->sort_maxpc_t = std::max(1, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_WAVECHUNKS_R")) e->wave_chunks_r = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_WAVECHUNKS_T")) e->wave_chunks_t = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_CUCHUNKS_T")) e->cu_chunks_t = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_CONTLDS")) e->cont_lds = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_LINELDS")) e->line_lds = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TILE_ZIGZAG")) e->tile_zigzag = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TILE_ADAPT")) e->tile_adapt = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TILE_BLOCK")) e->tile_block = std::max<int64_t>(0, std::atoll(b));
+  if (const char *b = std::getenv("ARTIS_AMD_POOL_KEEP")) e->pool_keep = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_MATABLES_LDS")) e->ma_tables_lds = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_REFILL")) e->thermal_refill = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_SORT_NUMAJOR")) e->sort_numajor = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_SORT_CELLSHIFT")) e->sort_cellshift = e->sort_numajor ? std::max(0, std::min(20, std::atoi(b))) : 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TQ_LOW")) e->tq_low = std::max(1, std::min(64, std::atoi(b)));
+  if (const char *b = std::getenv("ARTIS_AMD_SPARSE_FILL")) e->sparse_fill = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_SPARSE_MAX")) e->sparse_max_listed = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_THERMAL_BLOCKS")) e->thermal_blocks_per_cu = std::max(1, std::min(ARTIS_THERMAL_WAVES, std::atoi(b)));
+  e->trace = std::getenv("ARTIS_AMD_TRACE") != nullptr;
+  if (const char *b = std::getenv("ARTIS_AMD_VPKT_CONTLDS")) e->vpkt_cont_lds = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TILE_PARK")) e->park_tails = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TILE_PARK_AT")) e->park_at = std::max<int64_t>(0, std::atoll(b));
+}
 
 namespace {
 
@@ -3218,52 +3270,7 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
   HIP_TRY(hipEventCreate(&e->ev1));
   HIP_TRY(hipEventCreate(&e->ev2));
   HIP_TRY(hipEventCreate(&e->ev3));
-  if (const char *b = std::getenv("ARTIS_AMD_BUDGET")) {  // tuning / tests: launch budgets never change results
-    e->budget_r = std::max(1, std::atoi(b));
-    e->budget_t = std::max(1, std::atoi(b));
-    e->budget_g = e->budget_r * 8;
-  }
-  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_R")) e->budget_r = std::max(1, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_T")) e->budget_t = std::max(1, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_SMALL_LIST")) e->small_list = std::max(0, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_T_SMALL")) e->budget_t_small = std::max(0, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_R_SMALL")) e->budget_r_small = std::max(0, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_DRAIN_T")) e->drain_t = std::max(0, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_DRAIN_R")) e->drain_r = std::max(0, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_DRAIN_MIN")) e->drain_min_list = std::max(0, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_SLOTSORT")) e->slot_order_by_cell = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_BFDEFER")) e->bf_defer = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_SORT")) e->sort_lists = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_SORT_NU")) e->sort_nu = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_SORT_MA")) e->sort_ma = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TAIL")) e->tail_max = std::max(0, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_TAIL_ALWAYS")) e->tail_always = std::atoi(b) != 0;
-  if (ARTIS_OPT_VPKT_ON) e->tail_max = 0;  // (see the estimator block: the event queue is sized per split launch)
-  if (const char *b = std::getenv("ARTIS_AMD_RPKT_EST_OVER_CONT")) e->rpkt_est_over_cont = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_DENSE_CONTLDS")) e->dense_cont_lds = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_MABINS")) e->ma_bins = (std::atoi(b) > 1) ? SORT_MABINS : 1;
-  if (const char *b = std::getenv("ARTIS_AMD_MAFILTERS")) e->ma_filters = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_DENSE_LPR")) e->dense_lpr = (std::atoi(b) == 64) ? 64 : (std::atoi(b) == 16 ? 16 : 32);
-  if (const char *b = std::getenv("ARTIS_AMD_CELLEST_LDS")) e->cellest_in_lds = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_ESTCACHE")) e->estcache = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_SORT_MAXPC_R")) e->sort_maxpc_r = std::max(1, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_SORT_MAXPC_T")) e->sort_maxpc_t = std::max(1, std::atoi(b));
-  if (const char *b = std::getenv("ARTIS_AMD_WAVECHUNKS_R")) e->wave_chunks_r = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_WAVECHUNKS_T")) e->wave_chunks_t = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_CUCHUNKS_T")) e->cu_chunks_t = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_CONTLDS")) e->cont_lds = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_LINELDS")) e->line_lds = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TILE_ZIGZAG")) e->tile_zigzag = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TILE_ADAPT")) e->tile_adapt = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TILE_BLOCK")) e->tile_block = std::max<int64_t>(0, std::atoll(b));
-  if (const char *b = std::getenv("ARTIS_AMD_POOL_KEEP")) e->pool_keep = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_MATABLES_LDS")) e->ma_tables_lds = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_REFILL")) e->thermal_refill = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_SORT_NUMAJOR")) e->sort_numajor = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_SORT_CELLSHIFT")) e->sort_cellshift = e->sort_numajor ? std::max(0, std::min(20, std::atoi(b))) : 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TQ_LOW")) e->tq_low = std::max(1, std::min(64, std::atoi(b)));
-  if (const char *b = std::getenv("ARTIS_AMD_SPARSE_FILL")) e->sparse_fill = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_SPARSE_MAX")) e->sparse_max_listed = std::max(0, std::atoi(b));
+  read_switches(e);
   {
     // the static part of every macro-atom record (tables.h: filter entries that are never counted) is written once
     const int64_t nrows_ = e->tile_cells;  // every resident row; the static parts do not depend on the cell
@@ -3280,14 +3287,9 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
     e->pop_batch = std::max<int64_t>(1, std::min<int64_t>(e->tile_cells, (int64_t)(mb * 1048576.) / per));
     HIP_TRY(hipMalloc((void **)&e->d_collexc_terms, (size_t)(e->pop_batch * per) + 64));
   }
-  if (const char *b = std::getenv("ARTIS_AMD_THERMAL_BLOCKS")) e->thermal_blocks_per_cu = std::max(1, std::min(ARTIS_THERMAL_WAVES, std::atoi(b)));
-  e->trace = std::getenv("ARTIS_AMD_TRACE") != nullptr;
   if (e->trace)
     fprintf(stderr, "[artis_amd] record tiers: static records for %.2f of every ion's levels, %d cold levels, pool of %d slots per resident cell; %d tile(s) of %lld cells, %zu B per cell\n",
             e->ma_hotfrac, e->Mh.ncold, e->Mh.ma_pool_slots, e->ntiles, (long long)e->tile_cells, e->cache_bytes_per_cell);
-  if (const char *b = std::getenv("ARTIS_AMD_VPKT_CONTLDS")) e->vpkt_cont_lds = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TILE_PARK")) e->park_tails = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TILE_PARK_AT")) e->park_at = std::max<int64_t>(0, std::atoll(b));
   return ARTIS_OK;
 }
 }  // namespace
@@ -3754,507 +3756,6 @@ int artis_amd_packets_restore(artis_amd_engine *e) {
   return ARTIS_OK;
 }
 
-namespace {
-// counting sort of list[0..n) by its entries' keys into e->d_sorted; *out = the list to launch on
-// max_per_cell: a list with more entries per cell than this stays in the order it was appended in. A cell-sorted list puts
-// every lane that is running on an XCD into the same few cells when the cells are few and full, and their estimator
-// atomics then hit the same few addresses at the same time (device-wide atomics on one address are serialised in memory:
-// 20^3 cells, 1e7 packets: k_thermal 907 ms sorted, 725 ms unsorted), while the locality the sort buys matters less
-// because fewer cells' tables compete for the caches. Models with so few cells that the kernels accumulate their per-cell
-// estimators in LDS (Env::cellest_lds) have no such atomics and are always sorted (6^3 cells: 494 ms sorted, 593 unsorted).
-int sort_by_key(artis_amd_engine *e, hipStream_t s, const int32_t *list, const int32_t *keys, int32_t n, const int32_t **out, int nbins,
-                int64_t ncells, int max_per_cell, int32_t nkeys_given = 0) {
-  *out = list;
-  if (!e->sort_lists || n < 2 * BLOCK) return ARTIS_OK;
-  if ((int64_t)n > (int64_t)max_per_cell * (ncells > 0 ? ncells : 1)) return ARTIS_OK;
-  const int32_t nkeys = nkeys_given > 0 ? nkeys_given : e->Mh.ngrid * nbins;
-  HIP_TRY(hipMemsetAsync(e->d_hist, 0, sizeof(int32_t) * (size_t)(nkeys + 1), s));
-  if (nkeys <= SORT_LDS_KEYS)
-    hipLaunchKernelGGL(k_sort_hist_lds, dim3(sort_lds_grid(n)), dim3(BLOCK), 0, s, keys, n, e->d_hist, nkeys);
-  else
-    hipLaunchKernelGGL(k_sort_hist, dim3(nblocks(n)), dim3(BLOCK), 0, s, keys, n, e->d_hist);
-  const int ntiles = (nkeys + SCAN_TILE - 1) / SCAN_TILE;
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nkeys, e->d_tiles);
-  hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, s, e->d_tiles, ntiles);
-  hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nkeys, e->d_tiles);
-  if (nkeys <= SORT_LDS_KEYS)
-    hipLaunchKernelGGL(k_sort_scatter_lds, dim3(sort_lds_grid(n)), dim3(BLOCK), 0, s, list, keys, n, e->d_hist, e->d_sorted, nkeys);
-  else
-    hipLaunchKernelGGL(k_sort_scatter, dim3(nblocks(n)), dim3(BLOCK), 0, s, list, keys, n, e->d_hist, e->d_sorted);
-  *out = e->d_sorted;
-  return ARTIS_OK;
-}
-}  // namespace
-
-#if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
-// the estimator updates the propagation launch before it recorded (the cells' cache rows are still resident)
-static int launch_bfest_dense(artis_amd_engine *e, const Env &env, hipStream_t s) {
-  const bool lds = e->dense_cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX;
-  e->est_forms |= (lds ? ARTIS_AMD_EST_BF_DENSE_CONTLDS : ARTIS_AMD_EST_BF_DENSE_HBM) |
-                  (e->dense_lpr == 64 ? ARTIS_AMD_EST_BF_LPR64 : (e->dense_lpr == 16 ? ARTIS_AMD_EST_BF_LPR16 : ARTIS_AMD_EST_BF_LPR32));
-#define DENSE_LAUNCH(LPR)                                                                                        \
-  if (lds)                                                                                                       \
-    hipLaunchKernelGGL((k_bfest_dense<true, DENSE_TB, LPR>), dim3(e->ncu * ARTIS_DENSE_WGS), dim3(DENSE_TB), 0, s, env); \
-  else                                                                                                           \
-    hipLaunchKernelGGL((k_bfest_dense<false, BLOCK, LPR>), dim3(e->ncu * 8), dim3(BLOCK), 0, s, env);
-  if (e->dense_lpr == 64) {
-    DENSE_LAUNCH(64)
-  } else if (e->dense_lpr == 16) {
-    DENSE_LAUNCH(16)
-  } else {
-    DENSE_LAUNCH(32)
-  }
-#undef DENSE_LAUNCH
-  return ARTIS_OK;
-}
-#endif
-
-int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_stream) {
-  if (!e || !e->have_cells || !e->d_pkt) {
-    g_last_error = "engine needs artis_amd_set_cellstate() and resident packets first";
-    return ARTIS_ERR_ARG;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  e->fit_since_step = false;
-  hipStream_t s = (hipStream_t)hip_stream;
-  e->last_propagate_ms = 0.;
-  e->last_nlaunches = 0;
-  e->last_sweeps = e->last_tile_fills = e->last_listed = 0;
-  e->last_sparse_fills = e->last_cells_filled = 0;
-  e->last_parked = 0;
-  e->last_pool_resets = 0;
-  e->thermal_variants = 0;
-  e->est_forms = 0;
-  e->last_fill_ms = 0.;
-  for (int k = 0; k < NEXT_NKINDS; k++) {
-    e->kms[k] = 0.;
-    e->kms_tail = 0.;
-    e->klaunches[k] = 0;
-    e->kthreads[k] = 0;
-  }
-  const int64_t n = e->npackets;
-  if (n == 0) return ARTIS_OK;
-#ifdef ARTIS_VISIT_COUNTS
-  {
-    const size_t vb = sizeof(uint32_t) * (size_t)e->Mh.npts_nonempty * (size_t)e->Mh.nlevels;
-    if (e->d_visit_counts == nullptr) HIP_TRY(hipMalloc((void **)&e->d_visit_counts, vb));
-    HIP_TRY(hipMemsetAsync(e->d_visit_counts, 0, vb, s));
-  }
-#endif
-  Env env = make_env(e);
-  if (e->d_bfrate_kept != nullptr) {
-    if (e->bfrate_kept_dirty)
-      HIP_TRY(hipMemsetAsync(e->d_bfrate_kept, 0, sizeof(double) * (size_t)e->Mh.npts_nonempty * (size_t)e->Mh.nbfcontinua, s));
-    e->bfrate_kept_dirty = true;
-  }
-  int cur[NEXT_NKINDS] = {};             // which of the two buffers is the current list of each kind
-  const int r_nubins = e->sort_nu ? SORT_NUBINS : 1;  // frequency bins in the keys of the r-packet list
-  // cell groups of the frequency-major keys: the ONE number both the keys (Lists::numajor) and the sort's key count are made of
-  const int32_t r_ngroups = (e->sort_cellshift > 0) ? ((e->Mh.ngrid >> e->sort_cellshift) + 1) : e->Mh.ngrid;
-  int32_t cnt[2 * NEXT_NKINDS];                        // host copy of the device counters
-  bool pool_reset_due = false;
-  auto lists_for = [&](int self_kind) {
-    Lists L;
-    for (int k = 0; k < NEXT_NKINDS; k++) {
-      L.lst[k] = e->d_lists[k][cur[k]];
-      L.key[k] = e->d_keys[k][cur[k]];
-    }
-    L.counts = e->d_count;
-    L.self_kind = self_kind;
-    L.self_list = self_kind > 0 ? e->d_lists[self_kind][1 - cur[self_kind]] : nullptr;
-    L.self_key = self_kind > 0 ? e->d_keys[self_kind][1 - cur[self_kind]] : nullptr;
-    L.self_count = e->d_count + NEXT_NKINDS;  // one alternate counter: only one kernel runs at a time
-    L.kpkt_slot = NEXT_MA;  // k-packets travel in the thermal list
-    L.nubins = r_nubins;
-    L.numajor = e->sort_numajor ? r_ngroups : 0;
-    L.cellshift = e->sort_cellshift;
-    L.mabins = e->ma_bins;
-    return L;
-  };
-  int32_t errflag = 0;
-  // (ARTIS_AMD_TRACE: where the host's time of the call goes -- waiting for the stream, submitting sorts, submitting launches)
-  using clk = std::chrono::steady_clock;
-  double wall_sync = 0., wall_sort = 0., wall_launch = 0.;
-  const clk::time_point wall_t0 = clk::now();
-  auto since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
-  auto read_counts = [&]() -> int {
-    // (one copy into pinned memory: counters and error flag are neighbours. Two copies into the stack -- pageable, staged by the runtime -- were a
-    // measurable share of the ~90 ms a headline step spends outside its kernels)
-    const clk::time_point t_sync = clk::now();
-    HIP_TRY(hipMemcpyAsync(e->h_counts, e->d_count, sizeof(int32_t) * (2 * NEXT_NKINDS + 1), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    wall_sync += since(t_sync);
-    std::memcpy(cnt, e->h_counts, sizeof(int32_t) * 2 * NEXT_NKINDS);
-    errflag = e->h_counts[2 * NEXT_NKINDS];
-    HIP_TRY(hipGetLastError());
-    if (errflag != 0) {
-      g_last_error = "a kernel raised error flag " + std::to_string(errflag) + " (an assert_always of the reference would have fired)";
-      if (errflag == 46) g_last_error = "the pool of on-demand macro-atom records cannot hold a single record of this atomic data (error flag 46): raise ARTIS_AMD_MA_POOLFRAC (or ARTIS_AMD_MA_HOTFRAC)";
-      (void)hipMemsetAsync(e->d_err, 0, sizeof(int32_t), s);
-      return ARTIS_ERR_NOTCONVERGED;
-    }
-    if (cnt[2 * NEXT_NKINDS - 1] != 0) {  // a lane found the pool of on-demand records used up (Env::ma_pool_full)
-      pool_reset_due = true;
-      HIP_TRY(hipMemsetAsync(e->d_count + (2 * NEXT_NKINDS - 1), 0, sizeof(int32_t), s));
-    }
-    return ARTIS_OK;
-  };
-  // The pool of on-demand records used up: the packets that wait for a record sit on the slow-path list (PEND_MA_FILL). Before that list's next
-  // launch -- after the thermal kernel has walked on with the records the last one filled -- the pool is emptied: every cold level of the resident
-  // cells is without a record again and is filled when next needed, exactly as after a tile's refill. Costs fills, never an answer.
-  auto reset_pool_if_due = [&](const Env &env_now) -> int {
-    if (!pool_reset_due || e->Mh.ncold <= 0) return ARTIS_OK;
-    pool_reset_due = false;
-    (void)env_now;
-    HIP_TRY(hipMemsetAsync(e->K.ma_rowtab, 0xFF, sizeof(int32_t) * (size_t)(e->tile_cells * (int64_t)e->Mh.ncold), s));  // (every row: k_ma_reset)
-    HIP_TRY(hipMemsetAsync(e->K.ma_pool_used, 0, sizeof(uint32_t), s));
-    e->last_pool_resets++;
-    if (e->trace) fprintf(stderr, "[artis_amd] the pool of on-demand records was used up: emptied (%lld)\n", (long long)e->last_pool_resets);
-    return ARTIS_OK;
-  };
-  // the launches of the two propagation kernels (on a given stream, with a given set of chunk cursors): one after the other on the call's stream,
-  // or side by side on two streams where both lists are short ("duet", below)
-  auto launch_rpkt = [&](hipStream_t st, const int32_t *lst, int32_t nk, const Lists &next, int32_t *cursors) -> int {
-        const int grid = (int)std::min<int64_t>(((int64_t)nk + ARTIS_RPKT_TB - 1) / ARTIS_RPKT_TB, (int64_t)e->ncu * ARTIS_RPKT_WGS);  // persistent: every block resident
-        const int bud_r = (e->budget_r_small > 0 && nk < e->small_list) ? std::min(e->budget_r_small, e->budget_r) : e->budget_r;
-        const int nch = e->wave_chunks_r ? chunks_for(nk, grid * (ARTIS_RPKT_TB / 64)) : 8;
-        const bool rpkt_line_lds = e->line_lds && e->Mh.nlines <= LINE_LDS_MAX && e->Mh.nlines > 0 && !(env.cellest_n_r > RPKT_CELLEST_CAP);
-        const bool rpkt_cont_lds = !rpkt_line_lds && e->cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX && e->Mh.nbfcontinua > 0 &&
-                                   !(env.cellest_n_r > RPKT_CELLEST_CAP);
-        // (the kernel's own choice, k_rpkt: the workgroup's array for cellest_n_r > 0, else the waves' caches except in the LINE_LDS form)
-        e->est_forms |= env.cellest_n_r > 0 ? (rpkt_line_lds ? ARTIS_AMD_EST_RPKT_LDS_LINE
-                                                             : (rpkt_cont_lds ? ARTIS_AMD_EST_RPKT_LDS_CONT : ARTIS_AMD_EST_RPKT_LDS_NOCONT))
-                                            : ((!rpkt_line_lds && env.estcache_on) ? ARTIS_AMD_EST_RPKT_WAVECACHE : ARTIS_AMD_EST_RPKT_GLOBAL);
-        if (rpkt_line_lds)
-          hipLaunchKernelGGL((k_rpkt<false, ARTIS_RPKT_TB, true>), dim3(grid), dim3(ARTIS_RPKT_TB), 0, st, env, lst, nk, next, e->d_stats, bud_r, cursors, nch,
-                             (e->drain_r > 0 && nk >= e->drain_min_list) ? e->drain_r : bud_r);
-        else if (rpkt_cont_lds)
-          hipLaunchKernelGGL((k_rpkt<true, ARTIS_RPKT_TB>), dim3(grid), dim3(ARTIS_RPKT_TB), 0, st, env, lst, nk, next, e->d_stats, bud_r, cursors, nch,
-                             (e->drain_r > 0 && nk >= e->drain_min_list) ? e->drain_r : bud_r);
-        else
-          hipLaunchKernelGGL((k_rpkt<false, ARTIS_RPKT_TB>), dim3(grid), dim3(ARTIS_RPKT_TB), 0, st, env, lst, nk, next, e->d_stats, bud_r, cursors, nch,
-                             (e->drain_r > 0 && nk >= e->drain_min_list) ? e->drain_r : bud_r);
-#if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
-        if (env.bfev == nullptr) e->est_forms |= ARTIS_AMD_EST_BF_INPLACE;
-        if (env.bfev != nullptr) {  // the estimator updates the launch recorded (the cells' cache rows are still resident)
-          {
-            const int rcd = launch_bfest_dense(e, env, st);
-            if (rcd != ARTIS_OK) return rcd;
-          }
-          HIP_TRY(hipMemsetAsync(e->d_bfev_count, 0, sizeof(int32_t), st));
-        }
-#endif
-    return ARTIS_OK;
-  };
-  auto launch_thermal = [&](hipStream_t st, const int32_t *lst, int32_t nk, const Lists &next, int32_t *cursors) -> int {
-        // persistent: every workgroup resident (ARTIS_THERMAL_WAVES waves per SIMD)
-        {
-          const int grid = (int)std::min<int64_t>(((int64_t)nk + ARTIS_THERMAL_TB - 1) / ARTIS_THERMAL_TB,
-                                                  (int64_t)e->ncu * std::min(e->thermal_blocks_per_cu, ARTIS_THERMAL_WGS));
-          const bool per_cu = e->cu_chunks_t && nk >= 256 * 1024;
-          // (drain: only where the next thermal launch will be large too, so that what is handed on runs beside a full list)
-          const int bud_t = (e->budget_t_small > 0 && nk < e->small_list) ? std::min(e->budget_t_small, e->budget_t) : e->budget_t;
-          const int drain = (e->drain_t > 0 && nk >= e->drain_min_list) ? e->drain_t : bud_t;
-          const size_t tq_bytes = tq_lds_bytes(TQ_TB, e->Mh.nlevels, e->Mh.nalltrans);
-          const bool cold = e->Mh.ncold > 0;  // (kernels built with the on-demand records' look-ups only where the model has cold levels)
-          // the COLD = false / true instantiation of a thermal kernel (K<A, B, COLD>)
-#define LAUNCH_T2(K, A, B, GRID, TBS, LDSB, ...)                                                                   \
-  do {                                                                                                             \
-    if (cold)                                                                                                      \
-      hipLaunchKernelGGL((K<A, B, true>), dim3(GRID), dim3(TBS), LDSB, st, __VA_ARGS__);                            \
-    else                                                                                                           \
-      hipLaunchKernelGGL((K<A, B, false>), dim3(GRID), dim3(TBS), LDSB, st, __VA_ARGS__);                           \
-  } while (0)
-          if (cold) e->thermal_variants |= ARTIS_AMD_THERMAL_COLD;
-          if (e->thermal_refill && ARTIS_THERMAL_SPLIT_EXACT && env.cellest_n_t == 0 && tq_bytes <= 160 * 1024 - 1024 && nk >= 4096 && e->Mh.nlevels < 32768) {
-            e->thermal_variants |= ARTIS_AMD_THERMAL_REFILL;
-            e->est_forms |= ARTIS_AMD_EST_THERMAL_GLOBAL;  // (k_thermal_q keeps no per-cell sums in LDS)
-            if (!e->tq_attr_set) {  // (per engine, i.e. per device: the attribute is the device'st, not the process's -- ADVICE r05)
-              HIP_TRY(hipFuncSetAttribute((const void *)k_thermal_q<TQ_TB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-              HIP_TRY(hipFuncSetAttribute((const void *)k_thermal_q<TQ_TB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-              e->tq_attr_set = true;
-            }
-            const int grid1 = (int)std::min<int64_t>(((int64_t)nk + TQ_TB - 1) / TQ_TB, (int64_t)e->ncu);
-            if (cold)
-              hipLaunchKernelGGL((k_thermal_q<TQ_TB, true>), dim3(grid1), dim3(TQ_TB), tq_bytes, st, env, lst, nk, next, e->d_stats, bud_t, cursors,
-                                 e->wave_chunks_t ? chunks_for(nk, grid1 * (TQ_TB / 64)) : 8, drain, e->tq_low);
-            else
-              hipLaunchKernelGGL((k_thermal_q<TQ_TB, false>), dim3(grid1), dim3(TQ_TB), tq_bytes, st, env, lst, nk, next, e->d_stats, bud_t, cursors,
-                                 e->wave_chunks_t ? chunks_for(nk, grid1 * (TQ_TB / 64)) : 8, drain, e->tq_low);
-          } else if (e->ma_tables_lds && e->Mh.nlevels <= MA_LDS_LEVELS && e->Mh.nalltrans <= MA_LDS_TRANS && nk >= 4096) {
-            const int grid1 = (int)std::min<int64_t>(((int64_t)nk + 1023) / 1024, (int64_t)e->ncu);
-            e->thermal_variants |= ARTIS_AMD_THERMAL_LDS_TABLES;
-            e->est_forms |= thermal_est_form(env, 1);
-            LAUNCH_T2(k_thermal, 1024, 1, grid1, 1024, 0, env, lst, nk, next, e->d_stats, bud_t, cursors, e->wave_chunks_t ? chunks_for(nk, grid1 * 16) : 8, 0, drain);
-          } else if (e->ma_tables_lds && e->Mh.nlevels <= MA_LDS_LEVELS2 && nk >= 4096 && env.cellest_n_t == 0) {
-            const int grid1 = (int)std::min<int64_t>(((int64_t)nk + 1023) / 1024, (int64_t)e->ncu);
-            e->thermal_variants |= ARTIS_AMD_THERMAL_LDS_LEVELPACK;
-            e->est_forms |= thermal_est_form(env, 2);
-            LAUNCH_T2(k_thermal, 1024, 2, grid1, 1024, 0, env, lst, nk, next, e->d_stats, bud_t, cursors, e->wave_chunks_t ? chunks_for(nk, grid1 * 16) : 8, 0, drain);
-          } else {
-            e->thermal_variants |= ARTIS_AMD_THERMAL_PLAIN;
-            e->est_forms |= thermal_est_form(env, 0);
-            LAUNCH_T2(k_thermal, ARTIS_THERMAL_TB, 0, grid, ARTIS_THERMAL_TB, 0, env, lst, nk, next, e->d_stats, bud_t, cursors,
-                      per_cu ? 256 : (e->wave_chunks_t ? chunks_for(nk, grid * (ARTIS_THERMAL_TB / 64)) : 8), per_cu ? 2 : 0, drain);
-          }
-#undef LAUNCH_T2
-        }
-    return ARTIS_OK;
-  };
-  int rc = ARTIS_OK;
-  const int order[6] = {NEXT_SLOW, NEXT_GAMMA, NEXT_BB, NEXT_KPKT, NEXT_MA, NEXT_RPKT};
-  int64_t guard = 0;
-  const int64_t ncell_all = e->Mh.npts_nonempty;
-  bool first_pass = true;
-  // Sweeps over the cell-cache tiles (one tile, one sweep when the whole cache is resident): list the packets that sit
-  // in the tile, fill the tile's cache if any do, advance them until they leave the tile or are done; repeat until a
-  // sweep finds no packet left to advance.
-  const bool adaptive = e->tile_adapt && e->ntiles > 1;
-  bool all_done = false;
-  std::vector<int32_t> want;
-  if (e->ntiles > 1 && e->d_waiting == nullptr) {
-    HIP_TRY(hipMalloc((void **)&e->d_waiting, sizeof(int32_t) * (size_t)(ncell_all + 1)));
-    e->h_waiting.assign((size_t)ncell_all + 1, 0);
-  }
-  e->last_visits = 0;
-  for (int sweep = 0;; sweep++) {
-  bool any_active = false;
-  for (int tstep = 0; tstep < e->ntiles; tstep++) {
-  // sweeps alternate their direction: a packet that left its tile against the direction of one sweep is met by the next
-  // one on its way back (with one direction it waits a whole sweep per backward crossing)
-  const int tile = (e->tile_zigzag && (sweep & 1)) ? e->ntiles - 1 - tstep : tstep;
-  if (e->ntiles > 1) {
-    // where do the packets wait? The cells in which most of them do are made resident (choose_cells(): a window or a set of blocks of cells, or -- few
-    // packets -- the very cells); cells that are resident already keep their rows, the others are filled
-    env = make_env(e);
-    HIP_TRY(hipMemsetAsync(e->d_waiting, 0, sizeof(int32_t) * (size_t)(ncell_all + 1), s));
-    hipLaunchKernelGGL(k_count_waiting, dim3(nblocks(n)), dim3(BLOCK), 0, s, env, e->d_waiting, e->d_waiting + ncell_all);
-    HIP_TRY(hipMemcpyAsync(e->h_waiting.data(), e->d_waiting, sizeof(int32_t) * (size_t)(ncell_all + 1), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    int64_t total = 0;
-    for (int64_t c = 0; c < ncell_all; c++) total += e->h_waiting[(size_t)c];
-    if (total == 0 && e->h_waiting[(size_t)ncell_all] == 0) {  // nothing left anywhere
-      all_done = true;
-      break;
-    }
-    int64_t holds = 0, nfilled = 0;
-    bool sparse = false;
-    choose_cells(e, e->h_waiting, want, &holds, &sparse, adaptive ? -1 : (int64_t)tile * e->tile_cells);
-    if (holds == 0) want.clear();  // (no packet waits for a row of these cells: the visit is for the packets that need none, if any)
-    if (e->trace)
-      fprintf(stderr, "[artis_amd] visit %lld: %lld packets wait in cells, %d need no row; %zu cells chosen%s hold %lld\n", (long long)e->last_visits,
-              (long long)total, e->h_waiting[(size_t)ncell_all], want.size(), sparse ? " (sparse)" : "", (long long)holds);
-    HIP_TRY(hipEventRecord(e->ev2, s));
-    rc = make_resident(e, want, s, &nfilled);
-    if (rc != ARTIS_OK) return rc;
-    if (nfilled > 0) {
-      HIP_TRY(hipEventRecord(e->ev3, s));
-      HIP_TRY(hipEventSynchronize(e->ev3));
-      float fms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&fms, e->ev2, e->ev3));
-      e->last_fill_ms += fms;
-      e->last_tile_fills++;
-      e->last_cells_filled += nfilled;
-      if (sparse) e->last_sparse_fills++;
-    }
-  } else if (e->tile_valid_lo != 0) {
-    rc = populate_tile(e, s);
-    if (rc != ARTIS_OK) return rc;
-  }
-  env = make_env(e);
-  for (int k = 0; k < NEXT_NKINDS; k++) cur[k] = 0;
-  HIP_TRY(hipMemsetAsync(e->d_count, 0, sizeof(int32_t) * 2 * NEXT_NKINDS, s));
-  hipLaunchKernelGGL(k_classify, dim3(nblocks(n)), dim3(BLOCK), 0, s, env, lists_for(0), first_pass ? 1 : 0);
-  first_pass = false;
-  rc = read_counts();
-  if (rc != ARTIS_OK) return rc;
-  bool tile_active = false;
-  for (int k = 1; k < NEXT_NKINDS; k++) tile_active = tile_active || cnt[k] > 0;
-  if (!tile_active) continue;
-  any_active = true;
-  e->last_visits++;
-  for (int k = 1; k < NEXT_NKINDS; k++) e->last_listed += cnt[k];
-  if (e->trace) fprintf(stderr, "[artis_amd] sweep %d tile %d of %d\n", sweep, tile, e->ntiles);
-
-  // one launch = the whole current list of one kind. Order: slow path, k-packets, macro-atoms, r-packets, so that a
-  // k-packet -> macro-atom -> k-packet cycle costs two launches.
-  // the tail kernel takes the end of a population that began larger (a population that begins below the threshold runs on
-  // the split kernels throughout, unless ARTIS_AMD_TAIL_ALWAYS=1)
-  int64_t listed = 0;
-  for (int k = 1; k < NEXT_NKINDS; k++) listed += cnt[k];
-  // (tiled runs: the later sweeps bring a tile a few stragglers at a time; each such visit is a tail from its first launch)
-  const bool tail_ok = e->tail_max > 0 && (e->tail_always || listed > e->tail_max || sweep > 0 || (adaptive && e->last_visits > e->ntiles));
-  int64_t visit_launches = 0;  // split-kernel launches of this visit (a visit parks its tail only after it has advanced its packets)
-  while (cnt[NEXT_RPKT] > 0 || cnt[NEXT_MA] > 0 || cnt[NEXT_SLOW] > 0 || cnt[NEXT_KPKT] > 0 || cnt[NEXT_GAMMA] > 0 || cnt[NEXT_BB] > 0) {
-    const int tail_kinds[4] = {NEXT_RPKT, NEXT_MA, NEXT_SLOW, NEXT_BB};
-    int64_t tail_n = 0;
-    for (int k : tail_kinds) tail_n += cnt[k];
-    // (round 6) tiled run: a visit that began larger parks what is left of it once that has fallen to park_at packets -- BEFORE the long run
-    // of small, latency-bound launches that its last packets would otherwise cost every visit: they wait in their cells and are listed
-    // again, merged with the other windows' stragglers, by a later visit (a visit that BEGINS with that few runs them to their end)
-    if (e->park_tails && e->ntiles > 1 && e->park_at > e->tail_max && listed > e->park_at && visit_launches > 0 && tail_n > 0 &&
-        tail_n + cnt[NEXT_KPKT] <= e->park_at) {
-      e->last_parked += tail_n + cnt[NEXT_KPKT] + cnt[NEXT_GAMMA];
-      if (e->trace) fprintf(stderr, "[artis_amd] sweep %d tile %d: %lld packets parked (park_at)\n", sweep, tile, (long long)(tail_n + cnt[NEXT_KPKT]));
-      break;
-    }
-    if (tail_ok && tail_n > 0 && tail_n <= e->tail_max && cnt[NEXT_KPKT] == 0) {
-      if (e->park_tails && e->ntiles > 1 && listed > e->tail_max && visit_launches > 0) {
-        // tiled run, a visit that began larger: its last packets wait in the tile (their state is in the packet store; the next
-        // classify pass lists them again) and run with the packets that return to it in the next sweep, instead of one long
-        // k_tail launch per visit. A visit that BEGINS with a tail's worth of packets runs them to their end (below): no
-        // packet waits more than once without the tile's population having shrunk to that.
-        e->last_parked += tail_n + cnt[NEXT_GAMMA];
-        if (e->trace) fprintf(stderr, "[artis_amd] sweep %d tile %d: %lld packets parked\n", sweep, tile, (long long)tail_n);
-        break;
-      }
-      // the last packets of these kinds: one launch carries each through all its remaining alternations (k_tail)
-      const int32_t nr = (int32_t)tail_n, nt = 0;
-      // the four current lists are consumed whole, and no packet comes back to them -- but for one case: a packet that waits for a record of a
-      // pool that is used up leaves for the slow-path list (k_tail "waits"). That entry must not land in a buffer other waves still read their
-      // packets from: the slow-path kind is the launch's own kind, its entries go to the ALTERNATE slow-path list, which becomes the current one.
-      const Lists next = lists_for(NEXT_SLOW);
-      TailLists in;
-      for (int i = 0; i < 4; i++) {
-        in.list[i] = e->d_lists[tail_kinds[i]][cur[tail_kinds[i]]];
-        in.n[i] = cnt[tail_kinds[i]];
-        HIP_TRY(hipMemsetAsync(e->d_count + tail_kinds[i], 0, sizeof(int32_t), s));
-      }
-      HIP_TRY(hipMemsetAsync(e->d_count + NEXT_NKINDS, 0, sizeof(int32_t), s));
-      rc = reset_pool_if_due(env);
-      if (rc != ARTIS_OK) return rc;
-      HIP_TRY(hipEventRecord(e->ev0, s));
-      e->thermal_variants |= ARTIS_AMD_THERMAL_TAIL;
-      hipLaunchKernelGGL(k_tail, dim3(nblocks(tail_n * 64)), dim3(BLOCK), 0, s, env, in, next, e->d_stats);
-#if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
-      if (env.bfev != nullptr) {
-        rc = launch_bfest_dense(e, env, s);
-        if (rc != ARTIS_OK) return rc;
-        HIP_TRY(hipMemsetAsync(e->d_bfev_count, 0, sizeof(int32_t), s));
-      }
-#endif
-      HIP_TRY(hipEventRecord(e->ev1, s));
-      rc = read_counts();
-      if (rc != ARTIS_OK) return rc;
-      // (the alternate slow-path list becomes the current one, as after a launch of the slow-path kernel)
-      cur[NEXT_SLOW] = 1 - cur[NEXT_SLOW];
-      cnt[NEXT_SLOW] = cnt[NEXT_NKINDS];
-      HIP_TRY(hipMemcpyAsync(e->d_count + NEXT_SLOW, e->d_count + NEXT_NKINDS, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-      e->kms_tail += ms;
-      e->last_nlaunches++;
-      if (e->trace)
-        fprintf(stderr, "[artis_amd] launch %lld tail n=%d+%d %.3f ms -> r %d ma %d slow %d gamma %d bb %d\n", (long long)e->last_nlaunches, nr, nt,
-                ms, cnt[NEXT_RPKT], cnt[NEXT_MA], cnt[NEXT_SLOW], cnt[NEXT_GAMMA], cnt[NEXT_BB]);
-      if (++guard > 2000000LL) {
-        g_last_error = "packet loop did not terminate";
-        return ARTIS_ERR_NOTCONVERGED;
-      }
-      continue;
-    }
-    for (int kind : order) {
-      const int32_t nk = cnt[kind];
-      if (nk <= 0) continue;
-      const Lists next = lists_for(kind);
-      const int32_t *lst = e->d_lists[kind][cur[kind]];
-      const clk::time_point t_sort = clk::now();
-      if (kind == NEXT_RPKT || kind == NEXT_GAMMA || (kind == NEXT_MA && e->sort_ma)) {
-        rc = sort_by_key(e, s, e->d_lists[kind][cur[kind]], e->d_keys[kind][cur[kind]], nk, &lst, kind == NEXT_RPKT ? r_nubins : (kind == NEXT_MA ? e->ma_bins : 1),
-                         e->tile_cells, kind == NEXT_MA ? (env.cellest_n_t > 0 ? INT32_MAX : e->sort_maxpc_t)
-                                                  : (env.cellest_n_r > 0 ? INT32_MAX : e->sort_maxpc_r),
-                         (kind == NEXT_RPKT && r_nubins > 1 && e->sort_numajor) ? r_ngroups * r_nubins : 0);
-        if (rc != ARTIS_OK) return rc;
-      }
-      wall_sort += since(t_sort);
-      const clk::time_point t_launch = clk::now();
-      if (kind == NEXT_SLOW) {
-        rc = reset_pool_if_due(env);
-        if (rc != ARTIS_OK) return rc;
-      }
-      // the kernel starts with an empty current list of its own kind: everything it keeps goes to the alternate list
-      hipLaunchKernelGGL(k_launch_reset, dim3(1), dim3(BLOCK), 0, s, e->d_count, kind, e->d_cursors);  // (one command instead of three memsets)
-      HIP_TRY(hipEventRecord(e->ev0, s));
-      if (kind == NEXT_RPKT) {
-        rc = launch_rpkt(s, lst, nk, next, e->d_cursors);
-        if (rc != ARTIS_OK) return rc;
-      } else if (kind == NEXT_GAMMA) {
-        const int grid = std::min(nblocks(nk), e->ncu * ARTIS_GAMMA_WAVES);
-        e->est_forms |= env.cellest_n_g > 0 ? ARTIS_AMD_EST_GAMMA_LDS : ARTIS_AMD_EST_GAMMA_GLOBAL;
-        hipLaunchKernelGGL(k_gamma, dim3(grid), dim3(BLOCK), 0, s, env, lst, nk, next, e->d_stats, e->budget_g, e->d_cursors,
-                           e->wave_chunks_r ? chunks_for(nk, grid * (BLOCK / 64)) : 8);
-      } else if (kind == NEXT_MA) {
-        rc = launch_thermal(s, lst, nk, next, e->d_cursors);
-        if (rc != ARTIS_OK) return rc;
-      } else if (kind == NEXT_BB) {
-        hipLaunchKernelGGL(k_blackbody, dim3(nblocks(nk)), dim3(BLOCK), 0, s, env, lst, nk, next, e->d_stats);
-      } else {
-        hipLaunchKernelGGL(k_slow, dim3(nblocks(nk)), dim3(BLOCK), 0, s, env, lst, nk, next, e->d_stats);
-      }
-#if ARTIS_OPT_VPKT_ON
-      if (kind != NEXT_GAMMA && kind != NEXT_BB) {  // the virtual packets of the events the launch recorded
-        HIP_TRY(hipMemsetAsync(e->d_cursors, 0, sizeof(int32_t) * (MAX_CHUNKS + 1), s));
-        if (e->vpkt_cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX && e->Mh.nbfcontinua > 0)
-          hipLaunchKernelGGL((k_vpkt<true, ARTIS_VPKT_TB>), dim3(e->ncu), dim3(ARTIS_VPKT_TB), 0, s, env, e->d_stats, e->d_cursors);
-        else
-          hipLaunchKernelGGL((k_vpkt<false, BLOCK>), dim3(e->ncu * ARTIS_VPKT_WGS), dim3(BLOCK), 0, s, env, e->d_stats, e->d_cursors);
-        HIP_TRY(hipMemsetAsync(e->d_vpkt_count, 0, sizeof(int32_t), s));
-      }
-#endif
-      HIP_TRY(hipEventRecord(e->ev1, s));
-      wall_launch += since(t_launch);
-      rc = read_counts();
-      if (rc != ARTIS_OK) return rc;
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-      e->kms[kind] += ms;
-      e->klaunches[kind]++;
-      visit_launches++;
-      e->kthreads[kind] += nk;
-      e->last_nlaunches++;
-      if (e->trace)
-        fprintf(stderr, "[artis_amd] launch %lld kind %d n=%d %.3f ms -> r %d ma %d slow %d k %d self %d\n", (long long)e->last_nlaunches,
-                kind, nk, ms, cnt[NEXT_RPKT], cnt[NEXT_MA], cnt[NEXT_SLOW], cnt[NEXT_KPKT], cnt[NEXT_NKINDS]);
-      // the alternate list of this kind becomes its current list (its count moves on the device: no second sync)
-      cur[kind] = 1 - cur[kind];
-      cnt[kind] = cnt[NEXT_NKINDS];
-      HIP_TRY(hipMemcpyAsync(e->d_count + kind, e->d_count + NEXT_NKINDS, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-      if (++guard > 2000000LL) {
-        g_last_error = "packet loop did not terminate";
-        return ARTIS_ERR_NOTCONVERGED;
-      }
-    }
-  }
-  }  // tiles
-  if (any_active) e->last_sweeps++;
-  if (e->ntiles == 1 || !any_active || all_done) break;
-  }  // sweeps
-  for (int k = 1; k < NEXT_NKINDS; k++) e->last_propagate_ms += e->kms[k];
-  e->last_propagate_ms += e->kms_tail;
-  if (e->trace)
-    fprintf(stderr, "[artis_amd] host time of the call: %.1f ms = %.1f waiting for the stream + %.1f submitting sorts + %.1f submitting launches + the rest; kernels by their events %.1f ms\n",
-            since(wall_t0), wall_sync, wall_sort, wall_launch, e->last_propagate_ms);
-#if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
-  if (env.bfrate_kept != nullptr && env.bfev != nullptr)
-    hipLaunchKernelGGL(k_bfrate_expand, dim3(nblocks((int64_t)e->Mh.npts_nonempty * 64)), dim3(BLOCK), 0, s, env);
-  e->bfrate_kept_dirty = false;
-#endif
-  if (e->Mh.ncold > 0) {  // what the pool of on-demand records holds at the call's end (since its last emptying): artis_amd_last_pool_usage()
-    uint32_t used = 0;
-    HIP_TRY(hipMemcpy(&used, e->K.ma_pool_used, sizeof(used), hipMemcpyDeviceToHost));
-    e->last_pool_used = std::min<int64_t>(used, env.ma_pool_cap);
-    e->last_pool_cap = env.ma_pool_cap;
-  }
-  int32_t err = 0;
-  HIP_TRY(hipMemcpy(&err, e->d_err, sizeof(err), hipMemcpyDeviceToHost));
-  if (err != 0) {
-    g_last_error = "a kernel raised error flag " + std::to_string(err) + " (an assert_always of the reference would have fired)";
-    if (err == 46) g_last_error = "a cell's pool of on-demand macro-atom records is used up (error flag 46): raise ARTIS_AMD_MA_POOLFRAC (or ARTIS_AMD_MA_HOTFRAC)";
-    return ARTIS_ERR_NOTCONVERGED;
-  }
-  return ARTIS_OK;
-}
-
 int artis_amd_estimators_zero(artis_amd_engine *e, void *hip_stream) {
   if (!e) return ARTIS_ERR_ARG;
   HIP_TRY(hipSetDevice(e->device));
@@ -4405,38 +3906,38 @@ int artis_amd_update_packets(artis_amd_engine *e, artis_packet *packets, int64_t
 
 int artis_amd_last_kernel_ms(artis_amd_engine *e, double *propagate_ms, int64_t *nlaunches) {
   if (!e) return ARTIS_ERR_ARG;
-  if (propagate_ms) *propagate_ms = e->last_propagate_ms;
-  if (nlaunches) *nlaunches = e->last_nlaunches;
+  if (propagate_ms) *propagate_ms = e->last.propagate_ms;
+  if (nlaunches) *nlaunches = e->last.nlaunches;
   return ARTIS_OK;
 }
 
 int artis_amd_last_kernel_launches(artis_amd_engine *e, int64_t *rpkt_launches, int64_t *thermal_launches) {
   if (!e) return ARTIS_ERR_ARG;
-  if (rpkt_launches) *rpkt_launches = e->klaunches[NEXT_RPKT];
-  if (thermal_launches) *thermal_launches = e->klaunches[NEXT_MA] + e->klaunches[NEXT_KPKT];
+  if (rpkt_launches) *rpkt_launches = e->last.klaunches[NEXT_RPKT];
+  if (thermal_launches) *thermal_launches = e->last.klaunches[NEXT_MA] + e->last.klaunches[NEXT_KPKT];
   return ARTIS_OK;
 }
 
 int artis_amd_last_kernel_breakdown(artis_amd_engine *e, double *rpkt_ms, int64_t *rpkt_threads, double *thermal_ms,
                                     int64_t *thermal_threads) {
   if (!e) return ARTIS_ERR_ARG;
-  if (rpkt_ms) *rpkt_ms = e->kms[NEXT_RPKT];
-  if (rpkt_threads) *rpkt_threads = e->kthreads[NEXT_RPKT];
-  if (thermal_ms) *thermal_ms = e->kms[NEXT_MA] + e->kms[NEXT_KPKT];
-  if (thermal_threads) *thermal_threads = e->kthreads[NEXT_MA] + e->kthreads[NEXT_KPKT];
+  if (rpkt_ms) *rpkt_ms = e->last.kms[NEXT_RPKT];
+  if (rpkt_threads) *rpkt_threads = e->last.kthreads[NEXT_RPKT];
+  if (thermal_ms) *thermal_ms = e->last.kms[NEXT_MA] + e->last.kms[NEXT_KPKT];
+  if (thermal_threads) *thermal_threads = e->last.kthreads[NEXT_MA] + e->last.kthreads[NEXT_KPKT];
   return ARTIS_OK;
 }
 
 int artis_amd_last_tiling_fills(artis_amd_engine *e, int64_t *sparse_fills, int64_t *cells_filled) {
   if (!e) return ARTIS_ERR_ARG;
-  if (sparse_fills) *sparse_fills = e->last_sparse_fills;
-  if (cells_filled) *cells_filled = e->last_cells_filled;
+  if (sparse_fills) *sparse_fills = e->last.sparse_fills;
+  if (cells_filled) *cells_filled = e->last.cells_filled;
   return ARTIS_OK;
 }
 
 int artis_amd_last_pool_resets(artis_amd_engine *e, int64_t *resets) {
   if (!e) return ARTIS_ERR_ARG;
-  if (resets) *resets = e->last_pool_resets;
+  if (resets) *resets = e->last.pool_resets;
   return ARTIS_OK;
 }
 
@@ -4455,26 +3956,26 @@ int artis_amd_last_pool_usage(artis_amd_engine *e, int64_t *units_used, int64_t 
 }
 int artis_amd_last_thermal_variants(artis_amd_engine *e, int32_t *mask) {
   if (!e || !mask) return ARTIS_ERR_ARG;
-  *mask = e->thermal_variants;
+  *mask = e->last.thermal_variants;
   return ARTIS_OK;
 }
 int artis_amd_last_estimator_forms(artis_amd_engine *e, int32_t *mask) {
   if (!e || !mask) return ARTIS_ERR_ARG;
-  *mask = e->est_forms;
+  *mask = e->last.est_forms;
   return ARTIS_OK;
 }
 int artis_amd_last_tiling_parked(artis_amd_engine *e, int64_t *parked) {
   if (!e) return ARTIS_ERR_ARG;
-  if (parked) *parked = e->last_parked;
+  if (parked) *parked = e->last.parked;
   return ARTIS_OK;
 }
 
 int artis_amd_last_tiling(artis_amd_engine *e, int64_t *sweeps, int64_t *tile_fills, double *fill_ms, int64_t *listed) {
   if (!e) return ARTIS_ERR_ARG;
-  if (sweeps) *sweeps = e->last_sweeps;
-  if (tile_fills) *tile_fills = e->last_tile_fills;
-  if (fill_ms) *fill_ms = e->last_fill_ms;
-  if (listed) *listed = e->last_listed;
+  if (sweeps) *sweeps = e->last.sweeps;
+  if (tile_fills) *tile_fills = e->last.tile_fills;
+  if (fill_ms) *fill_ms = e->last.fill_ms;
+  if (listed) *listed = e->last.listed;
   return ARTIS_OK;
 }
 
@@ -4482,9 +3983,9 @@ int artis_amd_last_kernel_table(artis_amd_engine *e, double ms[4], int64_t launc
   if (!e) return ARTIS_ERR_ARG;
   const int kinds[4] = {NEXT_RPKT, NEXT_MA, NEXT_KPKT, NEXT_SLOW};
   for (int i = 0; i < 4; i++) {
-    if (ms) ms[i] = e->kms[kinds[i]];
-    if (launches) launches[i] = e->klaunches[kinds[i]];
-    if (packets) packets[i] = e->kthreads[kinds[i]];
+    if (ms) ms[i] = e->last.kms[kinds[i]];
+    if (launches) launches[i] = e->last.klaunches[kinds[i]];
+    if (packets) packets[i] = e->last.kthreads[kinds[i]];
   }
   return ARTIS_OK;
 }
@@ -4497,11 +3998,11 @@ int artis_amd_last_kernel_ms_by_kind(artis_amd_engine *e, double ms[8], int64_t 
     if (launches) launches[i] = 0;
   }
   for (int i = 0; i < 5; i++) {
-    ms[i] = e->kms[kinds[i]];
-    if (launches) launches[i] = e->klaunches[kinds[i]];
+    ms[i] = e->last.kms[kinds[i]];
+    if (launches) launches[i] = e->last.klaunches[kinds[i]];
   }
-  ms[5] = e->kms_tail;
-  ms[6] = e->last_fill_ms;
+  ms[5] = e->last.kms_tail;
+  ms[6] = e->last.fill_ms;
   return ARTIS_OK;
 }
 
@@ -4586,7 +4087,8 @@ int artis_amd_debug_cellcache(artis_amd_engine *e, int c, double *levelpops, dou
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ the timestep-end stages: spectra, radiation-field fit, ion balance
+// ------------------------------------------------------------------ the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance
+#include "stage_propagate.h"
 #include "stage_common.h"
 #include "stage_spectra.h"
 #include "stage_radfield.h"

@@ -1,0 +1,498 @@
+// stage_propagate.h -- artis_amd_update_packets_device: the host's side of propagating the resident packets through one timestep.
+// Sweeps over the cell-cache tiles (one tile, one sweep when the whole cache is resident): list the packets that sit in the tile, fill the
+// tile's cache if any do, advance them until they leave the tile or are done; repeat until a sweep finds no packet left to advance.
+#pragma once
+namespace {
+// a step's return code: anything but ARTIS_OK ends the call
+#define STEP(expr)                     \
+  do {                                 \
+    const int _rc = (expr);            \
+    if (_rc != ARTIS_OK) return _rc;   \
+  } while (0)
+template <int N>
+using Int = std::integral_constant<int, N>;  // a template argument chosen at run time, handed to the generic lambda that makes the launch
+// counting sort of list[0..n) by its entries' keys into e->d_sorted; *out = the list to launch on
+// max_per_cell: a list with more entries per cell than this stays in the order it was appended in. A cell-sorted list puts every lane that is running on
+// an XCD into the same few cells when the cells are few and full, and their estimator atomics then hit the same few addresses at the same time
+// (device-wide atomics on one address are serialised in memory: 20^3 cells, 1e7 packets: k_thermal 907 ms sorted, 725 ms unsorted), while the locality
+// the sort buys matters less because fewer cells' tables compete for the caches. Models with so few cells that the kernels accumulate their per-cell
+// estimators in LDS (Env::cellest_lds) have no such atomics and are always sorted (6^3 cells: 494 ms sorted, 593 unsorted).
+int sort_by_key(artis_amd_engine *e, hipStream_t s, const int32_t *list, const int32_t *keys, int32_t n, const int32_t **out, int nbins,
+                int64_t ncells, int max_per_cell, int32_t nkeys_given = 0) {
+  *out = list;
+  if (!e->sort_lists || n < 2 * BLOCK) return ARTIS_OK;
+  if ((int64_t)n > (int64_t)max_per_cell * (ncells > 0 ? ncells : 1)) return ARTIS_OK;
+  const int32_t nkeys = nkeys_given > 0 ? nkeys_given : e->Mh.ngrid * nbins;
+  HIP_TRY(hipMemsetAsync(e->d_hist, 0, sizeof(int32_t) * (size_t)(nkeys + 1), s));
+  if (nkeys <= SORT_LDS_KEYS)
+    hipLaunchKernelGGL(k_sort_hist_lds, dim3(sort_lds_grid(n)), dim3(BLOCK), 0, s, keys, n, e->d_hist, nkeys);
+  else
+    hipLaunchKernelGGL(k_sort_hist, dim3(nblocks(n)), dim3(BLOCK), 0, s, keys, n, e->d_hist);
+  const int ntiles = (nkeys + SCAN_TILE - 1) / SCAN_TILE;
+  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nkeys, e->d_tiles);
+  hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, s, e->d_tiles, ntiles);
+  hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nkeys, e->d_tiles);
+  if (nkeys <= SORT_LDS_KEYS)
+    hipLaunchKernelGGL(k_sort_scatter_lds, dim3(sort_lds_grid(n)), dim3(BLOCK), 0, s, list, keys, n, e->d_hist, e->d_sorted, nkeys);
+  else
+    hipLaunchKernelGGL(k_sort_scatter, dim3(nblocks(n)), dim3(BLOCK), 0, s, list, keys, n, e->d_hist, e->d_sorted);
+  *out = e->d_sorted;
+  return ARTIS_OK;
+}
+#if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
+// the estimator updates the propagation launch before it recorded (the cells' cache rows are still resident)
+void launch_bfest_dense(artis_amd_engine *e, const Env &env, hipStream_t s) {
+  const bool lds = e->dense_cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX;
+  e->last.est_forms |= (lds ? ARTIS_AMD_EST_BF_DENSE_CONTLDS : ARTIS_AMD_EST_BF_DENSE_HBM) |
+                       (e->dense_lpr == 64 ? ARTIS_AMD_EST_BF_LPR64 : (e->dense_lpr == 16 ? ARTIS_AMD_EST_BF_LPR16 : ARTIS_AMD_EST_BF_LPR32));
+  auto launch = [&](auto lpr) {
+    if (lds)
+      hipLaunchKernelGGL((k_bfest_dense<true, DENSE_TB, decltype(lpr)::value>), dim3(e->ncu * ARTIS_DENSE_WGS), dim3(DENSE_TB), 0, s, env);
+    else
+      hipLaunchKernelGGL((k_bfest_dense<false, BLOCK, decltype(lpr)::value>), dim3(e->ncu * 8), dim3(BLOCK), 0, s, env);
+  };
+  if (e->dense_lpr == 64)
+    launch(Int<64>{});
+  else if (e->dense_lpr == 16)
+    launch(Int<16>{});
+  else
+    launch(Int<32>{});
+}
+#endif
+// the text of a kernel's error flag. Flag 46 reads differently after a launch (the pool cannot hold one record) and at the call's end.
+std::string errflag_text(int32_t flag, bool at_call_end) {
+  if (flag != 46) return "a kernel raised error flag " + std::to_string(flag) + " (an assert_always of the reference would have fired)";
+  return std::string(at_call_end ? "a cell's pool of on-demand macro-atom records is used up"
+                                 : "the pool of on-demand macro-atom records cannot hold a single record of this atomic data") +
+         " (error flag 46): raise ARTIS_AMD_MA_POOLFRAC (or ARTIS_AMD_MA_HOTFRAC)";
+}
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument of the launch f makes
+template <class F>
+void with_flag(bool flag, F &&f) {
+  flag ? f(std::true_type{}) : f(std::false_type{});
+}
+// the state of one artis_amd_update_packets_device call; its members are the steps, the entry point at the end is the loop over sweeps, tiles and visits
+struct PropRun {
+  using clk = std::chrono::steady_clock;
+  static double since(clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); }
+  artis_amd_engine *const e;  // (an aggregate: PropRun run{e, s})
+  const hipStream_t s;
+  Env env = make_env(e);
+  int cur[NEXT_NKINDS] = {};        // which of the two buffers is the current list of each kind
+  int32_t cnt[2 * NEXT_NKINDS] = {};  // host copy of the device counters
+  bool pool_reset_due = false, first_pass = true;
+  const int r_nubins = e->sort_nu ? SORT_NUBINS : 1;  // frequency bins in the keys of the r-packet list
+  // cell groups of the frequency-major keys: the ONE number both the keys (Lists::numajor) and the sort's key count are made of
+  const int32_t r_ngroups = (e->sort_cellshift > 0) ? ((e->Mh.ngrid >> e->sort_cellshift) + 1) : e->Mh.ngrid;
+  const bool adaptive = e->tile_adapt && e->ntiles > 1;
+  int64_t guard = 0;
+  // (ARTIS_AMD_TRACE: where the host's time of the call goes -- waiting for the stream, submitting sorts, submitting launches)
+  double wall_sync = 0., wall_sort = 0., wall_launch = 0.;
+  clk::time_point t_launch;         // when run_kind() began to submit its launch
+  std::vector<int32_t> want;        // the cells prepare_visit() asks for
+  int64_t listed = 0;               // packets the current visit began with
+  int64_t visit_launches = 0;       // split-kernel launches of this visit (a visit parks its tail only after it has advanced its packets)
+  Lists lists_for(int self_kind) const {
+    Lists L;
+    for (int k = 0; k < NEXT_NKINDS; k++) {
+      L.lst[k] = e->d_lists[k][cur[k]];
+      L.key[k] = e->d_keys[k][cur[k]];
+    }
+    L.counts = e->d_count;
+    L.self_kind = self_kind;
+    L.self_list = self_kind > 0 ? e->d_lists[self_kind][1 - cur[self_kind]] : nullptr;
+    L.self_key = self_kind > 0 ? e->d_keys[self_kind][1 - cur[self_kind]] : nullptr;
+    L.self_count = e->d_count + NEXT_NKINDS;  // one alternate counter: only one kernel runs at a time
+    L.kpkt_slot = NEXT_MA;  // k-packets travel in the thermal list
+    L.nubins = r_nubins;
+    L.numajor = e->sort_numajor ? r_ngroups : 0;
+    L.cellshift = e->sort_cellshift;
+    L.mabins = e->ma_bins;
+    return L;
+  }
+  int read_counts() {
+    // (one copy into pinned memory: counters and error flag are neighbours. Two copies into the stack -- pageable, staged by the runtime -- were a
+    // measurable share of the ~90 ms a headline step spends outside its kernels)
+    const clk::time_point t_sync = clk::now();
+    HIP_TRY(hipMemcpyAsync(e->h_counts, e->d_count, sizeof(int32_t) * (2 * NEXT_NKINDS + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    wall_sync += since(t_sync);
+    std::memcpy(cnt, e->h_counts, sizeof(int32_t) * 2 * NEXT_NKINDS);
+    const int32_t errflag = e->h_counts[2 * NEXT_NKINDS];
+    HIP_TRY(hipGetLastError());
+    if (errflag != 0) {
+      g_last_error = errflag_text(errflag, false);
+      (void)hipMemsetAsync(e->d_err, 0, sizeof(int32_t), s);
+      return ARTIS_ERR_NOTCONVERGED;
+    }
+    if (cnt[2 * NEXT_NKINDS - 1] != 0) {  // a lane found the pool of on-demand records used up (Env::ma_pool_full)
+      pool_reset_due = true;
+      HIP_TRY(hipMemsetAsync(e->d_count + (2 * NEXT_NKINDS - 1), 0, sizeof(int32_t), s));
+    }
+    return ARTIS_OK;
+  }
+  // The pool of on-demand records used up: the packets that wait for a record sit on the slow-path list (PEND_MA_FILL). Before that list's next
+  // launch -- after the thermal kernel has walked on with the records the last one filled -- the pool is emptied: every cold level of the resident
+  // cells is without a record again and is filled when next needed, exactly as after a tile's refill. Costs fills, never an answer.
+  int reset_pool_if_due() {
+    if (!pool_reset_due || e->Mh.ncold <= 0) return ARTIS_OK;
+    pool_reset_due = false;
+    HIP_TRY(hipMemsetAsync(e->K.ma_rowtab, 0xFF, sizeof(int32_t) * (size_t)(e->tile_cells * (int64_t)e->Mh.ncold), s));  // (every row: k_ma_reset)
+    HIP_TRY(hipMemsetAsync(e->K.ma_pool_used, 0, sizeof(uint32_t), s));
+    e->last.pool_resets++;
+    if (e->trace) fprintf(stderr, "[artis_amd] the pool of on-demand records was used up: emptied (%lld)\n", (long long)e->last.pool_resets);
+    return ARTIS_OK;
+  }
+  // Before a visit: the cache rows its packets need. Tiled: where do the packets wait? The cells in which most of them do are made resident
+  // (choose_cells(): a window or a set of blocks of cells, or -- few packets -- the very cells); cells that are resident already keep their rows,
+  // the others are filled; *nothing_left is set where no packet waits anywhere. Untiled: the whole cache, if the cell state has changed since its last fill.
+  int prepare_visit(int tile, bool *nothing_left) {
+    const int64_t ncell_all = e->Mh.npts_nonempty;
+    if (e->ntiles > 1) {
+      env = make_env(e);
+      HIP_TRY(hipMemsetAsync(e->d_waiting, 0, sizeof(int32_t) * (size_t)(ncell_all + 1), s));
+      hipLaunchKernelGGL(k_count_waiting, dim3(nblocks(e->npackets)), dim3(BLOCK), 0, s, env, e->d_waiting, e->d_waiting + ncell_all);
+      HIP_TRY(hipMemcpyAsync(e->h_waiting.data(), e->d_waiting, sizeof(int32_t) * (size_t)(ncell_all + 1), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      int64_t total = 0;
+      for (int64_t c = 0; c < ncell_all; c++) total += e->h_waiting[(size_t)c];
+      if (total == 0 && e->h_waiting[(size_t)ncell_all] == 0) {
+        *nothing_left = true;
+        return ARTIS_OK;
+      }
+      int64_t holds = 0, nfilled = 0;
+      bool sparse = false;
+      choose_cells(e, e->h_waiting, want, &holds, &sparse, adaptive ? -1 : (int64_t)tile * e->tile_cells);
+      if (holds == 0) want.clear();  // (no packet waits for a row of these cells: the visit is for the packets that need none, if any)
+      if (e->trace)
+        fprintf(stderr, "[artis_amd] visit %lld: %lld packets wait in cells, %d need no row; %zu cells chosen%s hold %lld\n", (long long)e->last_visits,
+                (long long)total, e->h_waiting[(size_t)ncell_all], want.size(), sparse ? " (sparse)" : "", (long long)holds);
+      HIP_TRY(hipEventRecord(e->ev2, s));
+      STEP(make_resident(e, want, s, &nfilled));
+      if (nfilled > 0) {
+        HIP_TRY(hipEventRecord(e->ev3, s));
+        HIP_TRY(hipEventSynchronize(e->ev3));
+        float fms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&fms, e->ev2, e->ev3));
+        e->last.fill_ms += fms;
+        e->last.tile_fills++;
+        e->last.cells_filled += nfilled;
+        if (sparse) e->last.sparse_fills++;
+      }
+    } else if (e->tile_valid_lo != 0) {
+      STEP(populate_tile(e, s));
+    }
+    env = make_env(e);
+    return ARTIS_OK;
+  }
+  // the packets that sit in resident cells (and those that need no row) onto the lists of their kinds; cnt[] = how many of each
+  int classify() {
+    for (int k = 0; k < NEXT_NKINDS; k++) cur[k] = 0;
+    HIP_TRY(hipMemsetAsync(e->d_count, 0, sizeof(int32_t) * 2 * NEXT_NKINDS, s));
+    hipLaunchKernelGGL(k_classify, dim3(nblocks(e->npackets)), dim3(BLOCK), 0, s, env, lists_for(0), std::exchange(first_pass, false) ? 1 : 0);
+    return read_counts();
+  }
+  int64_t count_listed() const { return (int64_t)cnt[NEXT_RPKT] + cnt[NEXT_MA] + cnt[NEXT_SLOW] + cnt[NEXT_KPKT] + cnt[NEXT_GAMMA] + cnt[NEXT_BB]; }
+  // chunks of a pull kernel's list (one per wave of its grid, or eight: one per XCD); steps per packet of a launch (the smaller budget for a short list, where one is set)
+  static int chunk_count(bool per_wave, int32_t nk, int nwaves) { return per_wave ? chunks_for(nk, nwaves) : 8; }
+  int budget_for(int budget, int budget_small, int32_t nk) const { return (budget_small > 0 && nk < e->small_list) ? std::min(budget_small, budget) : budget; }
+  // ... and after the launch's list is used up (drain: only where the next launch will be large too, so that what is handed on runs beside a full list)
+  int drain_for(int drain, int budget, int32_t nk) const { return (drain > 0 && nk >= e->drain_min_list) ? drain : budget; }
+  // DETAILED_BF builds: the estimator updates the launch before recorded (the cells' cache rows are still resident)
+  int flush_bf_events() {
+#if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
+    if (env.bfev != nullptr) {
+      launch_bfest_dense(e, env, s);
+      HIP_TRY(hipMemsetAsync(e->d_bfev_count, 0, sizeof(int32_t), s));
+    }
+#endif
+    return ARTIS_OK;
+  }
+  int launch_rpkt(const int32_t *lst, int32_t nk, const Lists &next) {
+    const int grid = (int)std::min<int64_t>(((int64_t)nk + ARTIS_RPKT_TB - 1) / ARTIS_RPKT_TB, (int64_t)e->ncu * ARTIS_RPKT_WGS);  // persistent: every block resident
+    const int bud_r = budget_for(e->budget_r, e->budget_r_small, nk);
+    const int nch = chunk_count(e->wave_chunks_r, nk, grid * (ARTIS_RPKT_TB / 64));
+    const int drain = drain_for(e->drain_r, bud_r, nk);
+    const bool rpkt_line_lds = e->line_lds && e->Mh.nlines <= LINE_LDS_MAX && e->Mh.nlines > 0 && !(env.cellest_n_r > RPKT_CELLEST_CAP);
+    const bool rpkt_cont_lds = !rpkt_line_lds && e->cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX && e->Mh.nbfcontinua > 0 &&
+                               !(env.cellest_n_r > RPKT_CELLEST_CAP);
+    // (the kernel's own choice, k_rpkt: the workgroup's array for cellest_n_r > 0, else the waves' caches except in the LINE_LDS form)
+    e->last.est_forms |= env.cellest_n_r > 0 ? (rpkt_line_lds ? ARTIS_AMD_EST_RPKT_LDS_LINE
+                                                              : (rpkt_cont_lds ? ARTIS_AMD_EST_RPKT_LDS_CONT : ARTIS_AMD_EST_RPKT_LDS_NOCONT))
+                                             : ((!rpkt_line_lds && env.estcache_on) ? ARTIS_AMD_EST_RPKT_WAVECACHE : ARTIS_AMD_EST_RPKT_GLOBAL);
+    auto launch = [&](auto cont_lds, auto line_lds) {
+      hipLaunchKernelGGL((k_rpkt<decltype(cont_lds)::value, ARTIS_RPKT_TB, decltype(line_lds)::value>), dim3(grid), dim3(ARTIS_RPKT_TB), 0, s, env, lst, nk,
+                         next, e->d_stats, bud_r, e->d_cursors, nch, drain);
+    };
+    if (rpkt_line_lds)
+      launch(std::false_type{}, std::true_type{});
+    else if (rpkt_cont_lds)
+      launch(std::true_type{}, std::false_type{});
+    else
+      launch(std::false_type{}, std::false_type{});
+    if (ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON && env.bfev == nullptr) e->last.est_forms |= ARTIS_AMD_EST_BF_INPLACE;
+    return flush_bf_events();
+  }
+  int launch_thermal(const int32_t *lst, int32_t nk, const Lists &next) {
+    const int bud_t = budget_for(e->budget_t, e->budget_t_small, nk);
+    const int drain = drain_for(e->drain_t, bud_t, nk);
+    const size_t tq_bytes = tq_lds_bytes(TQ_TB, e->Mh.nlevels, e->Mh.nalltrans);
+    const bool cold = e->Mh.ncold > 0;  // (kernels built with the on-demand records' look-ups only where the model has cold levels)
+    if (cold) e->last.thermal_variants |= ARTIS_AMD_THERMAL_COLD;
+    auto launch = [&](auto tb, auto tables_lds, int grid, int nchunks, int chunk_mode) {
+      with_flag(cold, [&](auto is_cold) {
+        hipLaunchKernelGGL((k_thermal<decltype(tb)::value, decltype(tables_lds)::value, decltype(is_cold)::value>), dim3(grid), dim3(decltype(tb)::value), 0,
+                           s, env, lst, nk, next, e->d_stats, bud_t, e->d_cursors, nchunks, chunk_mode, drain);
+      });
+    };
+    const int grid1024 = (int)std::min<int64_t>(((int64_t)nk + 1023) / 1024, (int64_t)e->ncu);
+    if (e->thermal_refill && ARTIS_THERMAL_SPLIT_EXACT && env.cellest_n_t == 0 && tq_bytes <= 160 * 1024 - 1024 && nk >= 4096 && e->Mh.nlevels < 32768) {
+      e->last.thermal_variants |= ARTIS_AMD_THERMAL_REFILL;
+      e->last.est_forms |= ARTIS_AMD_EST_THERMAL_GLOBAL;  // (k_thermal_q keeps no per-cell sums in LDS)
+      if (!e->tq_attr_set) {  // (per engine, i.e. per device: the attribute is the device's, not the process's)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_thermal_q<TQ_TB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+        HIP_TRY(hipFuncSetAttribute((const void *)k_thermal_q<TQ_TB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+        e->tq_attr_set = true;
+      }
+      const int grid = (int)std::min<int64_t>(((int64_t)nk + TQ_TB - 1) / TQ_TB, (int64_t)e->ncu);
+      with_flag(cold, [&](auto is_cold) {
+        hipLaunchKernelGGL((k_thermal_q<TQ_TB, decltype(is_cold)::value>), dim3(grid), dim3(TQ_TB), tq_bytes, s, env, lst, nk, next, e->d_stats, bud_t,
+                           e->d_cursors, chunk_count(e->wave_chunks_t, nk, grid * (TQ_TB / 64)), drain, e->tq_low);
+      });
+    } else if (e->ma_tables_lds && e->Mh.nlevels <= MA_LDS_LEVELS && e->Mh.nalltrans <= MA_LDS_TRANS && nk >= 4096) {
+      e->last.thermal_variants |= ARTIS_AMD_THERMAL_LDS_TABLES;
+      e->last.est_forms |= thermal_est_form(env, 1);
+      launch(Int<1024>{}, Int<1>{}, grid1024, chunk_count(e->wave_chunks_t, nk, grid1024 * 16), 0);
+    } else if (e->ma_tables_lds && e->Mh.nlevels <= MA_LDS_LEVELS2 && nk >= 4096 && env.cellest_n_t == 0) {
+      e->last.thermal_variants |= ARTIS_AMD_THERMAL_LDS_LEVELPACK;
+      e->last.est_forms |= thermal_est_form(env, 2);
+      launch(Int<1024>{}, Int<2>{}, grid1024, chunk_count(e->wave_chunks_t, nk, grid1024 * 16), 0);
+    } else {
+      const int grid = (int)std::min<int64_t>(((int64_t)nk + ARTIS_THERMAL_TB - 1) / ARTIS_THERMAL_TB,
+                                              (int64_t)e->ncu * std::min(e->thermal_blocks_per_cu, ARTIS_THERMAL_WGS));  // persistent: every workgroup resident
+      const bool per_cu = e->cu_chunks_t && nk >= 256 * 1024;
+      e->last.thermal_variants |= ARTIS_AMD_THERMAL_PLAIN;
+      e->last.est_forms |= thermal_est_form(env, 0);
+      launch(Int<ARTIS_THERMAL_TB>{}, Int<0>{}, grid, per_cu ? 256 : chunk_count(e->wave_chunks_t, nk, grid * (ARTIS_THERMAL_TB / 64)), per_cu ? 2 : 0);
+    }
+    return ARTIS_OK;
+  }
+  void launch_gamma(const int32_t *lst, int32_t nk, const Lists &next) {
+    const int grid = std::min(nblocks(nk), e->ncu * ARTIS_GAMMA_WAVES);
+    e->last.est_forms |= env.cellest_n_g > 0 ? ARTIS_AMD_EST_GAMMA_LDS : ARTIS_AMD_EST_GAMMA_GLOBAL;
+    hipLaunchKernelGGL(k_gamma, dim3(grid), dim3(BLOCK), 0, s, env, lst, nk, next, e->d_stats, e->budget_g, e->d_cursors,
+                       chunk_count(e->wave_chunks_r, nk, grid * (BLOCK / 64)));
+  }
+  // VPKT builds: the virtual packets of the events the launch of `kind` recorded
+  int launch_vpkt_followup([[maybe_unused]] int kind) {
+#if ARTIS_OPT_VPKT_ON
+    if (kind != NEXT_GAMMA && kind != NEXT_BB) {
+      HIP_TRY(hipMemsetAsync(e->d_cursors, 0, sizeof(int32_t) * (MAX_CHUNKS + 1), s));
+      if (e->vpkt_cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX && e->Mh.nbfcontinua > 0)
+        hipLaunchKernelGGL((k_vpkt<true, ARTIS_VPKT_TB>), dim3(e->ncu), dim3(ARTIS_VPKT_TB), 0, s, env, e->d_stats, e->d_cursors);
+      else
+        hipLaunchKernelGGL((k_vpkt<false, BLOCK>), dim3(e->ncu * ARTIS_VPKT_WGS), dim3(BLOCK), 0, s, env, e->d_stats, e->d_cursors);
+      HIP_TRY(hipMemsetAsync(e->d_vpkt_count, 0, sizeof(int32_t), s));
+    }
+#endif
+    return ARTIS_OK;
+  }
+  // After a launch (events ev0 .. ev1 around it): the counts, its time, the call's records; the alternate list of `kind` -- what the launch kept of its own
+  // kind -- becomes the current one (its count moves on the device: no second sync). tail: k_tail's launch over n packets; `kind` is NEXT_SLOW, the one list it appends to.
+  int finish_launch(int kind, bool tail, int32_t n) {
+    HIP_TRY(hipEventRecord(e->ev1, s));
+    if (!tail) wall_launch += since(t_launch);
+    STEP(read_counts());
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    e->last.nlaunches++;
+    (tail ? e->last.kms_tail : e->last.kms[kind]) += ms;
+    if (!tail) {
+      e->last.klaunches[kind]++;
+      e->last.kthreads[kind] += n;
+      visit_launches++;
+    }
+    if (e->trace && tail)
+      fprintf(stderr, "[artis_amd] launch %lld tail n=%d+0 %.3f ms -> r %d ma %d slow %d gamma %d bb %d\n", (long long)e->last.nlaunches, n, ms, cnt[NEXT_RPKT], cnt[NEXT_MA], cnt[NEXT_NKINDS], cnt[NEXT_GAMMA], cnt[NEXT_BB]);
+    else if (e->trace)
+      fprintf(stderr, "[artis_amd] launch %lld kind %d n=%d %.3f ms -> r %d ma %d slow %d k %d self %d\n", (long long)e->last.nlaunches, kind, n, ms, cnt[NEXT_RPKT], cnt[NEXT_MA], cnt[NEXT_SLOW], cnt[NEXT_KPKT], cnt[NEXT_NKINDS]);
+    cur[kind] = 1 - cur[kind];
+    cnt[kind] = cnt[NEXT_NKINDS];
+    HIP_TRY(hipMemcpyAsync(e->d_count + kind, e->d_count + NEXT_NKINDS, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (++guard > 2000000LL) {
+      g_last_error = "packet loop did not terminate";
+      return ARTIS_ERR_NOTCONVERGED;
+    }
+    return ARTIS_OK;
+  }
+  // the last packets of the r-packet, thermal, slow-path and black-body kinds: one launch carries each through all its remaining alternations (k_tail)
+  static constexpr int tail_kinds[4] = {NEXT_RPKT, NEXT_MA, NEXT_SLOW, NEXT_BB};
+  int64_t count_tail() const { return (int64_t)cnt[NEXT_RPKT] + cnt[NEXT_MA] + cnt[NEXT_SLOW] + cnt[NEXT_BB]; }
+  int run_tail(int64_t tail_n) {
+    // the four current lists are consumed whole, and no packet comes back to them -- but for one case: a packet that waits for a record of a
+    // pool that is used up leaves for the slow-path list (k_tail "waits"). That entry must not land in a buffer other waves still read their
+    // packets from: the slow-path kind is the launch's own kind, its entries go to the ALTERNATE slow-path list, which becomes the current one
+    // (finish_launch(), as after a launch of the slow-path kernel).
+    TailLists in;
+    for (int i = 0; i < 4; i++) {
+      in.list[i] = e->d_lists[tail_kinds[i]][cur[tail_kinds[i]]];
+      in.n[i] = cnt[tail_kinds[i]];
+      HIP_TRY(hipMemsetAsync(e->d_count + tail_kinds[i], 0, sizeof(int32_t), s));
+    }
+    HIP_TRY(hipMemsetAsync(e->d_count + NEXT_NKINDS, 0, sizeof(int32_t), s));
+    STEP(reset_pool_if_due());
+    HIP_TRY(hipEventRecord(e->ev0, s));
+    e->last.thermal_variants |= ARTIS_AMD_THERMAL_TAIL;
+    hipLaunchKernelGGL(k_tail, dim3(nblocks(tail_n * 64)), dim3(BLOCK), 0, s, env, in, lists_for(NEXT_SLOW), e->d_stats);
+    STEP(flush_bf_events());
+    return finish_launch(NEXT_SLOW, true, (int32_t)tail_n);
+  }
+  // one launch = the whole current list of one kind: sort it, launch its kernel and what follows the kernel
+  int run_kind(int kind) {
+    const int32_t nk = cnt[kind];
+    const Lists next = lists_for(kind);
+    const int32_t *lst = e->d_lists[kind][cur[kind]];
+    const clk::time_point t_sort = clk::now();
+    if (kind == NEXT_RPKT || kind == NEXT_GAMMA || (kind == NEXT_MA && e->sort_ma)) {
+      STEP(sort_by_key(e, s, e->d_lists[kind][cur[kind]], e->d_keys[kind][cur[kind]], nk, &lst,
+                       kind == NEXT_RPKT ? r_nubins : (kind == NEXT_MA ? e->ma_bins : 1), e->tile_cells,
+                       kind == NEXT_MA ? (env.cellest_n_t > 0 ? INT32_MAX : e->sort_maxpc_t) : (env.cellest_n_r > 0 ? INT32_MAX : e->sort_maxpc_r),
+                       (kind == NEXT_RPKT && r_nubins > 1 && e->sort_numajor) ? r_ngroups * r_nubins : 0));
+    }
+    wall_sort += since(t_sort);
+    t_launch = clk::now();
+    if (kind == NEXT_SLOW) STEP(reset_pool_if_due());
+    // the kernel starts with an empty current list of its own kind: everything it keeps goes to the alternate list
+    hipLaunchKernelGGL(k_launch_reset, dim3(1), dim3(BLOCK), 0, s, e->d_count, kind, e->d_cursors);  // (one command instead of three memsets)
+    HIP_TRY(hipEventRecord(e->ev0, s));
+    if (kind == NEXT_RPKT)
+      STEP(launch_rpkt(lst, nk, next));
+    else if (kind == NEXT_GAMMA)
+      launch_gamma(lst, nk, next);
+    else if (kind == NEXT_MA)
+      STEP(launch_thermal(lst, nk, next));
+    else if (kind == NEXT_BB)
+      hipLaunchKernelGGL(k_blackbody, dim3(nblocks(nk)), dim3(BLOCK), 0, s, env, lst, nk, next, e->d_stats);
+    else
+      hipLaunchKernelGGL(k_slow, dim3(nblocks(nk)), dim3(BLOCK), 0, s, env, lst, nk, next, e->d_stats);
+    STEP(launch_vpkt_followup(kind));
+    return finish_launch(kind, false, nk);
+  }
+  // Tiled runs: does the visit leave what is left of it waiting in its cells? (Their state is in the packet store; the next classify pass lists
+  // them again.) tail_now: the tail kernel would take them with its next launch.
+  bool should_park(int sweep, int tile, int64_t tail_n, bool tail_now) {
+    if (!e->park_tails || e->ntiles <= 1 || visit_launches == 0) return false;
+    // (round 6) a visit that began larger parks what is left of it once that has fallen to park_at packets -- BEFORE the long run
+    // of small, latency-bound launches that its last packets would otherwise cost every visit: they wait in their cells and are listed
+    // again, merged with the other windows' stragglers, by a later visit (a visit that BEGINS with that few runs them to their end)
+    if (e->park_at > e->tail_max && listed > e->park_at && tail_n > 0 && tail_n + cnt[NEXT_KPKT] <= e->park_at) {
+      e->last.parked += tail_n + cnt[NEXT_KPKT] + cnt[NEXT_GAMMA];
+      if (e->trace) fprintf(stderr, "[artis_amd] sweep %d tile %d: %lld packets parked (park_at)\n", sweep, tile, (long long)(tail_n + cnt[NEXT_KPKT]));
+      return true;
+    }
+    // a visit that began larger than a tail: its last packets run with the packets that return to the tile in the next sweep, instead of one long
+    // k_tail launch per visit. A visit that BEGINS with a tail's worth of packets runs them to their end: no packet waits more than once without
+    // the tile's population having shrunk to that.
+    if (tail_now && listed > e->tail_max) {
+      e->last.parked += tail_n + cnt[NEXT_GAMMA];
+      if (e->trace) fprintf(stderr, "[artis_amd] sweep %d tile %d: %lld packets parked\n", sweep, tile, (long long)tail_n);
+      return true;
+    }
+    return false;
+  }
+  // One visit: launches until every list is empty or the rest is parked. Order: slow path, k-packets, macro-atoms, r-packets, so that a
+  // k-packet -> macro-atom -> k-packet cycle costs two launches.
+  int run_visit(int sweep, int tile) {
+    static constexpr int order[6] = {NEXT_SLOW, NEXT_GAMMA, NEXT_BB, NEXT_KPKT, NEXT_MA, NEXT_RPKT};
+    e->last_visits++;
+    listed = count_listed();
+    e->last.listed += listed;
+    visit_launches = 0;
+    if (e->trace) fprintf(stderr, "[artis_amd] sweep %d tile %d of %d\n", sweep, tile, e->ntiles);
+    // the tail kernel takes the end of a population that began larger (a population that begins below the threshold runs on
+    // the split kernels throughout, unless ARTIS_AMD_TAIL_ALWAYS=1)
+    // (tiled runs: the later sweeps bring a tile a few stragglers at a time; each such visit is a tail from its first launch)
+    const bool tail_ok = e->tail_max > 0 && (e->tail_always || listed > e->tail_max || sweep > 0 || (adaptive && e->last_visits > e->ntiles));
+    while (count_listed() > 0) {
+      const int64_t tail_n = count_tail();
+      const bool tail_now = tail_ok && tail_n > 0 && tail_n <= e->tail_max && cnt[NEXT_KPKT] == 0;
+      if (should_park(sweep, tile, tail_n, tail_now)) break;
+      if (tail_now) {
+        STEP(run_tail(tail_n));
+        continue;
+      }
+      for (int kind : order)
+        if (cnt[kind] > 0) STEP(run_kind(kind));
+    }
+    return ARTIS_OK;
+  }
+};
+}  // namespace
+extern "C" int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_stream) {
+  if (!e || !e->have_cells || !e->d_pkt) {
+    g_last_error = "engine needs artis_amd_set_cellstate() and resident packets first";
+    return ARTIS_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  e->fit_since_step = false;
+  hipStream_t s = (hipStream_t)hip_stream;
+  e->last = {};
+  if (e->npackets == 0) return ARTIS_OK;
+#ifdef ARTIS_VISIT_COUNTS
+  const size_t vb = sizeof(uint32_t) * (size_t)e->Mh.npts_nonempty * (size_t)e->Mh.nlevels;
+  if (e->d_visit_counts == nullptr) HIP_TRY(hipMalloc((void **)&e->d_visit_counts, vb));
+  HIP_TRY(hipMemsetAsync(e->d_visit_counts, 0, vb, s));
+#endif
+  PropRun run{e, s};
+  if (e->d_bfrate_kept != nullptr) {
+    if (e->bfrate_kept_dirty)
+      HIP_TRY(hipMemsetAsync(e->d_bfrate_kept, 0, sizeof(double) * (size_t)e->Mh.npts_nonempty * (size_t)e->Mh.nbfcontinua, s));
+    e->bfrate_kept_dirty = true;
+  }
+  const PropRun::clk::time_point wall_t0 = PropRun::clk::now();
+  if (e->ntiles > 1 && e->d_waiting == nullptr) {
+    HIP_TRY(hipMalloc((void **)&e->d_waiting, sizeof(int32_t) * (size_t)(e->Mh.npts_nonempty + 1)));
+    e->h_waiting.assign((size_t)e->Mh.npts_nonempty + 1, 0);
+  }
+  e->last_visits = 0;
+  for (int sweep = 0;; sweep++) {
+    bool any_active = false, all_done = false;
+    for (int tstep = 0; tstep < e->ntiles; tstep++) {
+      // sweeps alternate their direction: a packet that left its tile against the direction of one sweep is met by the next
+      // one on its way back (with one direction it waits a whole sweep per backward crossing)
+      const int tile = (e->tile_zigzag && (sweep & 1)) ? e->ntiles - 1 - tstep : tstep;
+      STEP(run.prepare_visit(tile, &all_done));
+      if (all_done) break;
+      STEP(run.classify());
+      if (run.count_listed() == 0) continue;
+      any_active = true;
+      STEP(run.run_visit(sweep, tile));
+    }
+    if (any_active) e->last.sweeps++;
+    if (e->ntiles == 1 || !any_active || all_done) break;
+  }
+  for (int k = 1; k < NEXT_NKINDS; k++) e->last.propagate_ms += e->last.kms[k];
+  e->last.propagate_ms += e->last.kms_tail;
+  if (e->trace)
+    fprintf(stderr, "[artis_amd] host time of the call: %.1f ms = %.1f waiting for the stream + %.1f submitting sorts + %.1f submitting launches + the rest; kernels by their events %.1f ms\n",
+            PropRun::since(wall_t0), run.wall_sync, run.wall_sort, run.wall_launch, e->last.propagate_ms);
+#if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
+  if (run.env.bfrate_kept != nullptr && run.env.bfev != nullptr)
+    hipLaunchKernelGGL(k_bfrate_expand, dim3(nblocks((int64_t)e->Mh.npts_nonempty * 64)), dim3(BLOCK), 0, s, run.env);
+  e->bfrate_kept_dirty = false;
+#endif
+  if (e->Mh.ncold > 0) {  // what the pool of on-demand records holds at the call's end (since its last emptying): artis_amd_last_pool_usage()
+    uint32_t used = 0;
+    HIP_TRY(hipMemcpy(&used, e->K.ma_pool_used, sizeof(used), hipMemcpyDeviceToHost));
+    e->last_pool_used = std::min<int64_t>(used, run.env.ma_pool_cap);
+    e->last_pool_cap = run.env.ma_pool_cap;
+  }
+  int32_t err = 0;
+  HIP_TRY(hipMemcpy(&err, e->d_err, sizeof(err), hipMemcpyDeviceToHost));
+  if (err != 0) {
+    g_last_error = errflag_text(err, true);
+    return ARTIS_ERR_NOTCONVERGED;
+  }
+  return ARTIS_OK;
+}
+#undef STEP

@@ -29,6 +29,24 @@ def test_exports_every_declared_symbol(lib):
     assert set(EXPORTED_SYMBOLS) == declared
 
 
+def test_build_sources_list_every_included_file():
+    """needs_build() compares the library's age with SOURCES only: a file of csrc/ that the engine includes (directly or through
+    another of its files) and SOURCES does not name would leave a stale library in place."""
+    from artis_amd.build import CSRC, SOURCES
+
+    seen, todo = set(), ["artis_engine.hip"]
+    while todo:
+        name = todo.pop()
+        if name in seen:
+            continue
+        seen.add(name)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(CSRC, name)).read(), re.M):
+            if os.sep not in inc and os.path.exists(os.path.join(CSRC, inc)):  # (include/*.h: needs_build() names them itself)
+                todo.append(inc)
+    assert "stage_propagate.h" in seen
+    assert seen <= set(SOURCES), f"not in artis_amd.build.SOURCES: {sorted(seen - set(SOURCES))}"
+
+
 def test_packet_layout_matches_header(lib):
     lib.artis_amd_sizeof_packet.restype = C.c_size_t
     assert lib.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize == 256
