@@ -452,6 +452,37 @@ class Spectra(C.Structure):
                [(k, C.c_int32) for k in ("ntimesteps", "ndirslots", "nelements", "max_nions", "proccount", "reserved")]
 
 
+# engine configuration and layout plan (include/artis_amd.h artis_amd_config / artis_amd_plan)
+class Config(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("cache_budget_bytes", C.c_int64), ("cache_headroom_bytes", C.c_int64),
+                ("pop_scratch_bytes", C.c_int64), ("ma_hot_fraction", C.c_double), ("ma_pool_fraction", C.c_double),
+                ("tail_threshold", C.c_int64), ("tile_park_at", C.c_int64), ("keep_line_dpop", C.c_int32), ("reserved", C.c_int32)]
+
+
+# what artis_amd_config_default() writes: every field "automatic / default"
+CONFIG_DEFAULTS = dict(cache_budget_bytes=0, cache_headroom_bytes=-1, pop_scratch_bytes=-1, ma_hot_fraction=-1.0, ma_pool_fraction=-1.0,
+                       tail_threshold=-1, tile_park_at=-1, keep_line_dpop=-1, reserved=0)
+
+
+def config(**fields) -> Config:
+    """An artis_amd_config with the given fields set and every other one at "automatic / default"."""
+    unknown = set(fields) - set(CONFIG_DEFAULTS)
+    if unknown:
+        raise TypeError(f"artis_amd_config has no field {sorted(unknown)}")
+    return Config(struct_size=C.sizeof(Config), **{**CONFIG_DEFAULTS, **fields})
+
+
+class Plan(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("bytes_per_cell", C.c_int64), ("cells_resident", C.c_int64), ("ntiles", C.c_int32),
+                ("ncold_levels", C.c_int32), ("hot_fraction", C.c_double), ("pool_slots", C.c_int64), ("cache_bytes", C.c_int64),
+                ("pool_bytes", C.c_int64), ("pop_scratch_bytes", C.c_int64), ("model_bytes", C.c_int64), ("free_bytes_assumed", C.c_int64),
+                ("line_dpop_kept", C.c_int32), ("reserved", C.c_int32)]
+
+
+def struct_dict(s: C.Structure) -> dict:
+    return {k: getattr(s, k) for k, _ in s._fields_}
+
+
 # radiation-field fit (include/artis_amd.h artis_amd_radfield_*)
 RADFIELD_FITTED, RADFIELD_NUBAR_KEPT, RADFIELD_TJ_KEPT = 1, 2, 4
 RADFIELD_TJ_LOW, RADFIELD_TJ_HIGH, RADFIELD_TR_LOW, RADFIELD_TR_HIGH = 8, 16, 32, 64

@@ -9,7 +9,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libartis_amd.so")
-SOURCES = ["artis_engine.hip", "physics.h", "tables.h", "model_build.h", "spectra.h", "radfield_fit.h", "ion_balance.h",
+SOURCES = ["artis_engine.hip", "physics.h", "tables.h", "model_build.h", "engine_config.h", "spectra.h", "radfield_fit.h", "ion_balance.h",
            "stage_propagate.h", "stage_common.h", "stage_spectra.h", "stage_radfield.h", "stage_ionbal.h"]
 # -ffp-contract=off: the operation order of physics.h is part of the parity contract (no FMA contraction).
 # -munsafe-fp-atomics: estimator adds become global_atomic_add_f64, not compare-and-swap loops.

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "model_build.h"
+#include "engine_config.h"
 #include "physics.h"
 #include "radfield_fit.h"
 #include "ion_balance.h"
@@ -2416,6 +2417,8 @@ struct LastCall {
 };
 struct artis_amd_engine {
   int device = 0;
+  EngineConfig cfg;           // the resolved configuration (engine_config.h resolve_config: struct field, else ARTIS_AMD_* variable, else default)
+  double cache_budget = 0.;   // [B] the budget the rows were sized by (given, or the automatic rule on the free memory at creation)
   SpecState *spec = nullptr;  // artis_amd_spectra_*: nothing until the first call
   RfState *rf = nullptr;      // artis_amd_radfield_*: nothing until the first call
   IbState *ib = nullptr;      // artis_amd_grid_update*: nothing until the first call
@@ -2500,7 +2503,7 @@ struct artis_amd_engine {
   // (builds with the detailed bound-free estimators -- the nltenebular family -- alternate twice as often between the
   // kernels and their r-packet steps are ~3x as heavy: measured optimum 16384 / 4 / 1024 instead of 4096 / 8 / 2048,
   // nltenebular step 1801 -> 1690 ms, profiles/r03/neb_sweep*.txt)
-  int tail_max = ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON ? 16384 : 4096;  // r-packets + thermal packets left at which k_tail takes over (ARTIS_AMD_TAIL; 0 = never)
+  int tail_max = ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON ? 16384 : 4096;  // r-packets + thermal packets left at which k_tail takes over (artis_amd_config.tail_threshold; 0 = never)
   bool tail_always = false;           // ... also for a population that starts below it (ARTIS_AMD_TAIL_ALWAYS=1)
   // the cells a fill of a tiled cache works on (make_resident()). Sparse fills: a visit for which few packets wait makes the cells in which they
   // wait (and the cells around those) resident instead of a whole window. ARTIS_AMD_SPARSE_FILL=0: whole windows.
@@ -2509,7 +2512,7 @@ struct artis_amd_engine {
   int64_t sparse_max_listed = 16384;  // ... for visits that list at most this many packets (ARTIS_AMD_SPARSE_MAX; 512 in round 3:
                                       // 4 tiles 3327 / 3205 / 3188 ms at 512 / 4096 / 16384, with parked tails 3222 / 3123 / 2982)
   bool park_tails = true;     // ARTIS_AMD_TILE_PARK=0: every visit of a tile runs its packets to their end (rounds 2-3)
-  // ARTIS_AMD_TILE_PARK_AT: packets left of a larger visit at which it parks them (0 / <= tail_max: round 4's rule, at the tail kernel's
+  // artis_amd_config.tile_park_at: packets left of a larger visit at which it parks them (0 / <= tail_max: round 4's rule, at the tail kernel's
   // threshold). Measured on the headline at a quarter of its cache (4 tiles, adaptive windows; profiles/r06/tiling.md): 4096 / 32768 / 131072 /
   // 524288 / 2097152 -> 2395 / 2147 / 1971 / 1899 / 1868 ms per step (untiled 760); with this round's rows for sets of cells and record tiers (two tiles
   // of rows with a quarter of the levels hot): 131072 / 524288 / 2097152 / 3145728 / 4194304 -> 1550 / 1532 / 1504 (1485 on the box of the last two) / 1448 / 1452 ms;
@@ -2596,7 +2599,26 @@ struct artis_amd_engine {
   ncclComm_t comm = nullptr;  // created by artis_amd_comm_init(), owned by the engine
 };
 
-// The ARTIS_AMD_* switches of the fields above (engine_fill). Order: BUDGET before _R / _T, the vpkt builds' tail_max = 0 after TAIL, SORT_CELLSHIFT after SORT_NUMAJOR.
+// The configuration of an engine, resolved once (engine_config.h resolve_config: struct field, else ARTIS_AMD_* variable, else default) into e->cfg, which
+// the sizing code reads, and into the driver's fields. Called by artis_amd_engine_create_ex before anything is sized; no other place reads these variables.
+static void apply_config(artis_amd_engine *e, const artis_amd_config &checked) {
+  e->cfg = resolve_config(checked);
+  if (e->cfg.tail_given) e->tail_max = e->cfg.tail_threshold;
+  if (ARTIS_OPT_VPKT_ON) e->tail_max = 0;  // (see the estimator block: the event queue is sized per split launch)
+  if (e->cfg.park_given) e->park_at = e->cfg.tile_park_at;
+}
+static void trace_config(const artis_amd_engine *e) {
+  const EngineConfig &c = e->cfg;
+  fprintf(stderr,
+          "[artis_amd] configuration: cache_budget_bytes %.0f (%s), cache_headroom_bytes %.0f (%s), pop_scratch_bytes %.0f (%s), ma_hot_fraction %.3f (%s), "
+          "ma_pool_fraction %.3f (%s), tail_threshold %d (%s), tile_park_at %lld (%s), keep_line_dpop %d (%s)\n",
+          e->cache_budget, c.budget_given ? config_source_name(c.src_budget) : "default: automatic", c.cache_headroom, config_source_name(c.src_headroom),
+          c.pop_scratch, config_source_name(c.src_scratch), e->ma_hotfrac, c.hot_given ? config_source_name(c.src_hot) : "default: automatic", c.ma_pool,
+          config_source_name(c.src_pool), e->tail_max, config_source_name(c.src_tail), (long long)e->park_at, config_source_name(c.src_park),
+          e->Mh.ndpop > 0 ? 1 : 0, c.keep_line_dpop >= 0 ? config_source_name(c.src_dpop) : "default: automatic");
+}
+
+// The experiment switches (ARTIS_AMD_*: kernel forms, sorts, chunking) of the fields above (engine_fill). Order: BUDGET before _R / _T, SORT_CELLSHIFT after SORT_NUMAJOR.
 static void read_switches(artis_amd_engine *e) {
   if (const char *b = std::getenv("ARTIS_AMD_BUDGET")) {  // tuning / tests: launch budgets never change results
     e->budget_r = std::max(1, std::atoi(b));
@@ -2616,9 +2638,7 @@ static void read_switches(artis_amd_engine *e) {
   if (const char *b = std::getenv("ARTIS_AMD_SORT")) e->sort_lists = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_SORT_NU")) e->sort_nu = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_SORT_MA")) e->sort_ma = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TAIL")) e->tail_max = std::max(0, std::atoi(b));
   if (const char *b = std::getenv("ARTIS_AMD_TAIL_ALWAYS")) e->tail_always = std::atoi(b) != 0;
-  if (ARTIS_OPT_VPKT_ON) e->tail_max = 0;  // (see the estimator block: the event queue is sized per split launch)
   if (const char *b = std::getenv("ARTIS_AMD_RPKT_EST_OVER_CONT")) e->rpkt_est_over_cont = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_DENSE_CONTLDS")) e->dense_cont_lds = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_MABINS")) e->ma_bins = (std::atoi(b) > 1) ? SORT_MABINS : 1;
@@ -2648,7 +2668,6 @@ static void read_switches(artis_amd_engine *e) {
   e->trace = std::getenv("ARTIS_AMD_TRACE") != nullptr;
   if (const char *b = std::getenv("ARTIS_AMD_VPKT_CONTLDS")) e->vpkt_cont_lds = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_TILE_PARK")) e->park_tails = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TILE_PARK_AT")) e->park_at = std::max<int64_t>(0, std::atoll(b));
 }
 
 namespace {
@@ -2801,22 +2820,142 @@ int ensure_aos(artis_amd_engine *e, int64_t n) {
 
 namespace {
 int engine_fill(artis_amd_engine *e, const artis_model *model);
-// scratch of the cell-cache population (allocated after the cache rows): ~2 GB, ARTIS_AMD_POP_SCRATCH_MB
-double pop_scratch_mb() {
-  double mb = 2048.;
-  if (const char *b = std::getenv("ARTIS_AMD_POP_SCRATCH_MB")) mb = std::max(1., std::atof(b));
-  return mb;
+
+// ---- sizing: the layout decisions of an engine, as pure functions of the model, the resolved configuration (engine_config.h) and the free device
+// memory. engine_fill() builds what they say; artis_amd_engine_plan() reports it without building anything.
+
+// bytes of one cell's cache row
+size_t cache_row_bytes(const DevModel &h) {
+  size_t per_cell = 0;
+#define SZ(f, T, per) per_cell += sizeof(T) * (size_t)(per);
+  ARTIS_CACHE_ARRAYS(SZ, h)
+#undef SZ
+  return per_cell;
 }
-// Bytes the cell-cache rows may take: 80 % of what is free once the population's scratch and a head-room for everything that is
-// allocated later (ARTIS_AMD_CACHE_HEADROOM_MB, default 0: the packets at ~1 KB each with their work lists, the caller's structs
-// and a snapshot -- 10 GB at 1e7 packets -- fit the remaining fifth of a 288 GB card; a smaller GPU, or two engines on one
-// device, set it) are taken off; ARTIS_AMD_CACHE_BUDGET_MB overrides the lot. One rule for the tile count and for the decision
-// to drop line_dpop.
-double cache_budget_bytes(size_t free_b) {
-  if (const char *b = std::getenv("ARTIS_AMD_CACHE_BUDGET_MB")) return std::atof(b) * 1048576.0;
-  double headroom_mb = 0.;
-  if (const char *b = std::getenv("ARTIS_AMD_CACHE_HEADROOM_MB")) headroom_mb = std::max(0., std::atof(b));
-  return std::max(0., 0.8 * ((double)free_b - (pop_scratch_mb() + headroom_mb) * 1048576.0));
+
+// Macro-atom record tiers (tables.h "ON-DEMAND RECORDS"): every level a static record while the whole cell cache fits one tile; when it
+// does not (even without line_dpop), static records for the lowest share of every ion's levels and a pool of ma_pool_fraction (0.15) of the rest for
+// the cold levels packets reach. A given hot share (artis_amd_config.ma_hot_fraction, ARTIS_AMD_MA_HOTFRAC) is taken as it is; free_b is read only without one.
+// (pool share: 0.25 in round 5. Measured on the 4e5-line set, 50^3 / 1e7, round 6 -- artis_amd_last_pool_usage(): a step leaves 48 % of a quarter-share
+// pool in use; with 0.15 the tier search affords hot 0.25 instead of 0.15 and the step takes 15.9 s instead of 16.6 (pool 64 % used); with 0.10 hot 0.30,
+// 15.7 s, 87 % used -- too close to a pool that is used up and emptied. profiles/r06/pool_share.txt)
+void choose_record_tiers(const artis_model &model, ModelOwned &own, const EngineConfig &cfg, double free_b, DevModel *Mh, double *hotfrac) {
+  const double hot = cfg.hot_given ? cfg.ma_hot : 1., pool = cfg.ma_pool;
+  *Mh = make_host_model_view(model, own, hot, pool);
+  *hotfrac = hot;
+  if (cfg.hot_given) return;
+  auto tiles_needed = [&]() -> int64_t {
+    size_t per_cell = cache_row_bytes(*Mh);
+    per_cell -= sizeof(double) * (size_t)Mh->ndpop;  // (dropped first when the cache does not fit: plan_cache_rows)
+    const int64_t fit = std::max<int64_t>(1, (int64_t)(cache_budget_bytes(cfg, free_b) / (double)(per_cell > 0 ? per_cell : 1)));
+    return (model.npts_nonempty + fit - 1) / fit;
+  };
+  // The largest hot share that lets the whole cache be resident (the fewer cold levels, the fewer first visits pay a fill). If none does, the
+  // cache is tiled, and the share is the largest one that needs the FEWEST tiles: smaller rows, more cells resident at a time (round 6; the headline
+  // forced to a quarter of its cache: 1875 ms with four tiles of static rows, 1532 ms with two tiles of rows with a quarter of the levels hot --
+  // profiles/r06/tiling.md. Round 5 kept the rows static in that case: every refill of a tile emptied the pool then, and a tiled run on on-demand
+  // records paid its fills again and again, 3.7 s against 3.0 s; now a fill leaves the pool and the rows of the cells that stay alone.)
+  // (round 6: in steps of 0.05 below one half -- with the round-5 steps 0.5 / 0.3 / 0.2 / 0.1 a record that grew by a quarter, the fine bytes, sent
+  // the 4e5-line set from 0.2 to 0.1 and doubled its fills)
+  // (the fewest tiles among the shares >= 0.2: a tile saved by going lower costs more in cold levels filled on demand than the tile did -- at 11600 MB
+  // two tiles at hot 0.10 take 1750 ms, three at 0.5 1620; a cache that fits ONE tile at a lower share takes that: one tile beats any tiling)
+  int64_t best_nt = tiles_needed(), tiled_nt = best_nt;
+  double best_h = 1., cur_h = 1., tiled_h = 1.;
+  for (const double h : {0.9, 0.8, 0.7, 0.6, 0.5, 0.45, 0.4, 0.35, 0.3, 0.25, 0.2, 0.15, 0.1, 0.05}) {
+    if (best_nt <= 1) break;
+    *Mh = make_host_model_view(model, own, h, pool);
+    cur_h = h;
+    const int64_t nt = tiles_needed();
+    if (nt < best_nt) {
+      best_nt = nt;
+      best_h = h;
+    }
+    if (h > 0.199 && nt < tiled_nt) {
+      tiled_nt = nt;
+      tiled_h = h;
+    }
+  }
+  if (best_nt > 1) best_h = tiled_h;
+  if (cur_h != best_h) *Mh = make_host_model_view(model, own, best_h, pool);
+  *hotfrac = best_h;
+}
+
+// The rows of the cell cache: all cells if that fits the budget, else one tile of cells at a time. free_b: the free device memory once the model's
+// tables are resident (read by the automatic budget only).
+struct CacheLayout {
+  double budget = 0.;      // [B] what the rows may take
+  size_t per_cell = 0;     // [B] one row
+  int64_t tile_cells = 1;  // rows
+  int ntiles = 1;
+  bool drop_dpop = false;  // the rows are without line_dpop (the caller sets ndpop = 0)
+};
+int plan_cache_rows(const DevModel &h, const EngineConfig &cfg, double free_b, CacheLayout *L) {
+  const int64_t ncell_all = h.npts_nonempty;
+  size_t per_cell = cache_row_bytes(h);
+  const double budget = cache_budget_bytes(cfg, free_b);
+  {
+    // The rows of line_dpop (8 bytes per line and cell: 0.9 of the 3.2 MB of a row with 110 860 lines) are dropped when the cell
+    // cache does not fit one tile with them and needs fewer tiles without: the line walk then forms a line's population factor from
+    // its record and the two level populations (physics.h line_dpop_at: the same expression, the same bits; two more reads per
+    // line visited). artis_amd_config.keep_line_dpop (ARTIS_AMD_DPOP) = 0 / 1 forces either.
+    const size_t per_without = per_cell - (sizeof(double) * (size_t)h.ndpop);
+    auto tiles_of = [&](size_t per) {
+      const int64_t fit = std::max<int64_t>(1, (int64_t)(budget / (double)(per > 0 ? per : 1)));
+      return (ncell_all + fit - 1) / fit;
+    };
+    bool drop = tiles_of(per_cell) > 1 && tiles_of(per_without) < tiles_of(per_cell);
+    if (cfg.keep_line_dpop >= 0) drop = cfg.keep_line_dpop == 0;
+    if (cfg.dpop_strict && h.ndpop > 0 && (double)per_cell > budget) {
+      g_last_error = "artis_amd_config.keep_line_dpop = 1, and the cache budget (" + std::to_string((long long)budget) + " B) cannot hold a row with line_dpop (" +
+                     std::to_string(per_cell) + " B; " + std::to_string(per_without) + " B without)";
+      return ARTIS_ERR_ARG;
+    }
+    L->drop_dpop = drop && h.ndpop > 0;
+    if (L->drop_dpop) per_cell = per_without;
+  }
+  L->budget = budget;
+  L->per_cell = per_cell;
+  const int64_t fit = (int64_t)(budget / (double)(per_cell > 0 ? per_cell : 1));
+  if (fit < 1 && cfg.budget_given && cfg.src_budget == CONFIG_STRUCT) {  // (a budget from the variable or from the automatic rule gets one row at a time, as ever)
+    g_last_error = "artis_amd_config.cache_budget_bytes (" + std::to_string((long long)budget) + ") cannot hold one row of the cell cache (" + std::to_string(per_cell) + " B)";
+    return ARTIS_ERR_ARG;
+  }
+  L->tile_cells = std::max<int64_t>(1, std::min<int64_t>(ncell_all > 0 ? ncell_all : 1, fit));
+  L->ntiles = (int)((ncell_all + L->tile_cells - 1) / L->tile_cells);
+  if (L->ntiles < 1) L->ntiles = 1;
+  if (ARTIS_OPT_VPKT_ON && L->ntiles > 1) {
+    // a virtual packet's ray reads the cache rows of every cell up to the grid's edge (vpkt.cc:183): all of them have to be resident
+    g_last_error = "this build has VPKT_ON and the cell cache does not fit one tile (" + std::to_string(per_cell) + " B per cell x " +
+                   std::to_string((long long)ncell_all) + " cells): virtual packets need every cell's row resident";
+    return ARTIS_ERR_UNSUPPORTED;
+  }
+  return ARTIS_OK;
+}
+
+// the population works through the cells in batches whose cooling terms fit its scratch (artis_amd_config.pop_scratch_bytes: ~2 GB), allocated after the
+// cache rows: cells per batch, and the bytes of the scratch
+int64_t pop_batch_cells(const DevModel &h, int64_t tile_cells, const EngineConfig &cfg) {
+  const int64_t per = std::max<int64_t>(1, (int64_t)h.nupcum) * (int64_t)sizeof(double);
+  return std::max<int64_t>(1, std::min<int64_t>(tile_cells, (int64_t)cfg.pop_scratch / per));
+}
+size_t pop_scratch_alloc_bytes(const DevModel &h, int64_t batch) {
+  return (size_t)(batch * std::max<int64_t>(1, (int64_t)h.nupcum) * (int64_t)sizeof(double)) + 64;
+}
+
+// bytes of the model's tables on the device (what engine_fill uploads before it sizes the cache: upload_array's sizes)
+int64_t model_table_bytes(const DevModel &h) {
+  int64_t bytes = 0;
+#define SZ(f, T, count) bytes += (int64_t)sizeof(T) * std::max<int64_t>(1, (int64_t)(count));
+  ARTIS_MODEL_ARRAYS(SZ, h)
+#undef SZ
+#define SZO(f, T, count) \
+  if (h.f) bytes += (int64_t)sizeof(T) * std::max<int64_t>(1, (int64_t)(count));
+  ARTIS_MODEL_OPTIONAL_ARRAYS(SZO, h)
+#undef SZO
+  const int ndim = (h.gridtype == ARTIS_GRID_SPHERICAL1D) ? 1 : ((h.gridtype == ARTIS_GRID_CYLINDRICAL2D) ? 2 : 3);
+  for (int a = 0; a < 3; a++) bytes += (int64_t)sizeof(double) * std::max<int64_t>(1, (a >= ndim) ? 1 : h.ncoordgrid[a]);
+  bytes += (int64_t)sizeof(int32_t) * std::max<int64_t>(1, h.nphixstargets_total);  // the target -> level table
+  return bytes;
 }
 
 // RCCL entry points, resolved at run time from the librccl the process already has (a host that links RCCL itself, or
@@ -2911,11 +3050,11 @@ const char *artis_amd_options_preset(void) {
 }
 size_t artis_amd_sizeof_packet(void) { return sizeof(artis_packet); }
 
-int artis_amd_engine_create(const artis_model *model, int device, artis_amd_engine **out) {
-  if (!model || !out) {
-    g_last_error = "null argument";
-    return ARTIS_ERR_ARG;
-  }
+}  // extern "C"
+
+namespace {
+// what the engine requires of a model before anything is sized or uploaded (artis_amd_engine_create_ex, artis_amd_engine_plan)
+int validate_model(const artis_model *model) {
   if (model->gridtype != ARTIS_GRID_CARTESIAN3D && model->gridtype != ARTIS_GRID_SPHERICAL1D &&
       model->gridtype != ARTIS_GRID_CYLINDRICAL2D) {
     g_last_error = "unknown grid type";
@@ -2991,6 +3130,31 @@ int artis_amd_engine_create(const artis_model *model, int device, artis_amd_engi
       return ARTIS_ERR_UNSUPPORTED;
     }
   }
+  return ARTIS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+size_t artis_amd_sizeof_config(void) { return sizeof(artis_amd_config); }
+size_t artis_amd_sizeof_plan(void) { return sizeof(artis_amd_plan); }
+void artis_amd_config_default(artis_amd_config *cfg) {
+  if (cfg) config_set_default(cfg);
+}
+
+int artis_amd_engine_create(const artis_model *model, int device, artis_amd_engine **out) {
+  return artis_amd_engine_create_ex(model, device, nullptr, out);
+}
+
+int artis_amd_engine_create_ex(const artis_model *model, int device, const artis_amd_config *cfg, artis_amd_engine **out) {
+  if (out) *out = nullptr;
+  if (!model || !out) {
+    g_last_error = "null argument";
+    return ARTIS_ERR_ARG;
+  }
+  artis_amd_config checked;  // the configuration first: a caller's mistake is reported before the device is touched
+  if (const int rc = config_copy_checked(cfg, &checked, &g_last_error)) return rc;
+  if (const int rc = validate_model(model)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     g_last_error = "no HIP device: the artis_amd engine has no CPU path";
@@ -2999,6 +3163,7 @@ int artis_amd_engine_create(const artis_model *model, int device, artis_amd_engi
   HIP_TRY(hipSetDevice(device));
   artis_amd_engine *e = new artis_amd_engine();
   e->device = device;
+  apply_config(e, checked);
   const int rc = engine_fill(e, model);
   if (rc != ARTIS_OK) {  // release whatever was allocated before the failing call (g_last_error is already set)
     artis_amd_engine_destroy(e);
@@ -3013,59 +3178,14 @@ int artis_amd_engine_create(const artis_model *model, int device, artis_amd_engi
 namespace {
 int engine_fill(artis_amd_engine *e, const artis_model *model) {
   const int device = e->device;
-  {
-    // Macro-atom record tiers (tables.h "ON-DEMAND RECORDS"): every level a static record while the whole cell cache fits one tile; when it
-    // does not (even without line_dpop), static records for the lowest ARTIS_AMD_MA_HOTFRAC (0.3) of every ion's levels and a pool of
-    // ARTIS_AMD_MA_POOLFRAC (0.15) of the rest for the cold levels packets reach. Either variable set: taken as given.
-    // (pool share: 0.25 in round 5. Measured on the 4e5-line set, 50^3 / 1e7, round 6 -- artis_amd_last_pool_usage(): a step leaves 48 % of a quarter-share
-    // pool in use; with 0.15 the tier search affords hot 0.25 instead of 0.15 and the step takes 15.9 s instead of 16.6 (pool 64 % used); with 0.10 hot 0.30,
-    // 15.7 s, 87 % used -- too close to a pool that is used up and emptied. profiles/r06/pool_share.txt)
-    double hot = 1., pool = 0.15;
-    const bool given = std::getenv("ARTIS_AMD_MA_HOTFRAC") != nullptr;
-    ma_tiers_from_env(&hot, &pool);
-    e->Mh = make_host_model_view(*model, e->own, hot, pool);
-    e->ma_hotfrac = hot;
-    if (!given) {
-      size_t free_b = 0, total_b = 0;
-      HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-      auto tiles_needed = [&]() -> int64_t {
-        size_t per_cell = 0;
-#define SZ(f, T, per) per_cell += sizeof(T) * (size_t)(per);
-        ARTIS_CACHE_ARRAYS(SZ, e->Mh)
-#undef SZ
-        per_cell -= sizeof(double) * (size_t)e->Mh.ndpop;  // (dropped first when the cache does not fit: below)
-        const int64_t fit = std::max<int64_t>(1, (int64_t)(cache_budget_bytes(free_b) / (double)(per_cell > 0 ? per_cell : 1)));
-        return (model->npts_nonempty + fit - 1) / fit;
-      };
-      // The largest hot share that lets the whole cache be resident (the fewer cold levels, the fewer first visits pay a fill). If none does, the
-      // cache is tiled, and the share is the largest one that needs the FEWEST tiles: smaller rows, more cells resident at a time (round 6; the headline
-      // forced to a quarter of its cache: 1875 ms with four tiles of static rows, 1532 ms with two tiles of rows with a quarter of the levels hot --
-      // profiles/r06/tiling.md. Round 5 kept the rows static in that case: every refill of a tile emptied the pool then, and a tiled run on on-demand
-      // records paid its fills again and again, 3.7 s against 3.0 s; now a fill leaves the pool and the rows of the cells that stay alone.)
-      // (round 6: in steps of 0.05 below one half -- with the round-5 steps 0.5 / 0.3 / 0.2 / 0.1 a record that grew by a quarter, the fine bytes, sent
-      // the 4e5-line set from 0.2 to 0.1 and doubled its fills)
-      // (the fewest tiles among the shares >= 0.2: a tile saved by going lower costs more in cold levels filled on demand than the tile did -- at 11600 MB
-      // two tiles at hot 0.10 take 1750 ms, three at 0.5 1620; a cache that fits ONE tile at a lower share takes that: one tile beats any tiling)
-      int64_t best_nt = tiles_needed(), tiled_nt = best_nt;
-      double best_h = 1., cur_h = 1., tiled_h = 1.;
-      for (const double h : {0.9, 0.8, 0.7, 0.6, 0.5, 0.45, 0.4, 0.35, 0.3, 0.25, 0.2, 0.15, 0.1, 0.05}) {
-        if (best_nt <= 1) break;
-        e->Mh = make_host_model_view(*model, e->own, h, pool);
-        cur_h = h;
-        const int64_t nt = tiles_needed();
-        if (nt < best_nt) {
-          best_nt = nt;
-          best_h = h;
-        }
-        if (h > 0.199 && nt < tiled_nt) {
-          tiled_nt = nt;
-          tiled_h = h;
-        }
-      }
-      if (best_nt > 1) best_h = tiled_h;
-      if (cur_h != best_h) e->Mh = make_host_model_view(*model, e->own, best_h, pool);
-      e->ma_hotfrac = best_h;
+  {  // macro-atom record tiers (choose_record_tiers): given, or chosen from the cache budget -- then from what is free on the device now
+    double free_b = 0.;
+    if (!e->cfg.hot_given) {
+      size_t f = 0, total_b = 0;
+      HIP_TRY(hipMemGetInfo(&f, &total_b));
+      free_b = (double)f;
     }
+    choose_record_tiers(*model, e->own, e->cfg, free_b, &e->Mh, &e->ma_hotfrac);
   }
   e->model_copy = *model;
   e->own_matransblock_start.assign(model->level_matransblock_start, model->level_matransblock_start + model->nlevels);
@@ -3131,48 +3251,23 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
     if (rc != ARTIS_OK) return rc;
     e->d_target_level = (int32_t *)d;
   }
-  // per-cell cache: all cells if that fits the budget, else one tile of cells at a time
+  // per-cell cache: all cells if that fits the budget, else one tile of cells at a time (plan_cache_rows)
   const int64_t ncell_all = h.npts_nonempty;
   {
-    size_t per_cell = 0;
-#define SZ(f, T, per) per_cell += sizeof(T) * (size_t)(per);
-    ARTIS_CACHE_ARRAYS(SZ, h)
-#undef SZ
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    {
-      // The rows of line_dpop (8 bytes per line and cell: 0.9 of the 3.2 MB of a row with 110 860 lines) are dropped when the cell
-      // cache does not fit one tile with them and needs fewer tiles without: the line walk then forms a line's population factor from
-      // its record and the two level populations (physics.h line_dpop_at: the same expression, the same bits; two more reads per
-      // line visited). ARTIS_AMD_DPOP=0 / 1 forces either.
-      double budget0 = cache_budget_bytes(free_b);
-      const size_t per_without = per_cell - (sizeof(double) * (size_t)h.ndpop);
-      auto tiles_of = [&](size_t per) {
-        const int64_t fit = std::max<int64_t>(1, (int64_t)(budget0 / (double)(per > 0 ? per : 1)));
-        return (ncell_all + fit - 1) / fit;
-      };
-      bool drop = tiles_of(per_cell) > 1 && tiles_of(per_without) < tiles_of(per_cell);
-      if (const char *b = std::getenv("ARTIS_AMD_DPOP")) drop = std::atoi(b) == 0;
-      if (drop && h.ndpop > 0) {
-        e->Mh.ndpop = 0;
-        e->M.ndpop = 0;
-        per_cell = per_without;
-      }
+    CacheLayout L;
+    if (const int rc = plan_cache_rows(h, e->cfg, (double)free_b, &L)) return rc;
+    if (L.drop_dpop) {
+      e->Mh.ndpop = 0;
+      e->M.ndpop = 0;
     }
-    e->cache_bytes_per_cell = per_cell;
-    double budget = cache_budget_bytes(free_b);
-    int64_t fit = (int64_t)(budget / (double)(per_cell > 0 ? per_cell : 1));
-    e->tile_cells = std::max<int64_t>(1, std::min<int64_t>(ncell_all > 0 ? ncell_all : 1, fit));
-    e->ntiles = (int)((ncell_all + e->tile_cells - 1) / e->tile_cells);
-    if (e->ntiles < 1) e->ntiles = 1;
+    e->cache_budget = L.budget;
+    e->cache_bytes_per_cell = L.per_cell;
+    e->tile_cells = L.tile_cells;
+    e->ntiles = L.ntiles;
     e->tile_lo = 0;
     e->tile_hi = (int)std::min<int64_t>(ncell_all, e->tile_cells);
-    if (ARTIS_OPT_VPKT_ON && e->ntiles > 1) {
-      // a virtual packet's ray reads the cache rows of every cell up to the grid's edge (vpkt.cc:183): all of them have to be resident
-      g_last_error = "this build has VPKT_ON and the cell cache does not fit one tile (" + std::to_string(per_cell) + " B per cell x " +
-                     std::to_string((long long)ncell_all) + " cells): virtual packets need every cell's row resident";
-      return ARTIS_ERR_UNSUPPORTED;
-    }
   }
   const int64_t nrows = e->tile_cells;  // rows allocated
 #define CA(f, T, per)                                                                       \
@@ -3281,12 +3376,11 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
     HIP_TRY(hipDeviceSynchronize());
   }
   {
-    // the population works through the cells in batches whose cooling terms fit a scratch of ~2 GB (ARTIS_AMD_POP_SCRATCH_MB)
-    const double mb = pop_scratch_mb();
-    const int64_t per = std::max<int64_t>(1, (int64_t)e->Mh.nupcum) * (int64_t)sizeof(double);
-    e->pop_batch = std::max<int64_t>(1, std::min<int64_t>(e->tile_cells, (int64_t)(mb * 1048576.) / per));
-    HIP_TRY(hipMalloc((void **)&e->d_collexc_terms, (size_t)(e->pop_batch * per) + 64));
+    // the population works through the cells in batches whose cooling terms fit its scratch (pop_batch_cells)
+    e->pop_batch = pop_batch_cells(e->Mh, e->tile_cells, e->cfg);
+    HIP_TRY(hipMalloc((void **)&e->d_collexc_terms, pop_scratch_alloc_bytes(e->Mh, e->pop_batch)));
   }
+  if (e->trace) trace_config(e);
   if (e->trace)
     fprintf(stderr, "[artis_amd] record tiers: static records for %.2f of every ion's levels, %d cold levels, pool of %d slots per resident cell; %d tile(s) of %lld cells, %zu B per cell\n",
             e->ma_hotfrac, e->Mh.ncold, e->Mh.ma_pool_slots, e->ntiles, (long long)e->tile_cells, e->cache_bytes_per_cell);
@@ -3668,6 +3762,86 @@ int artis_amd_cache_tiles(artis_amd_engine *e, int32_t *ntiles, int64_t *cells_p
   if (ntiles) *ntiles = e->ntiles;
   if (cells_per_tile) *cells_per_tile = e->tile_cells;
   if (bytes_per_cell) *bytes_per_cell = (int64_t)e->cache_bytes_per_cell;
+  return ARTIS_OK;
+}
+
+int artis_amd_engine_config(artis_amd_engine *e, artis_amd_config *effective) {
+  if (!e || !effective) {
+    g_last_error = "null argument";
+    return ARTIS_ERR_ARG;
+  }
+  const size_t n = effective->struct_size;
+  if (n > sizeof(artis_amd_config) || n < sizeof(size_t)) {
+    g_last_error = "artis_amd_config.struct_size is not one this library knows: artis_amd_config_default() fills it in";
+    return ARTIS_ERR_ARG;
+  }
+  artis_amd_config c;
+  config_set_default(&c);
+  c.struct_size = n;
+  c.cache_budget_bytes = (int64_t)e->cache_budget;
+  c.cache_headroom_bytes = (int64_t)e->cfg.cache_headroom;
+  c.pop_scratch_bytes = (int64_t)e->cfg.pop_scratch;
+  c.ma_hot_fraction = e->ma_hotfrac;
+  c.ma_pool_fraction = e->cfg.ma_pool;
+  c.tail_threshold = e->tail_max;
+  c.tile_park_at = e->park_at;
+  c.keep_line_dpop = e->Mh.ndpop > 0 ? 1 : 0;
+  std::memcpy(effective, &c, n);
+  return ARTIS_OK;
+}
+
+int artis_amd_engine_plan(const artis_model *model, int device, const artis_amd_config *cfg, int64_t free_bytes, artis_amd_plan *plan) {
+  if (!model || !plan || free_bytes < 0) {
+    g_last_error = !model || !plan ? "null argument" : "free_bytes is negative (0: ask the device)";
+    return ARTIS_ERR_ARG;
+  }
+  const size_t n = plan->struct_size;
+  if (n > sizeof(artis_amd_plan) || n < sizeof(size_t)) {
+    g_last_error = "artis_amd_plan.struct_size is not one this library knows: set it to sizeof(artis_amd_plan)";
+    return ARTIS_ERR_ARG;
+  }
+  artis_amd_config checked;
+  if (const int rc = config_copy_checked(cfg, &checked, &g_last_error)) return rc;
+  if (const int rc = validate_model(model)) return rc;
+  const EngineConfig rcfg = resolve_config(checked);
+  double free_b = (double)free_bytes;
+  if (free_bytes == 0) {  // what a creation would find free at this moment
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+      g_last_error = "no HIP device: artis_amd_engine_plan() needs one to ask for the free memory (free_bytes = 0)";
+      return ARTIS_ERR_NODEVICE;
+    }
+    HIP_TRY(hipSetDevice(device));
+    size_t f = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&f, &total_b));
+    free_b = (double)f;
+  }
+  ModelOwned own;
+  DevModel h;
+  double hot = 1.;
+  choose_record_tiers(*model, own, rcfg, free_b, &h, &hot);
+  const int64_t model_bytes = model_table_bytes(h);
+  CacheLayout L;
+  if (const int rc = plan_cache_rows(h, rcfg, std::max(0., free_b - (double)model_bytes), &L)) return rc;
+  if (L.drop_dpop) h.ndpop = 0;
+  artis_amd_plan p;
+  std::memset(&p, 0, sizeof(p));
+  p.struct_size = n;
+  p.bytes_per_cell = (int64_t)L.per_cell;
+  p.cells_resident = L.tile_cells;
+  p.ntiles = L.ntiles;
+  p.ncold_levels = h.ncold;
+  p.hot_fraction = hot;
+  p.pool_slots = h.ma_pool_slots;
+#define SZ(f, T, per) p.cache_bytes += (int64_t)sizeof(T) * (L.tile_cells * (int64_t)(per) + MAREC_SLACK);
+  ARTIS_CACHE_ARRAYS(SZ, h)
+#undef SZ
+  p.pool_bytes = (int64_t)sizeof(U4) * (L.tile_cells * (int64_t)h.ma_pool_slots + MAREC_SLACK);
+  p.pop_scratch_bytes = (int64_t)pop_scratch_alloc_bytes(h, pop_batch_cells(h, L.tile_cells, rcfg));
+  p.model_bytes = model_bytes;
+  p.free_bytes_assumed = (int64_t)free_b;
+  p.line_dpop_kept = h.ndpop > 0 ? 1 : 0;
+  std::memcpy(plan, &p, n);
   return ARTIS_OK;
 }
 

@@ -188,14 +188,17 @@ struct ModelOwned {
   X(chi_ff_nnionpart, double, 1)
 
 // Host view of the model: pointers into the caller's arrays plus the derived tables in `own`.
-// The macro-atom record tiers (tables.h "ON-DEMAND RECORDS"): ARTIS_AMD_MA_HOTFRAC = share of every ion's levels (the lowest ones) with a
-// static record in every cell's row, ARTIS_AMD_MA_POOLFRAC = the pool (shared by the resident cells) as a share of what the cold levels'
-// records of all of them would take.
-// Unset: hot 1 (everything static); the engine sets them itself when the whole cache does not fit one tile.
+// The macro-atom record tiers (tables.h "ON-DEMAND RECORDS"): hotfrac = share of every ion's levels (the lowest ones) with a static record in every
+// cell's row, poolfrac = the pool (shared by the resident cells) as a share of what the cold levels' records of all of them would take. The engine
+// passes what its configuration resolved to (engine_config.h: artis_amd_config.ma_hot_fraction / ma_pool_fraction, else ARTIS_AMD_MA_HOTFRAC /
+// _POOLFRAC, else hot 1 -- everything static -- or, when the whole cache does not fit one tile, its own choice).
+#ifdef ARTIS_HOST_EMU
+// (the host-emulation test build has no engine and no configuration: it reads the two variables here)
 inline void ma_tiers_from_env(double *hotfrac, double *poolfrac) {
   if (const char *b = std::getenv("ARTIS_AMD_MA_HOTFRAC")) *hotfrac = std::min(1., std::max(0., std::atof(b)));
   if (const char *b = std::getenv("ARTIS_AMD_MA_POOLFRAC")) *poolfrac = std::min(1., std::max(0., std::atof(b)));
 }
+#endif
 inline DevModel make_host_model_view(const artis_model &m, ModelOwned &own, double hotfrac = 1., double poolfrac = 0.25) {
   DevModel v;
   std::memset(&v, 0, sizeof(v));

@@ -40,6 +40,13 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_abi_version.restype = C.c_int
     L.artis_amd_sizeof_packet.restype = C.c_size_t
     L.artis_amd_engine_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.artis_amd_engine_create_ex.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.Config), C.POINTER(C.c_void_p)]
+    L.artis_amd_engine_config.argtypes = [C.c_void_p, C.POINTER(abi.Config)]
+    L.artis_amd_engine_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.Config), C.c_int64, C.POINTER(abi.Plan)]
+    L.artis_amd_config_default.argtypes = [C.POINTER(abi.Config)]
+    L.artis_amd_config_default.restype = None
+    L.artis_amd_sizeof_config.restype = C.c_size_t
+    L.artis_amd_sizeof_plan.restype = C.c_size_t
     L.artis_amd_engine_destroy.argtypes = [C.c_void_p]
     L.artis_amd_engine_destroy.restype = None
     L.artis_amd_set_cellstate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -64,6 +71,7 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
+    assert L.artis_amd_sizeof_config() == C.sizeof(abi.Config) and L.artis_amd_sizeof_plan() == C.sizeof(abi.Plan)
     L.artis_amd_options_preset.restype = C.c_char_p
     assert L.artis_amd_options_preset().decode() == preset, (L.artis_amd_options_preset(), preset)
     _LIBS[preset] = L
@@ -86,15 +94,39 @@ EXPORTED_SYMBOLS = [
     "artis_amd_spectra_compute", "artis_amd_spectra_devptr", "artis_amd_spectra_download",
     "artis_amd_radfield_fit", "artis_amd_radfield_download",
     "artis_amd_grid_update", "artis_amd_grid_update_download",
+    "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
+    "artis_amd_sizeof_plan", "artis_amd_engine_plan",
 ]
 
 
+def _as_config(config) -> abi.Config:
+    """an abi.Config, or a dict of its fields (the others at "automatic / default")"""
+    return config if isinstance(config, abi.Config) else abi.config(**config)
+
+
+def plan(model: abi.Model, config=None, device: int = 0, preset: str = "classic", free_bytes: int = 0) -> dict:
+    """The layout Engine(model, device, preset, config) would choose, without building it (artis_amd_engine_plan): a dict over the fields of
+    artis_amd_plan. free_bytes = 0 asks the device for its free memory; a value given is taken instead and no device is needed."""
+    L = load_library(preset=preset)
+    out = abi.Plan(struct_size=C.sizeof(abi.Plan))
+    cfg = C.byref(_as_config(config)) if config is not None else None
+    rc = L.artis_amd_engine_plan(C.cast(model.ref(), C.c_void_p), device, cfg, int(free_bytes), C.byref(out))
+    if rc != 0:
+        raise EngineError(f"artis_amd error {rc}: {L.artis_amd_last_error().decode()}")
+    return abi.struct_dict(out)
+
+
 class Engine:
-    def __init__(self, model: abi.Model, device: int = 0, preset: str = "classic"):
+    def __init__(self, model: abi.Model, device: int = 0, preset: str = "classic", config=None):
+        """config: an abi.Config (abi.config(...)) or a dict of its fields -- how the engine uses its device (include/artis_amd.h
+        artis_amd_config: a field set there wins over its ARTIS_AMD_* variable); None: artis_amd_engine_create, the variables and defaults."""
         self.L = load_library(preset=preset)
         self.model = model
         self.h = C.c_void_p()
-        self._check(self.L.artis_amd_engine_create(C.cast(model.ref(), C.c_void_p), device, C.byref(self.h)))
+        if config is None:
+            self._check(self.L.artis_amd_engine_create(C.cast(model.ref(), C.c_void_p), device, C.byref(self.h)))
+        else:
+            self._check(self.L.artis_amd_engine_create_ex(C.cast(model.ref(), C.c_void_p), device, C.byref(_as_config(config)), C.byref(self.h)))
 
     def _check(self, rc: int):
         if rc != 0:
@@ -281,6 +313,12 @@ class Engine:
         self._check(self.L.artis_amd_debug_cellcache(*args))
         out["chi_ff_nnionpart"] = chi.value
         return out
+
+    def config(self) -> dict:
+        """the configuration the engine runs with, every "automatic" resolved (artis_amd_engine_config): a dict over artis_amd_config's fields"""
+        out = abi.config()
+        self._check(self.L.artis_amd_engine_config(self.h, C.byref(out)))
+        return abi.struct_dict(out)
 
     def cache_tiles(self):
         """(number of cell-cache tiles, cells per tile, cache bytes per cell)"""

@@ -479,7 +479,11 @@ typedef struct artis_amd_engine artis_amd_engine;
 #define ARTIS_ERR_RCCL (-6)
 
 const char *artis_amd_last_error(void);
-int artis_amd_abi_version(void); /* 6: artis_amd_record_tiers() added (no struct changed); 5: virtual-packet configuration and spectra appended; 4: artis_cellstate.elem_meanweight appended (3: cell state and estimators of the nltenebular options) */
+/* 6 -- and it stays 6 with the engine configuration (artis_amd_config, artis_amd_plan and their four functions below): functions were added,
+ * no existing struct or function changed, so a caller built against the earlier header of version 6 runs unchanged.
+ * 6: artis_amd_record_tiers() added (no struct changed); 5: virtual-packet configuration and spectra appended;
+ * 4: artis_cellstate.elem_meanweight appended (3: cell state and estimators of the nltenebular options) */
+int artis_amd_abi_version(void);
 /* Name of the options preset the library was compiled with (include/artis_options.h): "classic" or "kilonova_lte".
  * Like the reference, one binary per artisoptions.h. */
 const char *artis_amd_options_preset(void);
@@ -487,8 +491,74 @@ size_t artis_amd_sizeof_packet(void);
 
 /* Create an engine on HIP device `device` and upload the static model.
  * Replaces the table set-up the reference's GPU build leaves in unified memory
- * (MPI_shared_array, mpi_logging.h). */
+ * (MPI_shared_array, mpi_logging.h). The same as artis_amd_engine_create_ex() with a default configuration. */
 int artis_amd_engine_create(const artis_model *model, int device, artis_amd_engine **out);
+
+/* ---- engine configuration ----------------------------------------------------
+ * How an engine uses its device: what input.txt and artisoptions.h are to the reference (input.cc:1862, constants.h:105-107), stated by the host
+ * per engine instead of per process. PRECEDENCE, for every field: a value set here wins; a field left at its "automatic / default" value takes
+ * the ARTIS_AMD_* variable named with it if that is set; otherwise the built-in default. None of it changes a packet history: the fields
+ * place work and memory, never physics.
+ * The kernel forms, sorts and chunkings that the other ARTIS_AMD_* variables select are experiment switches and stay variables. */
+typedef struct artis_amd_config {
+  size_t  struct_size;          /* sizeof(artis_amd_config) of the caller. Larger than the library's: refused. Smaller (an older caller): accepted,
+                                   the fields beyond it take their defaults */
+  int64_t cache_budget_bytes;   /* bytes the cell-cache rows may take; 0 = automatic: 80 % of the free device memory at creation less the
+                                   population scratch and the head-room (ARTIS_AMD_CACHE_BUDGET_MB). Set: the layout no longer depends on what
+                                   else is on the device. It must hold one row */
+  int64_t cache_headroom_bytes; /* taken off the free memory before the automatic rule: what is allocated later (packets, a second engine);
+                                   -1 = default, 0 (ARTIS_AMD_CACHE_HEADROOM_MB) */
+  int64_t pop_scratch_bytes;    /* scratch of the cell-cache population; -1 = default, 2 GB (ARTIS_AMD_POP_SCRATCH_MB) */
+  double  ma_hot_fraction;      /* share of every ion's levels (the lowest ones) with a static macro-atom record in every row, in (0, 1];
+                                   < 0 = automatic: 1 when the cache fits, else the share that needs the fewest tiles (ARTIS_AMD_MA_HOTFRAC) */
+  double  ma_pool_fraction;     /* the shared pool of on-demand records as a share of what all cold levels' records would take, >= 0 (above 1
+                                   counts as 1); -1 = default, 0.15 (ARTIS_AMD_MA_POOLFRAC) */
+  int64_t tail_threshold;       /* packets left at which the tail kernel takes over; 0 = never; -1 = default, 4096 (16384 in builds with
+                                   detailed bound-free estimators) (ARTIS_AMD_TAIL). VPKT_ON builds never use the tail kernel: always 0 */
+  int64_t tile_park_at;         /* tiled cache: packets left of a larger visit at which the visit parks them for the tile's next visit;
+                                   -1 = default, 3145728 (ARTIS_AMD_TILE_PARK_AT) */
+  int32_t keep_line_dpop;       /* the rows' per-line population factors: -1 = automatic (dropped when the cache does not fit one tile with them
+                                   and needs fewer without), 0 = drop them, 1 = keep them, or fail if the budget cannot hold a row that has
+                                   them (ARTIS_AMD_DPOP) */
+  int32_t reserved;             /* must be 0 */
+} artis_amd_config;
+size_t artis_amd_sizeof_config(void);
+/* Every field "automatic / default", struct_size filled in. */
+void artis_amd_config_default(artis_amd_config *cfg);
+/* artis_amd_engine_create() with a configuration (NULL: the default one). The configuration is checked before the device is touched:
+ * ARTIS_ERR_ARG for a struct_size larger than the library's, reserved != 0, a hot fraction of 0 or above 1, a negative pool fraction other
+ * than -1, any other negative value that is not the field's default, a cache_budget_bytes that cannot hold one row, keep_line_dpop == 1
+ * with a budget that cannot hold a row with line_dpop; ARTIS_ERR_UNSUPPORTED for a VPKT_ON build whose cache would be tiled. On any
+ * failure *out is NULL and nothing stays allocated. */
+int artis_amd_engine_create_ex(const artis_model *model, int device, const artis_amd_config *cfg, artis_amd_engine **out);
+/* The values the engine runs with, every "automatic" resolved: the budget the rows were sized by, the hot and pool shares of
+ * artis_amd_record_tiers(), keep_line_dpop 0 or 1, ... effective->struct_size is the caller's (artis_amd_config_default() fills it in). */
+int artis_amd_engine_config(artis_amd_engine *eng, artis_amd_config *effective);
+
+/* The layout artis_amd_engine_create_ex() would choose for this model and configuration, without building it: the same sizing code, no
+ * cache, pool or scratch allocated, nothing uploaded. free_bytes = 0 asks the device (hipMemGetInfo) and is what creation would see at
+ * this moment; free_bytes > 0 is taken instead and the device is not touched. With cache_budget_bytes set and free_bytes given the plan is a
+ * pure function of the model and the configuration: a layout that can be reproduced on a shared device. An engine created from the same
+ * configuration right afterwards reports the same numbers through artis_amd_cache_tiles(), artis_amd_record_tiers() and
+ * artis_amd_engine_config(). (Under the automatic budget the plan takes the model's arrays off the free memory as the sum of their sizes;
+ * creation measures again after uploading them, allocation granularity included.) Errors as artis_amd_engine_create_ex(). */
+typedef struct artis_amd_plan {
+  size_t  struct_size;         /* sizeof(artis_amd_plan) of the caller, set before the call (rule as artis_amd_config.struct_size) */
+  int64_t bytes_per_cell;      /* cache row */
+  int64_t cells_resident;      /* rows per tile */
+  int32_t ntiles;
+  int32_t ncold_levels;
+  double  hot_fraction;
+  int64_t pool_slots;          /* 16-byte slots of the shared pool per resident cell */
+  int64_t cache_bytes, pool_bytes, pop_scratch_bytes, model_bytes; /* what creation would allocate: all rows (the pool's part of them),
+                                                                      the population scratch, the model's tables */
+  int64_t free_bytes_assumed;  /* the free memory the automatic rules used: hipMemGetInfo, or the caller's */
+  int32_t line_dpop_kept;
+  int32_t reserved;
+} artis_amd_plan;
+size_t artis_amd_sizeof_plan(void);
+int artis_amd_engine_plan(const artis_model *model, int device, const artis_amd_config *cfg, int64_t free_bytes, artis_amd_plan *plan);
+
 void artis_amd_engine_destroy(artis_amd_engine *eng);
 
 /* Upload the cell state of the coming timestep and fill every cell's cache:
@@ -501,8 +571,8 @@ int artis_amd_set_cellstate(artis_amd_engine *eng, const artis_cellstate *cells,
  * reference does at its start, update_packets.cc:551-560). hip_stream is a hipStream_t (NULL = default). */
 int artis_amd_populate_cellcache(artis_amd_engine *eng, void *hip_stream);
 
-/* Cell-cache tiling. The cache of every non-empty cell is resident when it fits the budget (60 % of the free HBM at
- * engine creation, or ARTIS_AMD_CACHE_BUDGET_MB); otherwise there are rows for `*cells_per_tile` cells at a time
+/* Cell-cache tiling. The cache of every non-empty cell is resident when it fits the budget (artis_amd_config.cache_budget_bytes, or
+ * 80 % of the free HBM at engine creation less scratch and head-room); otherwise there are rows for `*cells_per_tile` cells at a time
  * (`*ntiles` = how many such sets cover the model) and artis_amd_update_packets*() visits sets of cells (make the cells in
  * which most packets wait resident -- cells that are resident already keep their rows --, advance the packets that sit in
  * them until they leave the set or are done, next set, ... until no packet is left): the reference's single-slot cell cache
@@ -568,8 +638,8 @@ int artis_amd_last_tiling_parked(artis_amd_engine *eng, int64_t *parked);
  * artis_amd_update_packets_device call found the shared pool of the other levels' records used up and emptied it (the records are filled again
  * when next needed: it costs fills, never an answer; the reference, which fills a level's rates on first use too, keeps them all: macroatom.cc:398-417) */
 int artis_amd_last_pool_resets(artis_amd_engine *eng, int64_t *resets);
-/* Which record tiers the engine keeps for this model (chosen at artis_amd_engine_create from the cache budget -- free device memory at that
- * moment or ARTIS_AMD_CACHE_BUDGET_MB -- unless ARTIS_AMD_MA_HOTFRAC gives them): the share of every ion's levels with a static record in every
+/* Which record tiers the engine keeps for this model (chosen at creation from the cache budget -- artis_amd_config.cache_budget_bytes or the free device
+ * memory at that moment -- unless artis_amd_config.ma_hot_fraction gives them): the share of every ion's levels with a static record in every
  * cell's row (1 = all of them: no on-demand records), the number of cold levels, and the 16-byte slots of the shared pool per resident cell.
  * Two runs are comparable in time and in artis_amd_last_pool_resets() only if these agree. Any pointer may be NULL. (ABI 6) */
 int artis_amd_record_tiers(artis_amd_engine *eng, double *hot_fraction, int32_t *ncold_levels, int64_t *pool_slots);
@@ -582,7 +652,7 @@ int artis_amd_last_pool_usage(artis_amd_engine *eng, int64_t *units_used, int64_
  * form it means to check is the one that ran. (ABI 6) */
 #define ARTIS_AMD_THERMAL_PLAIN 1         /* k_thermal<256, 0>: target tables in HBM (any size; lists below 4096 entries) */
 #define ARTIS_AMD_THERMAL_LDS_TABLES 2    /* k_thermal<1024, 1>: target levels + LevelPack in LDS (<= 2048 levels, <= 32768 transitions) */
-#define ARTIS_AMD_THERMAL_LDS_LEVELPACK 4 /* k_thermal<1024, 2>: LevelPack alone in LDS (<= 6144 levels) */
+#define ARTIS_AMD_THERMAL_LDS_LEVELPACK 4 /* k_thermal<1024, 2>: LevelPack alone in LDS (<= 9856 levels; not used while the per-cell LDS estimator arrays are active) */
 #define ARTIS_AMD_THERMAL_REFILL 8        /* k_thermal_q (ARTIS_AMD_REFILL=1) */
 #define ARTIS_AMD_THERMAL_COLD 16         /* ... instantiated with the on-demand records' look-ups (the model has cold levels) */
 #define ARTIS_AMD_THERMAL_TAIL 32         /* k_tail took the population's last packets */
