@@ -873,10 +873,7 @@ __global__ void __launch_bounds__(BLOCK) k_aos_cellkeys(const artis_packet *aos,
 }
 
 // append (pi, key) of every lane with flag set to list[] / keys[], one atomic per wave (wave-ballot compaction)
-// (Round 6, measured and removed: the list's key histogram kept HERE -- one fire-and-forget atomic per appended entry -- instead of by
-// k_sort_hist before the sort. Headline step 759.2 ms against 759.9: the 2.7e8 extra atomics per step cost inside the propagation kernels what
-// the 14 ms of histogram kernels cost outside them; and one run of the kilonova_expopac build at 50^3 / 1e7 gave different counters from the
-// same snapshot with it. profiles/r06/fused_histogram.md)
+// (the sort counts the keys itself, in LDS, a tile of the list at a time: k_sort_tilehist)
 __device__ inline void wave_append(bool flag, int32_t pi, int32_t key, int32_t *list, int32_t *keys, int32_t *count) {
   const unsigned long long mask = __ballot(flag);
   if (mask == 0) return;
@@ -984,16 +981,147 @@ __global__ void __launch_bounds__(BLOCK) k_count_waiting(Env env, int32_t *count
   else
     atomicAdd(&counts[c], 1);
 }
-// ---- counting sort of a work list by its entries' keys (propagation cell, frequency bin): three tiny kernels.
+// ---- counting sort of a work list by its entries' keys (propagation cell, frequency bin).
 // Within a cell, r-packets are ordered by comoving frequency like the reference's own packet sort
 // (compare_packet_order, update_packets.cc:363): neighbouring lanes then walk the same part of the line list and
 // the same window of bound-free continua.
-__global__ void __launch_bounds__(BLOCK) k_sort_hist(const int32_t *keys, int32_t n, int32_t *hist) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i < n) atomicAdd(&hist[keys[i]], 1);
+// MANY keys (a 3D grid: cells x bins, millions): two passes whose only atomics are LDS atomics (device-wide atomics on random
+// addresses are carried out beyond the XCDs' L2s; one per entry was the whole cost of the sort they replaced).
+//  pass 1, by the key's high digit (at most SORT_HI_MAX buckets): k_sort_tilehist counts every tile of SORT_TILE entries in LDS and stores
+//    the counts in its column of a [bucket][tile] matrix; the k_scan_* kernels below scan the matrix; k_sort_tilescatter loads a tile's
+//    cursors from its scanned column and places (key, entry) pairs, bucket by bucket, in the intermediate buffer.
+//  pass 2, by the low digit inside each bucket (a contiguous segment of the intermediate buffer): k_sort_plan cuts the segments into chunks
+//    of at most SORT_SEG_CAP entries; k_sort_segments gives every chunk a workgroup that counts the segment's low digits in LDS, scans
+//    them there and writes its chunk's entries to their places. A segment of several chunks is counted by each of its workgroups (reads
+//    only, from the L2), so a skewed list costs reads, never a workgroup that places a whole bucket on its own.
+// Nothing is zeroed per sort, and the scans cover buckets x tiles counters instead of one per key.
+constexpr int SORT_HI_BITS = 11;
+constexpr int SORT_HI_MAX = 1 << SORT_HI_BITS;
+constexpr int SORT_LO_BITS_MAX = 14;  // pass 2's two LDS tables: 2 x 2^14 x 4 B = 128 KB of a workgroup's 160 KB
+constexpr int64_t SORT_MAX_KEYS = (int64_t)1 << (SORT_HI_BITS + SORT_LO_BITS_MAX);  // 2^25: a 100^3 grid x SORT_NUBINS
+constexpr int SORT_TILE = 8192;     // entries per workgroup of pass 1
+constexpr int SORT_TB = 512;
+constexpr int SORT_SEG_CAP = 8192;  // entries a workgroup of pass 2 places
+__global__ void __launch_bounds__(SORT_TB) k_sort_tilehist(const int32_t *keys, int32_t n, int lobits, int nb, int32_t ntiles, int32_t *mat) {
+  __shared__ int32_t h[SORT_HI_MAX];
+  for (int b = threadIdx.x; b < nb; b += SORT_TB) h[b] = 0;
+  __syncthreads();
+  const int64_t lo = (int64_t)blockIdx.x * SORT_TILE, hi = (lo + SORT_TILE < n) ? lo + SORT_TILE : n;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += SORT_TB) atomicAdd(&h[keys[i] >> lobits], 1);
+  __syncthreads();
+  for (int b = threadIdx.x; b < nb; b += SORT_TB) mat[(int64_t)b * ntiles + blockIdx.x] = h[b];
 }
-// exclusive scan of the key histogram in three steps: per-block scan of SCAN_TILE keys, scan of the block totals
-// (one block), add the block offsets
+// mat: the scanned matrix, mat[b][tile] = where the tile's first entry of bucket b goes
+__global__ void __launch_bounds__(SORT_TB) k_sort_tilescatter(const int32_t *list, const int32_t *keys, int32_t n, int lobits, int nb, int32_t ntiles,
+                                                              const int32_t *mat, int2 *pairs) {
+  __shared__ int32_t h[SORT_HI_MAX];
+  for (int b = threadIdx.x; b < nb; b += SORT_TB) h[b] = mat[(int64_t)b * ntiles + blockIdx.x];
+  __syncthreads();
+  const int64_t lo = (int64_t)blockIdx.x * SORT_TILE, hi = (lo + SORT_TILE < n) ? lo + SORT_TILE : n;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += SORT_TB) {
+    const int32_t k = keys[i];
+    pairs[atomicAdd(&h[k >> lobits], 1)] = make_int2(k, list[i]);
+  }
+}
+// one workgroup: seg[b] = where bucket b begins (seg[nb] = n), chunk_base[b] = chunks of the buckets before it (chunk_base[nb] = all chunks)
+__global__ void __launch_bounds__(1024) k_sort_plan(const int32_t *mat, int32_t ntiles, int nb, int32_t n, int32_t *seg, int32_t *chunk_base) {
+  __shared__ int32_t part[1024];
+  const int t = threadIdx.x;
+  int32_t c[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const int b = 2 * t + k;
+    c[k] = 0;
+    if (b < nb) {
+      const int32_t s0 = mat[(int64_t)b * ntiles], s1 = (b + 1 < nb) ? mat[(int64_t)(b + 1) * ntiles] : n;
+      seg[b] = s0;
+      c[k] = (s1 - s0 + SORT_SEG_CAP - 1) / SORT_SEG_CAP;
+    }
+  }
+  if (t == 0) seg[nb] = n;
+  part[t] = c[0] + c[1];
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const int32_t add = (t >= off) ? part[t - off] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  const int32_t run = part[t] - c[0] - c[1];
+  if (2 * t < nb) chunk_base[2 * t] = run;
+  if (2 * t + 1 < nb) chunk_base[2 * t + 1] = run + c[0];
+  if (t == 1023) chunk_base[nb] = part[1023];
+}
+// a workgroup per chunk; sm[]: the segment's count of every low digit, then the cursors; behind it, for a later chunk of a segment, the
+// counts of the chunks before it
+__global__ void __launch_bounds__(BLOCK) k_sort_segments(const int2 *pairs, int lobits, int nb, const int32_t *seg, const int32_t *chunk_base,
+                                                         int32_t *out) {
+  extern __shared__ int32_t sm[];
+  __shared__ int32_t part[BLOCK];
+  __shared__ int s_bucket;
+  const int t = threadIdx.x;
+  const int nlow = 1 << lobits, mask = nlow - 1;
+  if (t == 0) {
+    int b = -1;
+    if ((int32_t)blockIdx.x < chunk_base[nb]) {  // the last bucket whose chunks begin at or before this one
+      int lo = 0, hi = nb - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (chunk_base[mid] <= (int32_t)blockIdx.x)
+          lo = mid;
+        else
+          hi = mid - 1;
+      }
+      b = lo;
+    }
+    s_bucket = b;
+  }
+  __syncthreads();
+  const int b = s_bucket;
+  if (b < 0) return;
+  const int32_t s0 = seg[b], s1 = seg[b + 1];
+  const int32_t c0 = s0 + ((int32_t)blockIdx.x - chunk_base[b]) * SORT_SEG_CAP, c1 = (s1 - c0 > SORT_SEG_CAP) ? c0 + SORT_SEG_CAP : s1;
+  int32_t *tot = sm, *before = sm + nlow;
+  const bool later = c0 > s0;
+  for (int d = t; d < nlow; d += BLOCK) {
+    tot[d] = 0;
+    if (later) before[d] = 0;
+  }
+  __syncthreads();
+  for (int32_t i = s0 + t; i < c0; i += BLOCK) {
+    const int d = pairs[i].x & mask;
+    atomicAdd(&tot[d], 1);
+    atomicAdd(&before[d], 1);
+  }
+  for (int32_t i = c0 + t; i < s1; i += BLOCK) atomicAdd(&tot[pairs[i].x & mask], 1);
+  __syncthreads();
+  // exclusive scan of tot[]: a run of digits per thread, the threads' sums, the runs again
+  const int per = (nlow + BLOCK - 1) / BLOCK;
+  const int d0 = (t * per < nlow) ? t * per : nlow, d1 = (d0 + per < nlow) ? d0 + per : nlow;
+  int32_t sum = 0;
+  for (int d = d0; d < d1; d++) sum += tot[d];
+  part[t] = sum;
+  __syncthreads();
+  for (int off = 1; off < BLOCK; off <<= 1) {
+    const int32_t add = (t >= off) ? part[t - off] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int32_t run = part[t] - sum;
+  for (int d = d0; d < d1; d++) {
+    const int32_t v = tot[d];
+    tot[d] = run + (later ? before[d] : 0);
+    run += v;
+  }
+  __syncthreads();
+  for (int32_t i = c0 + t; i < c1; i += BLOCK) {
+    const int2 p = pairs[i];
+    out[s0 + atomicAdd(&tot[p.x & mask], 1)] = p.y;
+  }
+}
+// exclusive scan of a table of counts (the few-keys histogram, the many-keys matrix) in three steps: per-block scan of SCAN_TILE
+// counts, scan of the block totals (one block), add the block offsets. A table of one tile is done after the first step.
 constexpr int SCAN_TILE = 8192;  // keys per block of 1024 threads (8 per thread)
 __global__ void __launch_bounds__(1024) k_scan_tiles(int32_t *hist, int32_t nkeys, int32_t *tile_totals) {
   __shared__ int32_t part[1024];
@@ -1048,10 +1176,6 @@ __global__ void __launch_bounds__(1024) k_scan_add(int32_t *hist, int32_t nkeys,
 #pragma unroll
   for (int k = 0; k < 8; k++)
     if (base + k < nkeys) hist[base + k] += off;
-}
-__global__ void __launch_bounds__(BLOCK) k_sort_scatter(const int32_t *list, const int32_t *keys, int32_t n, int32_t *offsets, int32_t *out) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i < n) out[atomicAdd(&offsets[keys[i]], 1)] = list[i];
 }
 // The same two steps for FEW keys (1D and 2D models, small 3D grids: a few hundred cells). With one global atomic per
 // entry the entries of a cell serialise on its counter (measured on a 6^3 grid with 1e7 packets: 7 ms per sort kernel,
@@ -2415,6 +2539,16 @@ struct LastCall {
   int64_t pool_resets = 0;       // times the pool of on-demand records was emptied because it was used up
   int32_t thermal_variants = 0, est_forms = 0;  // thermal-kernel instantiations launched; how the kernels added to the per-cell estimators (include/artis_amd.h)
 };
+// what the many-keys sort of a list of up to `capacity` entries needs besides its input and output: one allocation
+struct SortScratch {
+  void *base = nullptr;
+  int64_t capacity = 0;
+  int2 *pairs = nullptr;          // [capacity] pass 1's output: (key, entry), bucket by bucket
+  int32_t *mat = nullptr;         // [SORT_HI_MAX][tiles of the list] the tiles' bucket counts, scanned in place
+  int32_t *tiles = nullptr;       // the scan's tile totals
+  int32_t *seg = nullptr;         // [SORT_HI_MAX + 1] where every bucket begins
+  int32_t *chunk_base = nullptr;  // [SORT_HI_MAX + 1] pass 2's chunks before every bucket
+};
 struct artis_amd_engine {
   int device = 0;
   EngineConfig cfg;           // the resolved configuration (engine_config.h resolve_config: struct field, else ARTIS_AMD_* variable, else default)
@@ -2489,8 +2623,10 @@ struct artis_amd_engine {
   int32_t *d_perm = nullptr;                  // record slot -> index in the caller's packet array (k_aos_to_rec)
   bool use_perm = false;                      // d_perm describes the resident population
   bool slot_order_by_cell = true;             // ARTIS_AMD_SLOTSORT=0: slots in the caller's order
-  int32_t *d_hist = nullptr;                  // [ngrid * SORT_NUBINS + 1]
-  int32_t *d_tiles = nullptr;                 // scan tile totals
+  int32_t *d_hist = nullptr;                  // [SORT_LDS_KEYS + 1] key histogram of the few-keys sort
+  int32_t *d_tiles = nullptr;                 // ... and its scan's tile totals
+  SortScratch sort_scratch;                   // the many-keys sort's buffers, allocated with the lists
+  bool sort_attr_set = false;                 // k_sort_segments may use its 128 KB of LDS on this engine's device
   int32_t *d_count = nullptr;                 // [NEXT_NKINDS] current-list counts, [NEXT_NKINDS] alternate-list count
   int32_t *d_cursors = nullptr;               // [MAX_CHUNKS] chunk cursors of the running pull kernel
   int ncu = 256;
@@ -2743,12 +2879,86 @@ Env make_env(const artis_amd_engine *e) {
   return env;
 }
 
+void sort_scratch_free(SortScratch &S) {
+  if (S.base) (void)hipFree(S.base);
+  S = SortScratch{};
+}
+int sort_scratch_alloc(SortScratch &S, int64_t n) {
+  sort_scratch_free(S);
+  const size_t cap = (size_t)(n > 0 ? n : 1);
+  const size_t matlen = (size_t)SORT_HI_MAX * ((cap + SORT_TILE - 1) / SORT_TILE);
+  auto padded = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  const size_t b_pairs = padded(sizeof(int2) * cap), b_mat = padded(sizeof(int32_t) * matlen), b_tiles = padded(sizeof(int32_t) * (matlen / SCAN_TILE + 2)),
+               b_seg = padded(sizeof(int32_t) * (SORT_HI_MAX + 1));
+  HIP_TRY(hipMalloc(&S.base, b_pairs + b_mat + b_tiles + 2 * b_seg));
+  char *q = (char *)S.base;
+  S.pairs = (int2 *)q;
+  S.mat = (int32_t *)(q += b_pairs);
+  S.tiles = (int32_t *)(q += b_mat);
+  S.seg = (int32_t *)(q += b_tiles);
+  S.chunk_base = (int32_t *)(q += b_seg);
+  S.capacity = (int64_t)cap;
+  return ARTIS_OK;
+}
+std::string sort_too_many_keys_text(int64_t nkeys) {
+  return "the work-list sort takes at most " + std::to_string(SORT_MAX_KEYS) + " keys (cells x bins), this list has " + std::to_string(nkeys) +
+         ": run without sorted lists (ARTIS_AMD_SORT=0)";
+}
+// the many-keys sort (the kernels' comment): list[0..n) by keys[] (each in [0, nkeys)) into out[0..n); n <= S.capacity
+int sort_many_keys(artis_amd_engine *e, const SortScratch &S, hipStream_t s, const int32_t *list, const int32_t *keys, int32_t n, int64_t nkeys,
+                   int32_t *out) {
+  if (nkeys > SORT_MAX_KEYS) {
+    g_last_error = sort_too_many_keys_text(nkeys);
+    return ARTIS_ERR_UNSUPPORTED;
+  }
+  if (n <= 0 || n > S.capacity) {
+    g_last_error = "sort: the list does not fit the sort's buffers";
+    return ARTIS_ERR_ARG;
+  }
+  int keybits = 0;
+  while (((int64_t)1 << keybits) < nkeys) keybits++;
+  const int lobits = std::max(0, keybits - SORT_HI_BITS);
+  const int nb = (int)((nkeys - 1) >> lobits) + 1;
+  const int32_t ntiles = (int32_t)(((int64_t)n + SORT_TILE - 1) / SORT_TILE);
+  const int32_t matlen = nb * ntiles;
+  const int nscan = (matlen + SCAN_TILE - 1) / SCAN_TILE;
+  const size_t lds = sizeof(int32_t) * 2 * ((size_t)1 << lobits);
+  if (lds > 32 * 1024 && !e->sort_attr_set) {
+    HIP_TRY(hipFuncSetAttribute((const void *)k_sort_segments, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int32_t) * 2 << SORT_LO_BITS_MAX)));
+    e->sort_attr_set = true;
+  }
+  hipLaunchKernelGGL(k_sort_tilehist, dim3(ntiles), dim3(SORT_TB), 0, s, keys, n, lobits, nb, ntiles, S.mat);
+  hipLaunchKernelGGL(k_scan_tiles, dim3(nscan), dim3(1024), 0, s, S.mat, matlen, S.tiles);
+  if (nscan > 1) {
+    hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, s, S.tiles, nscan);
+    hipLaunchKernelGGL(k_scan_add, dim3(nscan), dim3(1024), 0, s, S.mat, matlen, S.tiles);
+  }
+  hipLaunchKernelGGL(k_sort_tilescatter, dim3(ntiles), dim3(SORT_TB), 0, s, list, keys, n, lobits, nb, ntiles, S.mat, S.pairs);
+  hipLaunchKernelGGL(k_sort_plan, dim3(1), dim3(1024), 0, s, S.mat, ntiles, nb, n, S.seg, S.chunk_base);
+  hipLaunchKernelGGL(k_sort_segments, dim3(n / SORT_SEG_CAP + nb), dim3(BLOCK), lds, s, S.pairs, lobits, nb, S.seg, S.chunk_base, out);
+  return ARTIS_OK;
+}
+// counting sort of list[0..n) by keys[] into out[0..n): in LDS-sized histograms for few keys, the two-pass sort for many
+int sort_list(artis_amd_engine *e, hipStream_t s, const int32_t *list, const int32_t *keys, int32_t n, int64_t nkeys, int32_t *out) {
+  if (nkeys > SORT_LDS_KEYS) return sort_many_keys(e, e->sort_scratch, s, list, keys, n, nkeys, out);
+  const int32_t nk = (int32_t)nkeys;
+  HIP_TRY(hipMemsetAsync(e->d_hist, 0, sizeof(int32_t) * (size_t)(nk + 1), s));
+  hipLaunchKernelGGL(k_sort_hist_lds, dim3(sort_lds_grid(n)), dim3(BLOCK), 0, s, keys, n, e->d_hist, nk);
+  const int ntiles = (nk + SCAN_TILE - 1) / SCAN_TILE;
+  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nk, e->d_tiles);
+  hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, s, e->d_tiles, ntiles);
+  hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nk, e->d_tiles);
+  hipLaunchKernelGGL(k_sort_scatter_lds, dim3(sort_lds_grid(n)), dim3(BLOCK), 0, s, list, keys, n, e->d_hist, out, nk);
+  return ARTIS_OK;
+}
+
 void free_packet_buffers(artis_amd_engine *e) {
   void **singles[] = {&e->d_pkt, &e->d_pkt_snapshot, (void **)&e->d_sorted, (void **)&e->d_perm, (void **)&e->d_gamma_ws,
                       (void **)&e->d_gamma_gi, (void **)&e->d_gamma_n, (void **)&e->d_bfev, (void **)&e->d_bfev_count,
                       (void **)&e->d_vpkt_queue, (void **)&e->d_vpkt_count};
   e->bfev_cap = 0;
   e->vpkt_cap = 0;
+  sort_scratch_free(e->sort_scratch);
   for (void **q : singles) {
     if (*q) (void)hipFree(*q);
     *q = nullptr;
@@ -2778,6 +2988,7 @@ int ensure_packet_buffers(artis_amd_engine *e, int64_t n) {
     }
   HIP_TRY(hipMalloc((void **)&e->d_sorted, listbytes));
   HIP_TRY(hipMalloc((void **)&e->d_perm, listbytes));
+  if (const int rc = sort_scratch_alloc(e->sort_scratch, n)) return rc;
   e->ws_capacity = n > 0 ? n : 1;
   const size_t wsbytes = sizeof(double) * (size_t)(e->Mh.nbfcontinua_ground + 1) * (size_t)e->ws_capacity;
   HIP_TRY(hipMalloc((void **)&e->d_gamma_ws, wsbytes));
@@ -3130,6 +3341,14 @@ int validate_model(const artis_model *model) {
       return ARTIS_ERR_UNSUPPORTED;
     }
   }
+  {  // the r-packet list's keys (cells x frequency bins) have to fit the work-list sort, unless the lists stay unsorted
+    const char *b = std::getenv("ARTIS_AMD_SORT");
+    const int64_t nkeys = (int64_t)model->ngrid * SORT_NUBINS;
+    if (nkeys > SORT_MAX_KEYS && !(b && std::atoi(b) == 0)) {
+      g_last_error = sort_too_many_keys_text(nkeys);
+      return ARTIS_ERR_UNSUPPORTED;
+    }
+  }
   return ARTIS_OK;
 }
 }  // namespace
@@ -3359,8 +3578,8 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     e->ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
-  HIP_TRY(hipMalloc((void **)&e->d_hist, sizeof(int32_t) * ((size_t)h.ngrid * SORT_NUBINS + 1)));
-  HIP_TRY(hipMalloc((void **)&e->d_tiles, sizeof(int32_t) * (((size_t)h.ngrid * SORT_NUBINS) / SCAN_TILE + 2)));
+  HIP_TRY(hipMalloc((void **)&e->d_hist, sizeof(int32_t) * (SORT_LDS_KEYS + 1)));
+  HIP_TRY(hipMalloc((void **)&e->d_tiles, sizeof(int32_t) * (SORT_LDS_KEYS / SCAN_TILE + 2)));
   HIP_TRY(hipEventCreate(&e->ev0));
   HIP_TRY(hipEventCreate(&e->ev1));
   HIP_TRY(hipEventCreate(&e->ev2));
@@ -3869,19 +4088,7 @@ int artis_amd_packets_upload(artis_amd_engine *e, const artis_packet *packets, i
       const int32_t nkeys = e->Mh.ngrid;
       hipStream_t s = nullptr;
       hipLaunchKernelGGL(k_aos_cellkeys, dim3(nblocks(npackets)), dim3(BLOCK), 0, s, e->d_aos, npackets, nkeys, ident, keys);
-      HIP_TRY(hipMemsetAsync(e->d_hist, 0, sizeof(int32_t) * (size_t)(nkeys + 1), s));
-      if (nkeys <= SORT_LDS_KEYS)
-        hipLaunchKernelGGL(k_sort_hist_lds, dim3(sort_lds_grid(n32)), dim3(BLOCK), 0, s, keys, n32, e->d_hist, nkeys);
-      else
-        hipLaunchKernelGGL(k_sort_hist, dim3(nblocks(n32)), dim3(BLOCK), 0, s, keys, n32, e->d_hist);
-      const int ntiles = (nkeys + SCAN_TILE - 1) / SCAN_TILE;
-      hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nkeys, e->d_tiles);
-      hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, s, e->d_tiles, ntiles);
-      hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nkeys, e->d_tiles);
-      if (nkeys <= SORT_LDS_KEYS)
-        hipLaunchKernelGGL(k_sort_scatter_lds, dim3(sort_lds_grid(n32)), dim3(BLOCK), 0, s, ident, keys, n32, e->d_hist, e->d_perm, nkeys);
-      else
-        hipLaunchKernelGGL(k_sort_scatter, dim3(nblocks(n32)), dim3(BLOCK), 0, s, ident, keys, n32, e->d_hist, e->d_perm);
+      if (const int rc2 = sort_list(e, s, ident, keys, n32, nkeys, e->d_perm)) return rc2;
       e->use_perm = true;
     }
     hipLaunchKernelGGL(k_aos_to_rec, dim3(nblocks(npackets)), dim3(BLOCK), 0, nullptr, e->d_aos, e->P, e->use_perm ? e->d_perm : nullptr);
@@ -4257,6 +4464,57 @@ int artis_amd_debug_cellcache(artis_amd_engine *e, int c, double *levelpops, dou
   DL(chi_ff_nnionpart, chi_ff_nnionpart, double, 1)
 #undef DL
   return ARTIS_OK;
+}
+
+
+int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const int32_t *list, int32_t n, int64_t nkeys, int32_t *out) {
+  if (!e || n < 0 || (n > 0 && (!keys || !list || !out))) {
+    g_last_error = "null argument or negative length";
+    return ARTIS_ERR_ARG;
+  }
+  if (nkeys <= SORT_LDS_KEYS) {
+    g_last_error = "debug_sort_list runs the many-keys sort: nkeys has to be above " + std::to_string(SORT_LDS_KEYS);
+    return ARTIS_ERR_ARG;
+  }
+  if (nkeys > SORT_MAX_KEYS) {
+    g_last_error = sort_too_many_keys_text(nkeys);
+    return ARTIS_ERR_UNSUPPORTED;
+  }
+  for (int32_t i = 0; i < n; i++)
+    if (keys[i] < 0 || keys[i] >= nkeys) {
+      g_last_error = "a key is outside [0, nkeys)";
+      return ARTIS_ERR_ARG;
+    }
+  if (n < 2 * BLOCK) {  // sort_by_key() leaves so short a list as it is
+    if (n > 0) std::memcpy(out, list, sizeof(int32_t) * (size_t)n);
+    return ARTIS_OK;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  // the engine's own sort scratch (grown if this list is longer than its packet lists: it holds nothing between two sorts), buffers of the
+  // call's own for keys, list and output: the engine's lists are not touched
+  SortScratch &S = e->sort_scratch;
+  int32_t *d_io = nullptr;  // keys, list, out
+  int rc = (S.capacity >= n) ? ARTIS_OK : sort_scratch_alloc(S, n);
+  if (rc == ARTIS_OK && hipMalloc((void **)&d_io, sizeof(int32_t) * 3 * (size_t)n) != hipSuccess) {
+    g_last_error = "debug_sort_list: out of device memory";
+    rc = ARTIS_ERR_HIP;
+  }
+  auto copy = [&](void *dst, const void *src, hipMemcpyKind kind) {
+    if (rc == ARTIS_OK && hipMemcpy(dst, src, sizeof(int32_t) * (size_t)n, kind) != hipSuccess) {
+      g_last_error = "debug_sort_list: copy failed";
+      rc = ARTIS_ERR_HIP;
+    }
+  };
+  copy(d_io, keys, hipMemcpyHostToDevice);
+  copy(d_io + n, list, hipMemcpyHostToDevice);
+  if (rc == ARTIS_OK) rc = sort_many_keys(e, S, nullptr, d_io + n, d_io, n, nkeys, d_io + 2 * (size_t)n);
+  if (rc == ARTIS_OK && (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
+    g_last_error = "debug_sort_list: a sort kernel failed";
+    rc = ARTIS_ERR_HIP;
+  }
+  copy(out, d_io + 2 * (size_t)n, hipMemcpyDeviceToHost);
+  if (d_io) (void)hipFree(d_io);
+  return rc;
 }
 
 }  // extern "C"

@@ -22,20 +22,7 @@ int sort_by_key(artis_amd_engine *e, hipStream_t s, const int32_t *list, const i
   *out = list;
   if (!e->sort_lists || n < 2 * BLOCK) return ARTIS_OK;
   if ((int64_t)n > (int64_t)max_per_cell * (ncells > 0 ? ncells : 1)) return ARTIS_OK;
-  const int32_t nkeys = nkeys_given > 0 ? nkeys_given : e->Mh.ngrid * nbins;
-  HIP_TRY(hipMemsetAsync(e->d_hist, 0, sizeof(int32_t) * (size_t)(nkeys + 1), s));
-  if (nkeys <= SORT_LDS_KEYS)
-    hipLaunchKernelGGL(k_sort_hist_lds, dim3(sort_lds_grid(n)), dim3(BLOCK), 0, s, keys, n, e->d_hist, nkeys);
-  else
-    hipLaunchKernelGGL(k_sort_hist, dim3(nblocks(n)), dim3(BLOCK), 0, s, keys, n, e->d_hist);
-  const int ntiles = (nkeys + SCAN_TILE - 1) / SCAN_TILE;
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nkeys, e->d_tiles);
-  hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, s, e->d_tiles, ntiles);
-  hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(1024), 0, s, e->d_hist, nkeys, e->d_tiles);
-  if (nkeys <= SORT_LDS_KEYS)
-    hipLaunchKernelGGL(k_sort_scatter_lds, dim3(sort_lds_grid(n)), dim3(BLOCK), 0, s, list, keys, n, e->d_hist, e->d_sorted, nkeys);
-  else
-    hipLaunchKernelGGL(k_sort_scatter, dim3(nblocks(n)), dim3(BLOCK), 0, s, list, keys, n, e->d_hist, e->d_sorted);
+  STEP(sort_list(e, s, list, keys, n, nkeys_given > 0 ? (int64_t)nkeys_given : (int64_t)e->Mh.ngrid * nbins, e->d_sorted));
   *out = e->d_sorted;
   return ARTIS_OK;
 }

@@ -83,7 +83,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_engine_destroy", "artis_amd_set_cellstate", "artis_amd_update_packets", "artis_amd_packets_upload",
     "artis_amd_packets_download", "artis_amd_packets_snapshot", "artis_amd_packets_restore",
     "artis_amd_update_packets_device", "artis_amd_estimators_zero", "artis_amd_estimators_download",
-    "artis_amd_estimators_devptr", "artis_amd_last_kernel_ms", "artis_amd_debug_cellcache", "artis_amd_debug_visit_counts", "artis_amd_last_kernel_ms_by_kind",
+    "artis_amd_estimators_devptr", "artis_amd_last_kernel_ms", "artis_amd_debug_cellcache", "artis_amd_debug_sort_list", "artis_amd_debug_visit_counts", "artis_amd_last_kernel_ms_by_kind",
     "artis_amd_populate_cellcache",
     "artis_amd_last_kernel_breakdown",
     "artis_amd_last_kernel_launches",
@@ -312,6 +312,18 @@ class Engine:
         args = [self.h, C.c_int(c)] + [v.ctypes.data_as(C.c_void_p) for v in out.values()] + [C.byref(chi)]
         self._check(self.L.artis_amd_debug_cellcache(*args))
         out["chi_ff_nnionpart"] = chi.value
+        return out
+
+    def debug_sort_list(self, keys, lst, nkeys: int):
+        """lst's entries ordered by non-decreasing key, by the many-keys work-list sort (artis_amd_debug_sort_list); keys[i] in [0, nkeys)
+        is the key of lst[i]. The engine's own lists are not touched."""
+        keys = np.ascontiguousarray(keys, dtype=np.int32)
+        lst = np.ascontiguousarray(lst, dtype=np.int32)
+        assert keys.shape == lst.shape and keys.ndim == 1
+        out = np.empty_like(lst)
+        self.L.artis_amd_debug_sort_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
+        self._check(self.L.artis_amd_debug_sort_list(self.h, keys.ctypes.data_as(C.c_void_p), lst.ctypes.data_as(C.c_void_p), len(lst), int(nkeys),
+                                                     out.ctypes.data_as(C.c_void_p)))
         return out
 
     def config(self) -> dict:

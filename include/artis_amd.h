@@ -699,6 +699,11 @@ int artis_amd_debug_cellcache(artis_amd_engine *eng, int nonemptymgi, double *le
                               double *matrans, double *allcont_nnlevel, double *allcont_departure,
                               double *allcont_edgepart, uint64_t *allcont_keepbits, double *corrphotoioncoeff,
                               double *cooling_contrib, double *ion_cooling_contribs, double *chi_ff_nnionpart);
+/* Test / debug: the many-keys work-list sort (more than 8192 keys) on host arrays. keys[i] in [0, nkeys) is the key of list[i]; out[0..n)
+ * receives list's entries ordered by non-decreasing key (any order among equal keys). A list shorter than 512 entries is copied as it is, as
+ * the propagation leaves it. The engine's lists are not touched (its sort scratch is used, and grown for a longer list). ARTIS_ERR_UNSUPPORTED for more keys than the sort
+ * takes (2^25), ARTIS_ERR_ARG for 8192 keys or fewer or a key outside the range. */
+int artis_amd_debug_sort_list(artis_amd_engine *eng, const int32_t *keys, const int32_t *list, int32_t n, int64_t nkeys, int32_t *out);
 
 /* Summed launch durations (HIP events on the launch stream) of the last artis_amd_update_packets_device() call by kind of kernel:
  * 0 k_rpkt (+ k_bfest_dense), 1 k_thermal, 2 k_slow, 3 k_gamma, 4 k_blackbody, 5 k_tail, 6 tile fills inside the call; 7 unused.
