@@ -1322,6 +1322,9 @@ inline int chunks_for(int64_t n, int nwaves) {
   return (int)std::min<int64_t>(c, MAX_CHUNKS);
 }
 
+#ifndef ARTIS_RPKT_SPLIT_ABSORB
+#define ARTIS_RPKT_SPLIT_ABSORB 0  // (1: measured round 5: k_rpkt 265 -> 258 ms, k_slow 16 -> 32 ms, step unchanged, scratch unchanged: off) free-free / bound-free absorptions of r-packets carried out by the slow-path kernel (physics.h PEND_RPKT_ABSORB)
+#endif
 // r-packets in flight: boundary distance, continuum opacity, line-by-line Sobolev walk, estimators, events.
 // CONT_LDS: the static table of bound-free continua (ContPack: edge frequency, target probability, cross-section table,
 // ground-continuum index; 32 B per continuum) is copied into LDS once per workgroup and every read of it in the opacity
@@ -1377,9 +1380,6 @@ __device__ inline void cellest_flush(const Env &env, int kind, double *global_ar
 // cell-sorted work list does not give: a wave's 64 packets sit in ~21 cells (2.6 lanes per cell) and
 // anywhere in the spectrum. Measured slower than the continuum table in LDS: profiles/r04/line_window.md.
 constexpr int LINE_LDS_MAX = 14336;  // lines (112 KB)
-#ifndef ARTIS_RPKT_SPLIT_ABSORB
-#define ARTIS_RPKT_SPLIT_ABSORB 0  // (1: measured round 5: k_rpkt 265 -> 258 ms, k_slow 16 -> 32 ms, step unchanged, scratch unchanged: off) free-free / bound-free absorptions of r-packets carried out by the slow-path kernel (physics.h PEND_RPKT_ABSORB)
-#endif
 template <bool CONT_LDS, int TB, bool LINE_LDS = false>
 __global__ void __launch_bounds__(TB, ARTIS_RPKT_WGS) k_rpkt(Env env, const int32_t *list, int32_t n, Lists next,
                                                                    unsigned long long *gstats, int budget, int32_t *cursors, int nchunks,
@@ -1452,40 +1452,11 @@ __global__ void __launch_bounds__(TB, ARTIS_RPKT_WGS) k_rpkt(Env env, const int3
       if (q.exhausted) break;
       continue;
     }
-    int kind = NEXT_DONE;
-    int32_t out_pi = 0;
-#ifdef ARTIS_PROFILE
-    {  // slot 53: everything outside do_rpkt_step (pull, load, store, append), 54: inside; 55: wave iterations
-      const long long now = clock64();
-      if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&lstats[53], (stat_t)((now - tprev) >> 4));
-        atomicAdd(&lstats[55], (stat_t)1);
-      }
-      tprev = now;
-    }
-#endif
-    if (have) {
-      bool go = rpkt_can_continue(p, ts_end);
-      if (go) {
-        go = rpkt_iter<ARTIS_RPKT_SPLIT_ABSORB != 0>(env, p, pi, x);
-        steps++;
-      }
-      if (!go || steps >= budget || (drained && steps >= drain_budget)) {
-        chi_store(env.P, pi, p, x);
-        pkt_store(env.P, pi, p);
-        kind = classify(env, p, ts_end);
-        out_pi = pi;
-        have = false;
-      }
-    }
-#ifdef ARTIS_PROFILE
-    {
-      const long long now = clock64();
-      if ((threadIdx.x & 63) == 0) atomicAdd(&lstats[54], (stat_t)((now - tprev) >> 4));
-      tprev = now;
-    }
-#endif
-    append_by_kind(kind, out_pi, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion));
+#define ROUND_LEAVE(n) ((n) >= budget || (drained && (n) >= drain_budget))
+#define ROUND_PUT(kind_, pi_) append_by_kind(kind_, pi_, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion))
+#include "rpkt_round.inc"
+#undef ROUND_LEAVE
+#undef ROUND_PUT
   }
   __syncthreads();
   if (env.estcache != nullptr) {  // the wave's accumulators go to the cells' records: a lane per slot
@@ -1757,94 +1728,23 @@ __global__ void __launch_bounds__(TB, (TABLES_LDS ? 1 : ARTIS_THERMAL_EU)) k_the
       if (q.exhausted) break;
       continue;
     }
-    int kind = NEXT_DONE;
-    int32_t out_pi = 0;
-    // the two phases of thermal_iter() (physics.h), spelled out so that the wave reconverges between them
-#ifdef ARTIS_PROFILE
-    // wave-cycle accounting (units of 16 clocks) in the spare stats slots 42..47: pull+load | macro-atom phase |
-    // k-packet phase | store+append, and the wave-level iteration counts of the two phases
-    const long long t0 = clock64();
-    PROF_ADD(42, t0 - tprev);
-#endif
-    bool go = have && thermal_can_continue(p, ts_end);
-    if (go) {
-      // the loop makes the internal transitions; the process that ends a walk is carried out after it, once per phase
-      int j = 0;
-      int exit_action = -1;
-      const U4 *rec = nullptr;
-      if (ma_pending(p) && p.pend == PEND_NONE) ma_prepare<COLD>(env, p, k);  // the record of the current level; the walk carries it on
-      while (j < ARTIS_MA_PHASE && exit_action < 0 && ma_pending(p) && p.pend == PEND_NONE) {  // [census: transition loop]
-#ifdef ARTIS_PROFILE
-        if ((threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) ARTIS_STAT(env, 46);
-#endif
-        rec = ma_record<COLD>(env, k);
-        exit_action = ma_jump_internal<ARTIS_MA_DEFER_EXACT != 0, COLD>(env, p, k, rec);
-        j++;
-      }
-      ma_flush_stats(env, k);
-      // (a transition whose search the filters could not decide is finished here, outside the loop: the walk goes on in the
-      // next phase)
-      if (exit_action == MA_EXIT_FILL) {
-        p.pend = PEND_MA_FILL;  // a cold level without a record in this cell: the slow-path kernel fills it (physics.h ma_slow_fill)
-      } else if (exit_action == MA_EXIT_DEFER) {
-#if ARTIS_THERMAL_SPLIT_EXACT
-        // the lines' fine bytes decide all but 1e-6 of these (round 6; tables.h "FINE BYTES"): the walk goes on in the next phase. What they leave:
-        if (!ma_jump_deferred_fine<COLD>(env, p, k, rec)) {
-          p.pend = PEND_MA_SEARCH;  // the slow-path kernel re-adds the sums and makes the transition (physics.h ma_slow_search)
-          p.pend_arg = k.defer;
-        }
-#else
-        ma_jump_deferred(env, p, k, rec);
-#endif
-      } else if (exit_action >= 0) {
-        ma_jump_exit<ARTIS_THERMAL_SPLIT_EXACT != 0>(env, p, pi, k, rec, exit_action);
-      }
-      if (j > 0) chi_after_ma(p);
-      units += j;
-    }
-#ifdef ARTIS_PROFILE
-    const long long t1 = clock64();
-    PROF_ADD(43, t1 - t0);
-#endif
-    if (go) {
-      // a pre-k-packet, or a k-packet in a grey cell, leaves for the blackbody kernel (classify() below)
-      const bool blackbody = (p.type == ARTIS_TYPE_PRE_KPKT) || k.thick;
-      if (kpkt_eligible(p, ts_end) && !blackbody) {
-#ifdef ARTIS_PROFILE
-        if ((threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) ARTIS_STAT(env, 47);
-#endif
-        do_kpkt<ARTIS_THERMAL_SPLIT_EXACT != 0>(env, p, pi);
-        p.chi_mgi = -1;
-        units++;
-      }
-      go = thermal_can_continue(p, ts_end) && !(blackbody && kpkt_eligible(p, ts_end));
-    }
-#ifdef ARTIS_PROFILE
-    const long long t2 = clock64();
-    PROF_ADD(44, t2 - t1);
-#endif
     // Once the work list is used up, the launch lasts as long as its slowest packets keep their lanes (up to `budget`
     // units each) while the rest of the GPU idles. In a launch whose successor is large anyway (drain_budget set by the
     // host), a packet then leaves after drain_budget units for that next launch, where its work runs beside a full list.
     // (Where a packet is handed from launch to launch never changes it: budgets are placement, tested.)
-    if (!drained && q.exhausted) {
-      drained = true;
-      if ((threadIdx.x & 63) == 0) __hip_atomic_store(&cursors[MAX_CHUNKS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (!drained && drain_budget < budget)
+#define ROUND_BEFORE_LEAVE \
+    if (!drained && q.exhausted) { \
+      drained = true; \
+      if ((threadIdx.x & 63) == 0) __hip_atomic_store(&cursors[MAX_CHUNKS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+    } \
+    if (!drained && drain_budget < budget) \
       drained = __hip_atomic_load(&cursors[MAX_CHUNKS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-    if (have && (!go || units >= budget || (drained && units >= drain_budget))) {
-      pkt_store_thermal(env.P, pi, p);  // the hot line; the flight line only if an r-packet was emitted
-      kind = classify(env, p, ts_end);
-      out_pi = pi;
-      have = false;
-    }
-    append_by_kind(kind, out_pi, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion));
-    pkt_clear_flight(p);  // a thermal packet never reads them: no live range across iterations
-#ifdef ARTIS_PROFILE
-    tprev = clock64();
-    PROF_ADD(45, tprev - t2);
-#endif
+#define ROUND_LEAVE(n) ((n) >= budget || (drained && (n) >= drain_budget))
+#define ROUND_PUT(kind_, pi_) append_by_kind(kind_, pi_, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion))
+#include "thermal_round.inc"
+#undef ROUND_BEFORE_LEAVE
+#undef ROUND_LEAVE
+#undef ROUND_PUT
   }
   __syncthreads();
   if (env.estcache_nv == 1) {  // the wave's sums go to the cells' records
@@ -2169,6 +2069,241 @@ constexpr int TQ_TB = ARTIS_TQ_TB;  // 12 waves per CU = 3 waves/SIMD at 168 VGP
 inline size_t tq_lds_bytes(int tb, int nlevels, int nalltrans) {
   return (((sizeof(TQWave) * (size_t)(tb / 64)) + 15) & ~(size_t)15) + (sizeof(LevelPack) * (size_t)nlevels) + (sizeof(uint32_t) * (size_t)((nalltrans + 1) / 2));
 }
+
+// ---- k_late: the END of a population -- the r-packets and thermal packets left once the lists are too short to fill the GPU -- in ONE persistent
+// launch. The split kernels put a device-wide barrier between every r-packet <-> thermal alternation, and below ~1e6 packets every such round costs a
+// floor (its slowest packet's visit) however few packets it holds; the sum over rounds of those maxima is far above the longest single chain. Here a
+// packet goes from one kind of step to the other inside the launch:
+//   geometry   one workgroup of LATE_TB = 512 threads per compute unit (2 waves per SIMD, no spilled register; 768 threads: 3 waves, 34 spilled, measured);
+//   ownership  workgroup b owns a fixed contiguous share of the (sorted) r-packet list and of the thermal list; a packet never changes workgroup, and
+//              nothing waits on another workgroup;
+//   queues     per workgroup one ring per role (r-packet, thermal) in its slice of a scratch array, capacity = the workgroup's share (a packet sits in
+//              at most one queue); head, reserved and published tail in LDS. A producer stores the packet (the bodies' pkt_store / chi_store /
+//              pkt_store_thermal), writes the entries it reserved, and publishes them in reservation order with a workgroup-scope release; a consumer
+//              reads the published tail with a workgroup-scope acquire, reads the entries, and takes them with a compare-and-swap on the head (entries
+//              [head, published) cannot be overwritten while the head stands: the ring holds as many entries as the workgroup has packets). All waves
+//              of a workgroup share a compute unit and its L1: no device-scope fence;
+//   roles      a wave runs one role at a time (all its lanes in the same body: rpkt_round.inc / thermal_round.inc, the split kernels' own); idle lanes pull
+//              from the role's queue; a lane keeps its packet until its kind changes or it ends -- no budget. The waves start split between the roles
+//              in proportion to the workgroup's two shares (at least one wave each where both are non-empty); a wave whose lanes are all idle and whose
+//              queue is empty takes the other role if that queue is not empty;
+//   ejection   a packet whose next kind is the slow path, a blackbody step, a gamma-ray kind, or that is done, is stored and appended to the ordinary
+//              lists (append_by_kind) exactly as a split kernel would; the host's loop runs those kinds and what comes back is listed again;
+//   the end    `live` (LDS) counts the workgroup's packets that have not been ejected; a wave leaves when it is 0;
+//   estimators plain f64 global atomics (the lists are short here): no per-wave caches, no few-cells LDS arrays;
+//   waits      every wait is for a wave of the same workgroup, so progress is certain; each is capped all the same. An idle wave polls with s_sleep at
+//              most poll_cap times, then counts itself in *bailouts and leaves (it holds no packet; the waves that do carry the workgroup's packets to
+//              their end: a bail-out costs time, never an answer). A producer waits for the reservations before its own to be published -- a few
+//              instructions of another wave -- and, if that never happens, raises error flag 47 and publishes nothing (the call fails; no entry is read that was not written).
+// Dynamic LDS: [stats | counters | LevelPack x nlevels | uint16 target levels x nalltrans | ContPack x nbfcontinua] (late_lds_bytes()).
+#ifndef ARTIS_LATE_KERNEL
+#define ARTIS_LATE_KERNEL (!ARTIS_OPT_VPKT_ON && !ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON)  // the builds that may use k_late
+#endif
+#ifndef ARTIS_LATE_TB
+#define ARTIS_LATE_TB 512  // 2 waves per SIMD at up to 256 VGPRs: no spilled register (768: 3 waves at 168 VGPRs, 34 spilled; profiles/r08/late_kernel.md)
+#endif
+constexpr int LATE_TB = ARTIS_LATE_TB;
+constexpr size_t LATE_LDS_HEAD = (sizeof(stat_t) * ARTIS_NSTATS) + 64;  // statistics, then the queues' counters
+inline size_t late_lds_bytes(int nlevels, int nalltrans, int nbfcontinua) {
+  return LATE_LDS_HEAD + (sizeof(LevelPack) * (size_t)nlevels) + (((sizeof(uint32_t) * (size_t)((nalltrans + 1) / 2)) + 15) & ~(size_t)15) +
+         (sizeof(ContPack) * (size_t)nbfcontinua);
+}
+struct LateArgs {
+  const int32_t *list[2];  // the r-packet and the thermal list, consumed whole
+  int32_t n[2];
+  int32_t *ring[2];        // scratch: [n[0] + n[1]] each; workgroup b's slice begins at the sum of its two shares' beginnings
+  int32_t *bailouts;
+  int32_t poll_cap;
+};
+#if ARTIS_LATE_KERNEL
+struct LateRing {
+  int32_t *ring;   // the workgroup's slice
+  uint32_t cap;
+  int32_t *head, *res, *pub;  // LDS: entries taken | reserved by producers | published (head <= pub <= res <= head + cap)
+};
+__device__ inline void late_push(const LateRing &Q, bool flag, int32_t pi, int32_t *errflag) {
+  const unsigned long long mask = __ballot(flag);
+  if (mask == 0) return;
+  const int lane = threadIdx.x & 63;
+  const int cnt = __popcll(mask);
+  const int prefix = __popcll(mask & ((1ull << lane) - 1ull));
+  const int leader = __ffsll((long long)mask) - 1;
+  int base = 0;
+  if (lane == leader) base = atomicAdd(Q.res, cnt);
+  base = __shfl(base, leader);
+  if (flag) Q.ring[(uint32_t)(base + prefix) % Q.cap] = pi;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // the packet records and the entries, before the entries are published
+  if (lane == leader) {
+    int spins = 0;
+    bool turn = true;
+    while (__hip_atomic_load(Q.pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != base) {  // earlier reservations are published first
+      __builtin_amdgcn_s_sleep(1);
+      if (++spins > (1 << 24)) {
+        // never publish over a reservation that was not: the entries stay out of reach, the workgroup's waves run into their poll caps, the
+        // kernel ends and the call fails with this flag
+        if (errflag) *errflag = 47;
+        turn = false;
+        break;
+      }
+    }
+    if (turn) __hip_atomic_store(Q.pub, base + cnt, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+}
+// hands queue entries to the lanes with need == true: the packet's index, or -1. Wave-uniform control flow.
+__device__ inline int32_t late_pull(const LateRing &Q, bool need) {
+  const unsigned long long mask = __ballot(need);
+  if (mask == 0) return -1;
+  const int lane = threadIdx.x & 63;
+  const int prefix = __popcll(mask & ((1ull << lane) - 1ull));
+  const int leader = __ffsll((long long)mask) - 1;
+  int h = 0, t = 0;
+  if (lane == leader) {
+    h = __hip_atomic_load(Q.head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    t = __hip_atomic_load(Q.pub, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  h = __shfl(h, leader);
+  t = __shfl(t, leader);
+  const int take = min(__popcll(mask), t - h);
+  if (take <= 0) return -1;
+  int32_t v = -1;
+  if (need && prefix < take) v = __hip_atomic_load(&Q.ring[(uint32_t)(h + prefix) % Q.cap], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  int ok = 0;
+  if (lane == leader) ok = (atomicCAS(Q.head, h, h + take) == h) ? 1 : 0;  // another wave took them first: the caller asks again
+  ok = __shfl(ok, leader);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // the packet records are read after this
+  return ok ? v : -1;
+}
+// k_late's policy for the loop bodies it shares with the split kernels (rpkt_round.inc, thermal_round.inc): no budget; a packet that stays an
+// r-packet or a thermal packet goes to the workgroup's queue of that role, every other packet leaves the kernel
+struct LateSink {
+  LateRing q[2];
+  int32_t *live;
+  int32_t *errflag;
+  // left: this lane gave up packet pi, whose next kind is `kind`. Wave-uniform control flow.
+  __device__ void put(bool left, int kind, int32_t pi, const Pkt &p, const Lists &next) const {
+    const bool to_r = left && kind == NEXT_RPKT;
+    const bool to_t = left && (kind == NEXT_MA || kind == NEXT_KPKT);
+    late_push(q[0], to_r, pi, errflag);
+    late_push(q[1], to_t, pi, errflag);
+    const bool out = left && !to_r && !to_t;
+    append_by_kind(out ? kind : NEXT_DONE, pi, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion));
+    const unsigned long long om = __ballot(out);
+    if (om != 0 && (int)(threadIdx.x & 63) == __ffsll((long long)om) - 1) atomicSub(live, __popcll(om));  // after the append: `live` 0 = all is on the lists
+  }
+};
+__global__ void __launch_bounds__(LATE_TB, 1) k_late(Env env, LateArgs a, Lists next, unsigned long long *gstats) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char late_lds[];
+  // this workgroup's shares of the two lists (contiguous; neighbouring shares on one XCD: xcd_chunk) and its slice of the rings
+  const int64_t nwg = gridDim.x, b = xcd_chunk(blockIdx.x, nwg);
+  const int32_t r0 = (int32_t)(((int64_t)a.n[0] * b) / nwg), r1 = (int32_t)(((int64_t)a.n[0] * (b + 1)) / nwg);
+  const int32_t t0 = (int32_t)(((int64_t)a.n[1] * b) / nwg), t1 = (int32_t)(((int64_t)a.n[1] * (b + 1)) / nwg);
+  const int32_t own = (r1 - r0) + (t1 - t0);
+  if (own == 0) return;  // (the whole workgroup)
+  stat_t *lstats = (stat_t *)late_lds;
+  int32_t *ctr = (int32_t *)(late_lds + (sizeof(stat_t) * ARTIS_NSTATS));  // head r, t | reserved r, t | published r, t | live
+  LevelPack *lds_levelpack = (LevelPack *)(late_lds + LATE_LDS_HEAD);
+  uint16_t *lds_tlevel = (uint16_t *)(lds_levelpack + env.M.nlevels);
+  ContPack *lds_cont = (ContPack *)((unsigned char *)lds_tlevel + (((sizeof(uint32_t) * (size_t)((env.M.nalltrans + 1) / 2)) + 15) & ~(size_t)15));
+  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
+  for (int i = threadIdx.x; i < env.M.nlevels; i += LATE_TB) lds_levelpack[i] = env.M.level_pack[i];
+  {
+    const uint32_t *src = (const uint32_t *)env.M.alltrans_tlevel16;  // (the allocation is padded to whole words)
+    uint32_t *dst = (uint32_t *)lds_tlevel;
+    for (int i = threadIdx.x; i < (env.M.nalltrans + 1) / 2; i += LATE_TB) dst[i] = src[i];
+  }
+  {
+    const D2 *src = (const D2 *)env.M.cont_pack;
+    D2 *dst = (D2 *)lds_cont;
+    for (int i = threadIdx.x; i < env.M.nbfcontinua * 2; i += LATE_TB) dst[i] = src[i];
+  }
+  LateSink sink{{{a.ring[0] + (r0 + t0), (uint32_t)own, ctr + 0, ctr + 2, ctr + 4}, {a.ring[1] + (r0 + t0), (uint32_t)own, ctr + 1, ctr + 3, ctr + 5}},
+                ctr + 6, env.errflag};
+  // the queues begin with the workgroup's shares
+  for (int i = threadIdx.x; i < r1 - r0; i += LATE_TB) sink.q[0].ring[i] = a.list[0][r0 + i];
+  for (int i = threadIdx.x; i < t1 - t0; i += LATE_TB) sink.q[1].ring[i] = a.list[1][t0 + i];
+  if (threadIdx.x == 0) {
+    ctr[0] = ctr[1] = 0;
+    ctr[2] = ctr[4] = r1 - r0;
+    ctr[3] = ctr[5] = t1 - t0;
+    ctr[6] = own;
+  }
+  env.M.level_pack = lds_levelpack;
+  env.M.alltrans_tlevel16 = lds_tlevel;
+  env.ma_tables_in_lds = 1;
+  env.M.cont_pack = lds_cont;
+  env.cont_in_lds = 1;
+  env.cellest_lds = nullptr;
+  env.cellest_n = 0;
+  env.estcache = nullptr;
+  env.estcache_nv = 0;
+  __syncthreads();
+  env.stats = lstats;
+  const double ts_end = env.S.ts_end;
+  constexpr int NW = LATE_TB / 64;
+  // roles: 0 = r-packets, 1 = thermal packets
+  int nw_r = (int)((((int64_t)(r1 - r0) * NW) + (own / 2)) / own);
+  if (r1 > r0 && t1 > t0) nw_r = max(1, min(NW - 1, nw_r));
+  int role = __builtin_amdgcn_readfirstlane(((int)(threadIdx.x >> 6) < nw_r) ? 0 : 1);
+  bool have = false;
+  int32_t pi = 0;
+  int n_it = 0;  // (the bodies count the lane's steps / units; no budget reads them here)
+  int polls = 0;
+  Pkt p;
+  Chi x;
+  MACtx k;
+  long long tprev = 0;
+  while (true) {
+    const int32_t got = late_pull(sink.q[role], !have);
+    if (got >= 0) {
+      pi = got;
+      if (role == 0) {
+        pkt_load(env.P, pi, p);
+        chi_load(env.P, pi, p, x);
+      } else {
+        pkt_load_thermal(env.P, pi, p);  // the hot line only
+        k = ma_ctx(env, p);
+      }
+      have = true;
+    }
+    if (!__any(have)) {
+      const int mine = __hip_atomic_load(ctr + 4 + role, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) -
+                       __hip_atomic_load(ctr + role, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const int other = __hip_atomic_load(ctr + 5 - role, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) -
+                        __hip_atomic_load(ctr + 1 - role, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (__builtin_amdgcn_readfirstlane(mine) > 0) continue;  // (another wave was faster: ask again)
+      if (__builtin_amdgcn_readfirstlane(other) > 0) {
+        role = 1 - role;
+        continue;
+      }
+      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) break;
+      if (++polls > a.poll_cap) {  // the other waves hold what is left and carry it to its end
+        if ((threadIdx.x & 63) == 0) atomicAdd(a.bailouts, 1);
+        break;
+      }
+      __builtin_amdgcn_s_sleep(64);
+      continue;
+    }
+    polls = 0;
+    const bool held = have;
+    constexpr bool COLD = false;  // (no cold levels where this kernel runs)
+#define ROUND_LEAVE(n) false
+#define ROUND_BEFORE_LEAVE
+#define ROUND_PUT(kind_, pi_) sink.put(held && !have, kind_, pi_, p, next)
+    if (role == 0) {
+      int &steps = n_it;
+#include "rpkt_round.inc"
+    } else {
+      int &units = n_it;
+#include "thermal_round.inc"
+    }
+#undef ROUND_LEAVE
+#undef ROUND_BEFORE_LEAVE
+#undef ROUND_PUT
+  }
+  __syncthreads();
+  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
+}
+#endif
 
 // Tail kernel: the LAST few thousand r-packets and thermal packets of a timestep, one per lane, each carried through
 // r-packet steps, macro-atom walks and k-packet steps until it leaves these kinds (end of the timestep, escape, a
@@ -2533,6 +2668,9 @@ void ib_free(IbState *st);
 // What one artis_amd_update_packets_device call did: zeroed when the call begins, read by the artis_amd_last_* accessors.
 struct LastCall {
   double propagate_ms = 0., kms[NEXT_NKINDS] = {}, kms_tail = 0., fill_ms = 0.;  // summed launch durations: all, per kind, the tail kernel's; tile fills'
+  double kms_late = 0.;          // ... k_late's
+  int64_t late_launches = 0;
+  int64_t late_bailouts = 0;     // waves of k_late that gave up waiting for work (ARTIS_AMD_TRACE prints them)
   int64_t klaunches[NEXT_NKINDS] = {}, kthreads[NEXT_NKINDS] = {}, nlaunches = 0;
   // tiled runs: sweeps over the tiles, tile fills (sparse ones, cells filled), packets listed per (sweep, tile), packets parked
   int64_t sweeps = 0, tile_fills = 0, sparse_fills = 0, cells_filled = 0, listed = 0, parked = 0;
@@ -2641,6 +2779,14 @@ struct artis_amd_engine {
   // nltenebular step 1801 -> 1690 ms, profiles/r03/neb_sweep*.txt)
   int tail_max = ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON ? 16384 : 4096;  // r-packets + thermal packets left at which k_tail takes over (artis_amd_config.tail_threshold; 0 = never)
   bool tail_always = false;           // ... also for a population that starts below it (ARTIS_AMD_TAIL_ALWAYS=1)
+  // k_late: r-packets + thermal packets left at which one persistent launch takes over from the split kernels (ARTIS_AMD_LATE; 0 = never;
+  // chosen by a sweep on the headline, profiles/r08/late_kernel.md), for a population that began larger -- or any (ARTIS_AMD_LATE_ALWAYS=1)
+  int64_t late_max = 200000;
+  bool late_always = false;
+  bool late_strict = false;           // ARTIS_AMD_LATE_STRICT=1: a wave of k_late that gave up waiting fails the call (tests)
+  bool late_attr_set = false;         // k_late's dynamic-LDS attribute has been set on this engine's device
+  int32_t *d_late_ring[2] = {nullptr, nullptr};  // the workgroups' queues (allocated with the lists)
+  int32_t *d_late_bail = nullptr;     // the slot after the error flag
   // the cells a fill of a tiled cache works on (make_resident()). Sparse fills: a visit for which few packets wait makes the cells in which they
   // wait (and the cells around those) resident instead of a whole window. ARTIS_AMD_SPARSE_FILL=0: whole windows.
   int32_t *d_fill_cells = nullptr;
@@ -2775,6 +2921,9 @@ static void read_switches(artis_amd_engine *e) {
   if (const char *b = std::getenv("ARTIS_AMD_SORT_NU")) e->sort_nu = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_SORT_MA")) e->sort_ma = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_TAIL_ALWAYS")) e->tail_always = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_LATE")) e->late_max = std::max<int64_t>(0, std::atoll(b));
+  if (const char *b = std::getenv("ARTIS_AMD_LATE_ALWAYS")) e->late_always = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_LATE_STRICT")) e->late_strict = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_RPKT_EST_OVER_CONT")) e->rpkt_est_over_cont = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_DENSE_CONTLDS")) e->dense_cont_lds = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_MABINS")) e->ma_bins = (std::atoi(b) > 1) ? SORT_MABINS : 1;
@@ -2954,6 +3103,7 @@ int sort_list(artis_amd_engine *e, hipStream_t s, const int32_t *list, const int
 
 void free_packet_buffers(artis_amd_engine *e) {
   void **singles[] = {&e->d_pkt, &e->d_pkt_snapshot, (void **)&e->d_sorted, (void **)&e->d_perm, (void **)&e->d_gamma_ws,
+                      (void **)&e->d_late_ring[0], (void **)&e->d_late_ring[1],
                       (void **)&e->d_gamma_gi, (void **)&e->d_gamma_n, (void **)&e->d_bfev, (void **)&e->d_bfev_count,
                       (void **)&e->d_vpkt_queue, (void **)&e->d_vpkt_count};
   e->bfev_cap = 0;
@@ -2974,6 +3124,12 @@ void free_packet_buffers(artis_amd_engine *e) {
   e->use_perm = false;
 }
 
+// k_late may take the end of this engine's populations: a build with the kernel, k_tail allowed (no virtual packets, no deferred bound-free
+// events), the whole cache resident, no cold levels, and tables that fit the LDS
+bool late_possible(const artis_amd_engine *e) {
+  return ARTIS_LATE_KERNEL && e->late_max > 0 && e->tail_max > 0 && e->ntiles == 1 && e->Mh.ncold == 0 && e->Mh.nlevels > 0 && e->Mh.nlevels < 32768 &&
+         e->Mh.nalltrans > 0 && e->Mh.nbfcontinua > 0 && late_lds_bytes(e->Mh.nlevels, e->Mh.nalltrans, e->Mh.nbfcontinua) <= 160 * 1024 - 1024;
+}
 int ensure_packet_buffers(artis_amd_engine *e, int64_t n) {
   if (n == e->npackets && e->d_pkt) return ARTIS_OK;
   free_packet_buffers(e);
@@ -2988,6 +3144,9 @@ int ensure_packet_buffers(artis_amd_engine *e, int64_t n) {
     }
   HIP_TRY(hipMalloc((void **)&e->d_sorted, listbytes));
   HIP_TRY(hipMalloc((void **)&e->d_perm, listbytes));
+  if (late_possible(e)) {  // (80 MB at 1e7 packets: only for an engine that can launch k_late)
+    for (int k = 0; k < 2; k++) HIP_TRY(hipMalloc((void **)&e->d_late_ring[k], listbytes));
+  }
   if (const int rc = sort_scratch_alloc(e->sort_scratch, n)) return rc;
   e->ws_capacity = n > 0 ? n : 1;
   const size_t wsbytes = sizeof(double) * (size_t)(e->Mh.nbfcontinua_ground + 1) * (size_t)e->ws_capacity;
@@ -3557,10 +3716,11 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
 #endif
   HIP_TRY(hipMalloc((void **)&e->d_stats, sizeof(unsigned long long) * ARTIS_NSTATS));
   HIP_TRY(hipMemset(e->d_stats, 0, sizeof(unsigned long long) * ARTIS_NSTATS));
-  HIP_TRY(hipMalloc((void **)&e->d_count, sizeof(int32_t) * (2 * NEXT_NKINDS + 1)));
-  HIP_TRY(hipMemset(e->d_count, 0, sizeof(int32_t) * (2 * NEXT_NKINDS + 1)));
+  HIP_TRY(hipMalloc((void **)&e->d_count, sizeof(int32_t) * (2 * NEXT_NKINDS + 2)));
+  HIP_TRY(hipMemset(e->d_count, 0, sizeof(int32_t) * (2 * NEXT_NKINDS + 2)));
   e->d_err = e->d_count + (2 * NEXT_NKINDS);
-  HIP_TRY(hipHostMalloc((void **)&e->h_counts, sizeof(int32_t) * (2 * NEXT_NKINDS + 1), hipHostMallocDefault));
+  e->d_late_bail = e->d_err + 1;  // (k_late's count of waves that gave up waiting: travels with the counters)
+  HIP_TRY(hipHostMalloc((void **)&e->h_counts, sizeof(int32_t) * (2 * NEXT_NKINDS + 2), hipHostMallocDefault));
   HIP_TRY(hipMalloc((void **)&e->d_cursors, sizeof(int32_t) * (MAX_CHUNKS + 1)));  // + the launch's "list used up" flag
   HIP_TRY(hipMalloc((void **)&e->d_fill_cells, sizeof(int32_t) * (size_t)(ncell_all > 0 ? ncell_all : 1)));
   if (e->ntiles > 1) {  // rows for a set of cells at a time: the table of rows, no cell resident yet
@@ -4384,6 +4544,8 @@ int artis_amd_last_kernel_ms_by_kind(artis_amd_engine *e, double ms[8], int64_t 
   }
   ms[5] = e->last.kms_tail;
   ms[6] = e->last.fill_ms;
+  ms[7] = e->last.kms_late;
+  if (launches) launches[7] = e->last.late_launches;
   return ARTIS_OK;
 }
 

@@ -17,13 +17,15 @@ using Int = std::integral_constant<int, N>;  // a template argument chosen at ru
 // (device-wide atomics on one address are serialised in memory: 20^3 cells, 1e7 packets: k_thermal 907 ms sorted, 725 ms unsorted), while the locality
 // the sort buys matters less because fewer cells' tables compete for the caches. Models with so few cells that the kernels accumulate their per-cell
 // estimators in LDS (Env::cellest_lds) have no such atomics and are always sorted (6^3 cells: 494 ms sorted, 593 unsorted).
+// into: where the sorted list goes, if not e->d_sorted
 int sort_by_key(artis_amd_engine *e, hipStream_t s, const int32_t *list, const int32_t *keys, int32_t n, const int32_t **out, int nbins,
-                int64_t ncells, int max_per_cell, int32_t nkeys_given = 0) {
+                int64_t ncells, int max_per_cell, int32_t nkeys_given = 0, int32_t *into = nullptr) {
   *out = list;
   if (!e->sort_lists || n < 2 * BLOCK) return ARTIS_OK;
   if ((int64_t)n > (int64_t)max_per_cell * (ncells > 0 ? ncells : 1)) return ARTIS_OK;
-  STEP(sort_list(e, s, list, keys, n, nkeys_given > 0 ? (int64_t)nkeys_given : (int64_t)e->Mh.ngrid * nbins, e->d_sorted));
-  *out = e->d_sorted;
+  if (into == nullptr) into = e->d_sorted;
+  STEP(sort_list(e, s, list, keys, n, nkeys_given > 0 ? (int64_t)nkeys_given : (int64_t)e->Mh.ngrid * nbins, into));
+  *out = into;
   return ARTIS_OK;
 }
 #if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
@@ -48,6 +50,7 @@ void launch_bfest_dense(artis_amd_engine *e, const Env &env, hipStream_t s) {
 #endif
 // the text of a kernel's error flag. Flag 46 reads differently after a launch (the pool cannot hold one record) and at the call's end.
 std::string errflag_text(int32_t flag, bool at_call_end) {
+  if (flag == 47) return "k_late: a wave waited in vain for its turn to publish queue entries (error flag 47): a fault of the kernel's queue protocol";
   if (flag != 46) return "a kernel raised error flag " + std::to_string(flag) + " (an assert_always of the reference would have fired)";
   return std::string(at_call_end ? "a cell's pool of on-demand macro-atom records is used up"
                                  : "the pool of on-demand macro-atom records cannot hold a single record of this atomic data") +
@@ -101,7 +104,7 @@ struct PropRun {
     // (one copy into pinned memory: counters and error flag are neighbours. Two copies into the stack -- pageable, staged by the runtime -- were a
     // measurable share of the ~90 ms a headline step spends outside its kernels)
     const clk::time_point t_sync = clk::now();
-    HIP_TRY(hipMemcpyAsync(e->h_counts, e->d_count, sizeof(int32_t) * (2 * NEXT_NKINDS + 1), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(e->h_counts, e->d_count, sizeof(int32_t) * (2 * NEXT_NKINDS + 2), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     wall_sync += since(t_sync);
     std::memcpy(cnt, e->h_counts, sizeof(int32_t) * 2 * NEXT_NKINDS);
@@ -334,18 +337,75 @@ struct PropRun {
     STEP(flush_bf_events());
     return finish_launch(NEXT_SLOW, true, (int32_t)tail_n);
   }
+  // the current list of `kind`, sorted by its keys where lists of that kind are (*lst: the list to launch on; into: sort_by_key())
+  int sort_current(int kind, const int32_t **lst, int32_t *into = nullptr) {
+    *lst = e->d_lists[kind][cur[kind]];
+    if (kind == NEXT_RPKT || kind == NEXT_GAMMA || (kind == NEXT_MA && e->sort_ma)) {
+      STEP(sort_by_key(e, s, e->d_lists[kind][cur[kind]], e->d_keys[kind][cur[kind]], cnt[kind], lst,
+                       kind == NEXT_RPKT ? r_nubins : (kind == NEXT_MA ? e->ma_bins : 1), e->tile_cells,
+                       kind == NEXT_MA ? (env.cellest_n_t > 0 ? INT32_MAX : e->sort_maxpc_t) : (env.cellest_n_r > 0 ? INT32_MAX : e->sort_maxpc_r),
+                       (kind == NEXT_RPKT && r_nubins > 1 && e->sort_numajor) ? r_ngroups * r_nubins : 0, into));
+    }
+    return ARTIS_OK;
+  }
+  bool late_eligible() const { return late_possible(e) && e->d_late_ring[0] != nullptr; }  // (late_possible(): with the packet buffers)
+  // The r-packet and the thermal list go to k_late whole (sorted first, as for the split kernels: a workgroup's share is local in cell and
+  // frequency) and no packet comes back to them: what the kernel ejects goes to the CURRENT slow-path, blackbody and gamma-ray lists, which no
+  // wave reads during the launch (their entries so far stay where they are; the appends follow them).
+  int run_late() {
+#if ARTIS_LATE_KERNEL
+    LateArgs a;
+    const int kinds[2] = {NEXT_RPKT, NEXT_MA};
+    const clk::time_point t_sort = clk::now();
+    for (int i = 0; i < 2; i++) {
+      // (the second sort's output must not be the first's: the kind's alternate list is free, this launch has no kind of its own)
+      STEP(sort_current(kinds[i], &a.list[i], e->d_lists[kinds[i]][1 - cur[kinds[i]]]));
+      a.n[i] = cnt[kinds[i]];
+      a.ring[i] = e->d_late_ring[i];
+    }
+    wall_sort += since(t_sort);
+    a.bailouts = e->d_late_bail;
+    a.poll_cap = 1 << 20;  // x s_sleep 64: seconds
+    const size_t lds = late_lds_bytes(e->Mh.nlevels, e->Mh.nalltrans, e->Mh.nbfcontinua);
+    if (!e->late_attr_set) {  // (per engine, i.e. per device)
+      HIP_TRY(hipFuncSetAttribute((const void *)k_late, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+      e->late_attr_set = true;
+    }
+    for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(e->d_count + kinds[i], 0, sizeof(int32_t), s));
+    HIP_TRY(hipMemsetAsync(e->d_late_bail, 0, sizeof(int32_t), s));
+    HIP_TRY(hipEventRecord(e->ev0, s));
+    e->last.thermal_variants |= ARTIS_AMD_THERMAL_LATE;
+    hipLaunchKernelGGL(k_late, dim3(e->ncu), dim3(LATE_TB), lds, s, env, a, lists_for(0), e->d_stats);
+    HIP_TRY(hipEventRecord(e->ev1, s));
+    STEP(read_counts());
+    const int32_t bail = e->h_counts[(2 * NEXT_NKINDS) + 1];  // (the slot after the error flag: one pinned copy brings all)
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    e->last.nlaunches++;
+    e->last.kms_late += ms;
+    e->last.late_launches++;
+    e->last.late_bailouts += bail;
+    if (e->trace)
+      fprintf(stderr, "[artis_amd] launch %lld late n=%d+%d %.3f ms -> slow %d gamma %d bb %d; %d waves gave up waiting\n", (long long)e->last.nlaunches, a.n[0],
+              a.n[1], ms, cnt[NEXT_SLOW], cnt[NEXT_GAMMA], cnt[NEXT_BB], bail);
+    if (bail != 0 && e->late_strict) {
+      g_last_error = "k_late: " + std::to_string(bail) + " waves gave up waiting for work (ARTIS_AMD_LATE_STRICT=1)";
+      return ARTIS_ERR_NOTCONVERGED;
+    }
+    if (++guard > 2000000LL) {
+      g_last_error = "packet loop did not terminate";
+      return ARTIS_ERR_NOTCONVERGED;
+    }
+#endif
+    return ARTIS_OK;
+  }
   // one launch = the whole current list of one kind: sort it, launch its kernel and what follows the kernel
   int run_kind(int kind) {
     const int32_t nk = cnt[kind];
     const Lists next = lists_for(kind);
     const int32_t *lst = e->d_lists[kind][cur[kind]];
     const clk::time_point t_sort = clk::now();
-    if (kind == NEXT_RPKT || kind == NEXT_GAMMA || (kind == NEXT_MA && e->sort_ma)) {
-      STEP(sort_by_key(e, s, e->d_lists[kind][cur[kind]], e->d_keys[kind][cur[kind]], nk, &lst,
-                       kind == NEXT_RPKT ? r_nubins : (kind == NEXT_MA ? e->ma_bins : 1), e->tile_cells,
-                       kind == NEXT_MA ? (env.cellest_n_t > 0 ? INT32_MAX : e->sort_maxpc_t) : (env.cellest_n_r > 0 ? INT32_MAX : e->sort_maxpc_r),
-                       (kind == NEXT_RPKT && r_nubins > 1 && e->sort_numajor) ? r_ngroups * r_nubins : 0));
-    }
+    STEP(sort_current(kind, &lst));
     wall_sort += since(t_sort);
     t_launch = clk::now();
     if (kind == NEXT_SLOW) STEP(reset_pool_if_due());
@@ -400,12 +460,24 @@ struct PropRun {
     // the split kernels throughout, unless ARTIS_AMD_TAIL_ALWAYS=1)
     // (tiled runs: the later sweeps bring a tile a few stragglers at a time; each such visit is a tail from its first launch)
     const bool tail_ok = e->tail_max > 0 && (e->tail_always || listed > e->tail_max || sweep > 0 || (adaptive && e->last_visits > e->ntiles));
+    // k_late takes the r-packets and thermal packets of a population that began larger than late_max once that few are left (same rule; a small
+    // population stays on the split kernels unless ARTIS_AMD_LATE_ALWAYS=1); the kinds it ejects run on their own kernels between its launches
+    const bool late_ok = late_eligible() && (e->late_always || listed > e->late_max);
     while (count_listed() > 0) {
       const int64_t tail_n = count_tail();
       const bool tail_now = tail_ok && tail_n > 0 && tail_n <= e->tail_max && cnt[NEXT_KPKT] == 0;
       if (should_park(sweep, tile, tail_n, tail_now)) break;
       if (tail_now) {
         STEP(run_tail(tail_n));
+        continue;
+      }
+      // (r-packet + thermal + k-packet lists; and the blackbody list must not be longer than that either: a step's first round has most packets
+      // there, about to become r-packets, beside a short thermal list)
+      if (late_ok && cnt[NEXT_KPKT] == 0 && (int64_t)cnt[NEXT_RPKT] + cnt[NEXT_MA] <= e->late_max && cnt[NEXT_BB] <= e->late_max) {
+        if (cnt[NEXT_RPKT] + cnt[NEXT_MA] > 0) STEP(run_late());
+        for (int kind : order)
+          if (kind == NEXT_SLOW || kind == NEXT_GAMMA || kind == NEXT_BB)
+            if (cnt[kind] > 0) STEP(run_kind(kind));
         continue;
       }
       for (int kind : order)
@@ -459,7 +531,7 @@ extern "C" int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_st
     if (e->ntiles == 1 || !any_active || all_done) break;
   }
   for (int k = 1; k < NEXT_NKINDS; k++) e->last.propagate_ms += e->last.kms[k];
-  e->last.propagate_ms += e->last.kms_tail;
+  e->last.propagate_ms += e->last.kms_tail + e->last.kms_late;
   if (e->trace)
     fprintf(stderr, "[artis_amd] host time of the call: %.1f ms = %.1f waiting for the stream + %.1f submitting sorts + %.1f submitting launches + the rest; kernels by their events %.1f ms\n",
             PropRun::since(wall_t0), run.wall_sync, run.wall_sort, run.wall_launch, e->last.propagate_ms);

@@ -348,6 +348,7 @@ class Engine:
         return {"hot_fraction": h.value, "ncold": n.value, "pool_slots": p.value}
 
     THERMAL_PLAIN, THERMAL_LDS_TABLES, THERMAL_LDS_LEVELPACK, THERMAL_REFILL, THERMAL_COLD, THERMAL_TAIL = 1, 2, 4, 8, 16, 32
+    THERMAL_LATE = 64
 
     def last_thermal_variants(self) -> int:
         """mask of the thermal-kernel forms the last step() launched (include/artis_amd.h ARTIS_AMD_THERMAL_*)"""
@@ -429,7 +430,7 @@ class Engine:
         ms, nl = (C.c_double * 8)(), (C.c_int64 * 8)()
         self.L.artis_amd_last_kernel_ms_by_kind.argtypes = [C.c_void_p] * 3
         self._check(self.L.artis_amd_last_kernel_ms_by_kind(self.h, ms, nl))
-        names = ["k_rpkt", "k_thermal", "k_slow", "k_gamma", "k_blackbody", "k_tail", "tile_fills"]
+        names = ["k_rpkt", "k_thermal", "k_slow", "k_gamma", "k_blackbody", "k_tail", "tile_fills", "k_late"]
         return {n: {"ms": round(ms[i], 3), "launches": nl[i]} for i, n in enumerate(names)}
 
     def last_kernel_ms(self):
