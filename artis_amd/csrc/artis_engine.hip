@@ -26,6 +26,7 @@
 
 #include "model_build.h"
 #include "engine_config.h"
+#include "cache_residency.h"
 #include "physics.h"
 #include "radfield_fit.h"
 #include "ion_balance.h"
@@ -50,806 +51,7 @@ thread_local std::string g_last_error;
 
 constexpr int BLOCK = 256;
 
-// ------------------------------------------------------------------ populate kernels
-// The cells a fill works on: every cell (the whole cache at once, or a batch of it), or -- a tiled cache (Env::fill_cells) -- the listed ones: the cells
-// make_resident() gave rows to.
-__device__ inline int64_t fill_count(const Env &env) { return env.fill_cells ? env.nfill : (env.tile_hi - env.tile_lo); }
-__device__ inline int fill_cell(const Env &env, int64_t k) { return env.fill_cells ? env.fill_cells[k] : env.tile_lo + (int)k; }
-#ifndef ARTIS_MA_WAVE_FILL
-#define ARTIS_MA_WAVE_FILL 1  // a cold level's record filled by the wave (ma_fill_record_wave); 0: by the lane (physics.h ma_fill_record)
-#endif
-#ifndef ARTIS_COLD_COOLING_ONLY
-#define ARTIS_COLD_COOLING_ONLY 1  // the population evaluates of a cold level's transitions only the cooling terms (physics.h matrans_terms<true>)
-#endif
-__global__ void __launch_bounds__(BLOCK) k_levelpops(Env env) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int64_t total = fill_count(env) * env.M.nlevels;
-  if (i >= total) return;
-  populate_levelpop(env, fill_cell(env, i / env.M.nlevels), (int)(i % env.M.nlevels));
-}
-__global__ void __launch_bounds__(BLOCK) k_line_dpop(Env env) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int64_t total = fill_count(env) * env.M.nlines;
-  if (i >= total) return;
-  populate_line_dpop(env, fill_cell(env, i / env.M.nlines), (int)(i % env.M.nlines));
-}
-#if ARTIS_EXPOPAC_TABLES
-// calculate_expansion_opacities() for the cells of the resident tile, when the host did not hand the tables over
-__global__ void __launch_bounds__(BLOCK) k_expopac(Env env) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int64_t total = fill_count(env) * ARTIS_EXPOPAC_NBINS;
-  if (i >= total) return;
-  const int c = fill_cell(env, i / ARTIS_EXPOPAC_NBINS);
-  if (env.C.thick[c] == ARTIS_CELL_THICK) return;  // update_grid.cc:657
-  populate_expopac_bin(env, c, (int)(i % ARTIS_EXPOPAC_NBINS));
-}
-__global__ void __launch_bounds__(BLOCK) k_expopac_planck(Env env) {
-  const int64_t kf = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (kf >= fill_count(env)) return;
-  const int c = fill_cell(env, kf);
-  if (env.C.thick[c] == ARTIS_CELL_THICK) return;
-  populate_expopac_planck(env, c);
-}
-#endif
-#if ARTIS_OPT_NT_ON
-// every cell of the model (not a tile): the non-thermal ionisation rate coefficients and energy-rate sums
-__global__ void __launch_bounds__(BLOCK) k_nt_cells(Env env, int ncell) {
-  const int c = blockIdx.x * BLOCK + threadIdx.x;
-  if (c >= ncell) return;
-  if (!populate_nt_cell(env, c)) fail(env, 90);
-}
-#endif
-__global__ void __launch_bounds__(BLOCK) k_cell_scalars(Env env) {
-  const int64_t kf = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (kf >= fill_count(env)) return;
-  const int c = fill_cell(env, kf);
-  populate_chi_ff(env, c);
-}
-// one wave = one 64-bit word of a cell's keep bitmap: the ballot IS the word (globals.h:296-305)
-__global__ void __launch_bounds__(BLOCK) k_allcont(Env env) {
-  const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  const int64_t nwaves = fill_count(env) * env.M.nkeepwords;
-  if (wave >= nwaves) return;
-  const int c = fill_cell(env, wave / env.M.nkeepwords);
-  const int word = (int)(wave % env.M.nkeepwords);
-  const int i = word * 64 + lane;
-  bool keep = false;
-  if (i < env.M.nbfcontinua) keep = populate_allcont(env, c, i);
-  const unsigned long long bits = __ballot(keep);
-  if (lane == 0) env.K.allcont_keepbits[(krow(env, c) * env.M.nkeepwords) + word] = bits;
-}
-// one wave = one cell: the kept continua as a list, the count of kept continua below each bitmap word and the pairs in list
-// order (physics.h populate_keptlist; after k_allcont)
-__global__ void __launch_bounds__(BLOCK) k_keptlist(Env env) {
-  const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  if (wave >= fill_count(env)) return;
-  const int c = fill_cell(env, wave);
-  const int nw = env.M.nkeepwords;
-  const uint64_t *keep = env.K.allcont_keepbits + (krow(env, c) * nw);
-  int32_t *list = env.K.allcont_keptlist + (krow(env, c) * env.M.nbfcontinua);
-  int32_t *prefix = env.K.allcont_keepprefix + (krow(env, c) * nw);
-  const D2 *pair = env.K.allcont_pair + (krow(env, c) * env.M.nbfcontinua);
-  D2 *keptpair = env.K.allcont_keptpair + (krow(env, c) * env.M.nbfcontinua);
-  int base = 0;
-  for (int w0 = 0; w0 < nw; w0 += 64) {
-    const int j = w0 + lane;
-    unsigned long long word = (j < nw) ? keep[j] : 0ull;
-    const int pc = __popcll(word);
-    int incl = pc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(incl, o);
-      if (lane >= o) incl += v;
-    }
-    int at = base + incl - pc;
-    if (j < nw) prefix[j] = at;
-    while (word != 0ull) {
-      const int i = (j * 64) + __builtin_ctzll(word);
-      list[at] = i;
-      keptpair[at] = pair[i];
-      at++;
-      word &= word - 1ull;
-    }
-    base += __shfl(incl, 63);
-  }
-}
-__global__ void __launch_bounds__(BLOCK) k_corrphotoion(Env env, const int32_t *target_level) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int64_t total = fill_count(env) * env.M.nphixstargets_total;
-  if (i >= total) return;
-  const int c = fill_cell(env, i / env.M.nphixstargets_total);
-  const int k = (int)(i % env.M.nphixstargets_total);
-  const int ul = target_level[k];
-  populate_corrphotoion(env, c, ul, k - env.M.level_phixstargetstart[ul]);
-}
-// Bound-bound part of a cell's macro-atom records: one WAVE per (cell, block of alltrans entries), three passes over the
-// block's entries in LDS (round 4; rounds 2-3: a wave scan in registers whose serial steps -- one per position in the longest
-// segment of a 64-entry chunk, 18 instructions each for all 64 lanes -- were 11 % of the population with ~9 transitions per
-// direction and 26 % with ~25):
-//   1. every lane evaluates the rate coefficients of its transitions (every lane busy, whatever the levels' transition counts)
-//      and leaves the three terms each adds to its level's running sums (macroatom.cc:64-140) in LDS;
-//   2. ONE LANE PER SEGMENT (a level's downward or upward transitions) adds its segment's terms up in the reference's order --
-//      the additions of the sequential form (physics.h populate_level_bb / populate_dirfilter_seq), so the same bits -- 10-30
-//      segments side by side, and writes the level's rates;
-//   3. every lane turns its transitions' sums into filter entries (tables.h "FILTERS": fractions of the segment's last sum); a
-//      line is usable when every one of its entries is a finite fraction (a flag per line in LDS).
-// A segment longer than a block (DevModel::malongsegs) is a block of its own: its rates are summed here 64 terms at a time, its
-// filters written by k_mafilter_long.
-// the value of the lane below (lane 0: 0), as two DPP wave-shift moves
-__device__ inline double wave_shr1(double x) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0x138, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-// the lanes of the wave that hold the entries of this lane's filter line (7 transitions of one direction: consecutive lanes)
-__device__ inline unsigned long long line_lanes(int lane, int ti, int seglen) {
-  const int first = lane - (ti % MAREC_PER);
-  const int left = seglen - (ti - (ti % MAREC_PER));
-  const int cnt = left < MAREC_PER ? left : MAREC_PER;
-  return ((1ull << cnt) - 1ull) << first;
-}
-// where entry e of a block (alltrans index a0 + e) sits in its segment
-struct MaEntryPos {
-  LevelPack lpk;
-  int ti, seglen, e_seg0;  // index within the direction, the direction's transitions, the block entry of the direction's first
-  bool isdown;
-};
-__device__ inline MaEntryPos ma_entry_pos(const DevModel &M, int a0, int e) {
-  MaEntryPos r;
-  r.lpk = M.level_pack[M.alltrans_owner[a0 + e]];
-  const int i = (a0 + e) - r.lpk.alltrans_startdown;
-  r.isdown = i < r.lpk.ndown;
-  r.ti = r.isdown ? i : i - r.lpk.ndown;
-  r.seglen = r.isdown ? r.lpk.ndown : r.lpk.nup;
-  r.e_seg0 = e - r.ti;
-  return r;
-}
-__global__ void __launch_bounds__(BLOCK, 4) k_matrans(Env env) {
-  __shared__ double lds_v[BLOCK / 64][3][MATRANS_BLOCK];          // the terms, then the running sums
-  __shared__ uint16_t lds_q[BLOCK / 64][2][MATRANS_BLOCK];        // filter entries: internal, radiative
-  __shared__ uint8_t lds_qf[BLOCK / 64][MATRANS_BLOCK];           // ... the internal entries' fine bytes (tables.h "FINE BYTES")
-  __shared__ uint8_t lds_ok[BLOCK / 64][2][MATRANS_BLOCK];        // per filter line (at its first entry): every entry a finite fraction
-  const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const DevModel &M = env.M;
-  const int nblk = M.nscanblk;
-  if (wave >= fill_count(env) * nblk) return;
-  const int64_t kf = wave / nblk;
-  const int c = fill_cell(env, kf);
-  const int blk = (int)(wave % nblk);
-  const int seg0 = M.scanblk_seg0[blk], seg1 = M.scanblk_seg0[blk + 1];
-  const MaLongSeg sfirst = M.scansegs[seg0], slast = M.scansegs[seg1 - 1];
-  const int a0 = sfirst.ats0, nent = (slast.ats0 + slast.n) - a0;
-  U4 *row = env.K.macache + (krow(env, c) * M.nmacache);
-  double *upterms = env.collexc_terms + (kf * M.nupcum);
-  double(*v)[MATRANS_BLOCK] = lds_v[w];
-  if (nent > MATRANS_BLOCK) {
-    // one long segment: its rates, 64 terms at a time (lane k adds its term to the finished sum of lane k - 1; lane 0 takes the carry)
-    const LevelPack lpk = M.level_pack[sfirst.ul];
-    double c0 = 0., c1 = 0., c2 = 0.;
-    for (int base = 0; base < nent; base += 64) {
-      const bool valid = base + lane < nent;
-      MaTransTerms t;
-      t.v0 = t.v1 = t.v2 = t.kterm = 0.;
-      if (valid) {
-        t = matrans_terms<ARTIS_COLD_COOLING_ONLY != 0>(env, c, a0 + base + lane);
-        if (!t.isdown) upterms[M.level_upcum_start[t.ul] + t.i] = t.kterm;
-      }
-      double s0 = (lane == 0 ? c0 : 0.) + t.v0, s1 = (lane == 0 ? c1 : 0.) + t.v1, s2 = (lane == 0 ? c2 : 0.) + t.v2;
-      for (int k = 1; k < 64; k++) {
-        const double p0 = wave_shr1(s0), p1 = wave_shr1(s1), p2 = wave_shr1(s2);
-        if (lane == k) {
-          s0 = p0 + t.v0;
-          s1 = p1 + t.v1;
-          s2 = p2 + t.v2;
-        }
-      }
-      const int last = (nent - base < 64 ? nent - base : 64) - 1;
-      c0 = __shfl(s0, last);
-      c1 = __shfl(s1, last);
-      c2 = __shfl(s2, last);
-    }
-    if (lane == 0 && lpk.rec_off >= 0) {  // (a cold level has no static record: only its cooling terms above are kept)
-      double *rates = ma_rates_of(row + lpk.rec_off, lpk.ndown, lpk.nup);
-      if (sfirst.dir == 0) {
-        rates[ARTIS_MA_ACTION_RADDEEXC] = c0;
-        rates[ARTIS_MA_ACTION_COLDEEXC] = c1;
-        rates[ARTIS_MA_ACTION_INTERNALDOWNSAME] = c2;
-      } else {
-        rates[ARTIS_MA_ACTION_INTERNALUPSAME] = c0;
-      }
-    }
-    return;
-  }
-  // 1. the terms (the block's entries in the order of DevModel::scanperm: a wave's 64 entries are of one kind wherever the block has 64 of it)
-  for (int k = lane; k < nent; k += 64) {
-    const int e = M.scanperm[a0 + k];
-    const MaTransTerms t = matrans_terms<ARTIS_COLD_COOLING_ONLY != 0>(env, c, a0 + e);
-    v[0][e] = t.v0;
-    v[1][e] = t.v1;
-    v[2][e] = t.v2;
-    lds_ok[w][0][e] = 1;
-    lds_ok[w][1][e] = 1;
-    if (!t.isdown) upterms[M.level_upcum_start[t.ul] + t.i] = t.kterm;
-  }
-  __threadfence_block();  // (the passes exchange data between the lanes of this wave through LDS: in order, but the compiler must not move them)
-  // 2. the running sums, a lane per segment
-  for (int si = seg0 + lane; si < seg1; si += 64) {
-    const MaLongSeg sg = M.scansegs[si];
-    const int o = sg.ats0 - a0;
-    double s0 = 0., s1 = 0., s2 = 0.;
-    for (int i = 0; i < sg.n; i++) {
-      s0 += v[0][o + i];
-      s1 += v[1][o + i];
-      s2 += v[2][o + i];
-      v[0][o + i] = s0;
-      v[2][o + i] = s2;
-    }
-    const LevelPack lpk = M.level_pack[sg.ul];
-    if (lpk.rec_off < 0) continue;
-    double *rates = ma_rates_of(row + lpk.rec_off, lpk.ndown, lpk.nup);
-    if (sg.dir == 0) {
-      rates[ARTIS_MA_ACTION_RADDEEXC] = s0;
-      rates[ARTIS_MA_ACTION_COLDEEXC] = s1;
-      rates[ARTIS_MA_ACTION_INTERNALDOWNSAME] = s2;
-    } else {
-      rates[ARTIS_MA_ACTION_INTERNALUPSAME] = s0;
-    }
-  }
-  __threadfence_block();
-  // 3a. the filter entries of every transition: its running sums as fractions of the direction's last ones
-  for (int e = lane; e < nent; e += 64) {
-    const MaEntryPos ps = ma_entry_pos(M, a0, e);
-    const int e_last = ps.e_seg0 + ps.seglen - 1;
-    const double whole_int = v[ps.isdown ? 2 : 0][e_last], whole_rad = v[0][e_last];
-    bool ok_int = (whole_int > 0.) && (whole_int <= DBLMAX), ok_rad = (whole_rad > 0.) && (whole_rad <= DBLMAX);
-    uint32_t q_int = MAFILT_NONE23, q_rad = MAFILT_NONE;
-    if (ps.ti < ps.seglen - 1) {
-      if (ok_int) q_int = mafilt_quant23(v[ps.isdown ? 2 : 0][e], whole_int, &ok_int);
-      if (ok_rad && ps.isdown) q_rad = mafilt_quant(v[0][e], whole_rad, &ok_rad);
-    }
-    lds_q[w][0][e] = (uint16_t)(q_int >> 8);
-    lds_qf[w][e] = (uint8_t)(q_int & 0xFFu);
-    lds_q[w][1][e] = (uint16_t)q_rad;
-    const int e_line = e - (ps.ti % MAREC_PER);
-    if (!ok_int) lds_ok[w][0][e_line] = 0;
-    if (ps.isdown && !ok_rad) lds_ok[w][1][e_line] = 0;
-  }
-  __threadfence_block();
-  // 3b. ... into the records: the entries of a line that is not usable are 0, its mark too
-  for (int e = lane; e < nent; e += 64) {
-    const MaEntryPos ps = ma_entry_pos(M, a0, e);
-    if (ps.lpk.rec_off < 0) continue;
-    const int e_line = e - (ps.ti % MAREC_PER);
-    U4 *rec = row + ps.lpk.rec_off;
-    const bool lok_int = lds_ok[w][0][e_line] != 0;
-    U4 *line = rec + marec_slot(ps.isdown ? MADIR_DOWN : MADIR_UP, ps.ti / MAREC_PER, ps.lpk.ndown, ps.lpk.nup);
-    mafilt_put(line, ps.ti % MAREC_PER, lok_int ? lds_q[w][0][e] : 0u);
-    ((uint8_t *)rec)[marec_fine_byte0(ps.isdown ? MADIR_DOWN : MADIR_UP, ps.ti / MAREC_PER, ps.lpk.ndown, ps.lpk.nup) + (ps.ti % MAREC_PER)] =
-        lok_int ? lds_qf[w][e] : (uint8_t)0u;
-    if (ps.ti % MAREC_PER == 0) mafilt_put(line, 7, lok_int ? MAFILT_NONE : 0u);  // the line's "usable" mark
-    if (ps.isdown) {
-      const bool lok_rad = lds_ok[w][1][e_line] != 0;
-      U4 *rline = rec + marec_slot(MADIR_RAD, ps.ti / MAREC_PER, ps.lpk.ndown, ps.lpk.nup);
-      mafilt_put(rline, ps.ti % MAREC_PER, lok_rad ? lds_q[w][1][e] : 0u);
-      if (ps.ti % MAREC_PER == 0) mafilt_put(rline, 7, lok_rad ? MAFILT_NONE : 0u);
-    }
-  }
-}
-__device__ inline double row_shr1(double x);
-// The recombination sums of a level (macroatom.cc:147-168: over the levels of the ion below that ionise into it) -- three running sums
-// over up to ~60 channels for the 45 levels of the bench's data that have any, none for the other 1522. As a loop of populate_macroatom()
-// the lane of such a level walked its list with three dependent gathers per channel while the other 63 lanes of its wave waited
-// (k_macroatom at 0.21 lane utilisation). Here a ROW OF 16 LANES per (cell, listed level) reads 16 channels at a time and forms the
-// sums with the loop's additions in the loop's order (lane k adds its term to lane k-1's finished sum, as k_cooling_chain does).
-__global__ void __launch_bounds__(BLOCK) k_macroatom_recomb(Env env) {
-  const int64_t row_id = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 4;
-  const int r = threadIdx.x & 15;
-  const DevModel &M = env.M;
-  const int64_t nrows = fill_count(env) * M.nrecomblevels;
-  const bool valid = row_id < nrows;
-  const int c = fill_cell(env, (valid ? row_id : 0) / M.nrecomblevels);
-  const int ul = M.recomb_levels[(valid ? row_id : 0) % M.nrecomblevels];
-  const int ui = M.level_ion[ul];
-  const int ls = M.ion_uniquelevelindexstart[ui > 0 ? ui - 1 : 0];
-  const int64_t cb = krow(env, c) * M.nphixstargets_total;
-  const double e_cur = eps(M, ul);
-  const int j0 = valid ? M.level_recomb_start[ul] : 0, j1 = valid ? M.level_recomb_start[ul + 1] : 0;
-  double carry0 = 0., carry1 = 0., carry2 = 0.;
-  for (int j = j0; __any(j < j1); j += 16) {
-    const bool in = (j + r) < j1;
-    double x0 = 0., x1 = 0., x2 = 0.;
-    if (in) {
-      const int lower = M.recomb_lower[j + r];
-      const int t = M.recomb_target[j + r];
-      const double e_target = eps(M, ls + lower);
-      const double e_trans = e_cur - e_target;
-      const int64_t o = cb + M.level_phixstargetstart[ls + lower] + t;
-      const double R = env.K.bf_radrecomb[o];
-      const double Cc = env.K.bf_colrecomb[o];
-      x0 = (R + Cc) * e_target;
-      x1 = R * e_trans;
-      x2 = Cc * e_trans;
-    }
-    double a0 = (r == 0) ? carry0 + x0 : x0, a1 = (r == 0) ? carry1 + x1 : x1, a2 = (r == 0) ? carry2 + x2 : x2;
-#pragma unroll
-    for (int s = 1; s < 16; s++) {
-      const double p0 = row_shr1(a0), p1 = row_shr1(a1), p2 = row_shr1(a2);
-      if (r == s) {
-        a0 = p0 + x0;
-        a1 = p1 + x1;
-        a2 = p2 + x2;
-      }
-    }
-    // the sums after the row's last channel, broadcast to the row (lanes past the list's end added 0. to them)
-    const int src = ((threadIdx.x & 63) | 15) << 2;
-    carry0 = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(a0)), __builtin_amdgcn_ds_bpermute(src, __double2loint(a0)));
-    carry1 = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(a1)), __builtin_amdgcn_ds_bpermute(src, __double2loint(a1)));
-    carry2 = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(a2)), __builtin_amdgcn_ds_bpermute(src, __double2loint(a2)));
-  }
-  if (valid && r == 0) {
-    const LevelPack lpk = M.level_pack[ul];
-    double *rates = ma_rates_of(ma_rec_of(env, c, lpk), lpk.ndown, lpk.nup);
-    rates[ARTIS_MA_ACTION_INTERNALDOWNLOWER] = carry0;
-    rates[ARTIS_MA_ACTION_RADRECOMB] = carry1;
-    rates[ARTIS_MA_ACTION_COLRECOMB] = carry2;
-  }
-}
-__global__ void __launch_bounds__(BLOCK) k_macroatom(Env env) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int64_t total = fill_count(env) * env.M.nlevels;
-  if (i >= total) return;
-  if (env.M.level_pack[i % env.M.nlevels].rec_off < 0) return;  // (a cold level: filled when a packet reaches it, physics.h ma_slow_fill)
-  populate_macroatom<true>(env, fill_cell(env, i / env.M.nlevels), (int)(i % env.M.nlevels));
-}
-// The filters of the directions with more transitions than a block of k_matrans holds (DevModel::malongsegs: > MATRANS_BLOCK):
-// a wave per (cell, segment) re-forms the running sums 63 transitions (nine filter lines) at a time -- the same terms
-// added in the same order, lane k to the finished sum of lane k-1 -- and quantises them with the direction's whole rates,
-// which k_matrans has left in the record. (physics.h populate_dirfilter_seq is the sequential form.)
-__global__ void __launch_bounds__(BLOCK) k_mafilter_long(Env env) {
-  const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  const int nseg = env.M.nmalongsegs;
-  if (wave >= fill_count(env) * nseg) return;
-  const int c = fill_cell(env, wave / nseg);
-  const MaLongSeg seg = env.M.malongsegs[wave % nseg];
-  const LevelPack lpk = env.M.level_pack[seg.ul];
-  U4 *rec = env.K.macache + (krow(env, c) * env.M.nmacache) + lpk.rec_off;
-  const double *rates = ma_rates_of(rec, lpk.ndown, lpk.nup);
-  const bool down = seg.dir == 0;
-  const double whole_int = rates[down ? ARTIS_MA_ACTION_INTERNALDOWNSAME : ARTIS_MA_ACTION_INTERNALUPSAME];
-  const double whole_rad = rates[ARTIS_MA_ACTION_RADDEEXC];
-  double ca = 0., cb = 0.;
-  for (int base = 0; base < seg.n; base += 63) {
-    const int ti = base + lane;
-    const bool valid = lane < 63 && ti < seg.n;
-    double a = 0., b = 0.;
-    if (valid) {
-      const MaTransTerms t = matrans_terms(env, c, seg.ats0 + ti);
-      a = down ? t.v2 : t.v0;
-      b = down ? t.v0 : 0.;
-    }
-    double sa = (lane == 0 ? ca : 0.) + a, sb = (lane == 0 ? cb : 0.) + b;
-    for (int k = 1; k < 63; k++) {
-      const double pa = wave_shr1(sa), pb = wave_shr1(sb);
-      if (lane == k) {
-        sa = pa + a;
-        sb = pb + b;
-      }
-    }
-    bool ok_int = (whole_int > 0.) && (whole_int <= DBLMAX), ok_rad = (whole_rad > 0.) && (whole_rad <= DBLMAX);
-    uint32_t q_int = MAFILT_NONE23, q_rad = MAFILT_NONE;
-    if (valid && ti < seg.n - 1) {
-      if (ok_int) q_int = mafilt_quant23(sa, whole_int, &ok_int);
-      if (ok_rad && down) q_rad = mafilt_quant(sb, whole_rad, &ok_rad);
-    }
-    const unsigned long long bad_int = __ballot(valid && !ok_int), bad_rad = __ballot(valid && down && !ok_rad);
-    if (valid) {
-      const unsigned long long mine = line_lanes(lane, ti, seg.n);  // (63 lanes = nine whole lines: lane % 7 == ti % 7)
-      const bool lok_int = (bad_int & mine) == 0ull, lok_rad = (bad_rad & mine) == 0ull;
-      U4 *line = rec + marec_slot(down ? MADIR_DOWN : MADIR_UP, ti / MAREC_PER, lpk.ndown, lpk.nup);
-      mafilt_put23(rec, down ? MADIR_DOWN : MADIR_UP, ti, lpk.ndown, lpk.nup, lok_int ? q_int : 0u);
-      if (ti % MAREC_PER == 0) mafilt_put(line, 7, lok_int ? MAFILT_NONE : 0u);
-      if (down) {
-        U4 *rline = rec + marec_slot(MADIR_RAD, ti / MAREC_PER, lpk.ndown, lpk.nup);
-        mafilt_put(rline, ti % MAREC_PER, lok_rad ? q_rad : 0u);
-        if (ti % MAREC_PER == 0) mafilt_put(rline, 7, lok_rad ? MAFILT_NONE : 0u);
-      }
-    }
-    const int last = (seg.n - base < 63 ? seg.n - base : 63) - 1;
-    ca = __shfl(sa, last);
-    cb = __shfl(sb, last);
-  }
-}
-// ---- A cold level's record filled by a WAVE (tables.h "ON-DEMAND RECORDS"; physics.h ma_fill_record is the sequential form, which one lane of
-// the slow-path kernel ran in the first version: 585 ms of a 6.5 s step with the w7big data, most of the 3.3 s of k_slow with cd23like). The
-// transitions' terms -- the expensive part: rate coefficients with exp() and divisions -- are evaluated by 63 lanes side by side; the running
-// sums are formed in the sequential loop's order (lane j ends with carry + t_0 + ... + t_j, added left to right); each lane quantises its own
-// entry, a filter line's "usable" mark is a vote of its lanes (as in k_mafilter_long); lane 0 writes the rates and runs the bound-free part
-// and the action filter (populate_macroatom). Same terms, same additions in the same order: the same bits (GPU test: the records a run
-// left in the pool against populate_dirfilter_seq, artis_amd_debug_cellcache()).
-__device__ inline double wave_prefix_inorder(double t, double carry, int n, int lane) {
-  double acc = carry;
-  for (int k = 0; k < n; k++) {
-    const double x = wave_bcast(t, k);
-    if (lane >= k) acc += x;
-  }
-  return acc;
-}
-// ... NS running sums at once, through LDS (round 6): the lanes leave their terms in the wave's own rows, lane j < NS adds row j up from left to
-// right -- the same additions in the same order, so the same bits -- and every lane reads its sums back. As broadcasts and masked additions the
-// three sums of a block of 63 transitions were ~950 wave instructions; this is 63 dependent additions by three lanes side by side (the fills
-// of the 4e5-line set: 2.1 s of its 17 s step).
-constexpr int PREFIX_ROWS = 3;
-// the wave's rows (one set for all instantiations: 12 KB per workgroup of BLOCK threads)
-__device__ inline double (*prefix_rows(bool out))[64] {
-  __shared__ double rows_in[BLOCK / 64][PREFIX_ROWS][64];
-  __shared__ double rows_out[BLOCK / 64][PREFIX_ROWS][64];
-  const int w = (int)(threadIdx.x >> 6) % (BLOCK / 64);
-  return out ? rows_out[w] : rows_in[w];
-}
-template <int NS>
-__device__ inline void wave_prefix_inorder_n(const double (&t)[NS], const double (&carry)[NS], int n, int lane, double (&out)[NS]) {
-  static_assert(NS <= PREFIX_ROWS, "rows");
-  double(*rin)[64] = prefix_rows(false);
-  double(*rout)[64] = prefix_rows(true);
-#pragma unroll
-  for (int j = 0; j < NS; j++) rin[j][lane] = t[j];
-  __threadfence_block();  // (lanes of one wave exchange data through LDS: in order, but the compiler must not move the accesses)
-  if (lane < NS) {
-    double acc = 0.;
-#pragma unroll
-    for (int j = 0; j < NS; j++) acc = (lane == j) ? carry[j] : acc;
-    const double *in = rin[lane];
-    double *o = rout[lane];
-    for (int k = 0; k < n; k++) {
-      acc += in[k];
-      o[k] = acc;
-    }
-  }
-  __threadfence_block();
-  const int k = (lane < n) ? lane : n - 1;  // (a lane past the block's last transition holds the block's total, as wave_prefix_inorder() gives it)
-#pragma unroll
-  for (int j = 0; j < NS; j++) out[j] = rout[j][k];
-  __threadfence_block();  // (the next call writes the rows again)
-}
-// the entries of one block (lanes 0..62 = transitions base .. base + 62 of a direction of n) into the record: internal filter from s_int,
-// radiative filter (downward only) from s_rad
-__device__ inline void wave_put_dirfilters(U4 *rec, const LevelPack &lpk, bool down, int n, int ti, bool valid, double s_int, double s_rad,
-                                           double whole_int, double whole_rad, int lane) {
-  bool ok_int = (whole_int > 0.) && (whole_int <= DBLMAX), ok_rad = (whole_rad > 0.) && (whole_rad <= DBLMAX);
-  uint32_t q_int = MAFILT_NONE23, q_rad = MAFILT_NONE;
-  if (valid && ti < n - 1) {
-    if (ok_int) q_int = mafilt_quant23(s_int, whole_int, &ok_int);
-    if (ok_rad && down) q_rad = mafilt_quant(s_rad, whole_rad, &ok_rad);
-  }
-  const unsigned long long bad_int = __ballot(valid && !ok_int), bad_rad = __ballot(valid && down && !ok_rad);
-  if (valid) {
-    const unsigned long long mine = line_lanes(lane, ti, n);
-    const bool lok_int = (bad_int & mine) == 0ull, lok_rad = (bad_rad & mine) == 0ull;
-    U4 *line = rec + marec_slot(down ? MADIR_DOWN : MADIR_UP, ti / MAREC_PER, lpk.ndown, lpk.nup);
-    mafilt_put23(rec, down ? MADIR_DOWN : MADIR_UP, ti, lpk.ndown, lpk.nup, lok_int ? q_int : 0u);
-    if (ti % MAREC_PER == 0) mafilt_put(line, 7, lok_int ? MAFILT_NONE : 0u);
-    if (down) {
-      U4 *rline = rec + marec_slot(MADIR_RAD, ti / MAREC_PER, lpk.ndown, lpk.nup);
-      mafilt_put(rline, ti % MAREC_PER, lok_rad ? q_rad : 0u);
-      if (ti % MAREC_PER == 0) mafilt_put(rline, 7, lok_rad ? MAFILT_NONE : 0u);
-    }
-  }
-}
-__device__ inline void ma_fill_record_wave(const Env &env, int c, int ul) {
-  const DevModel &M = env.M;
-  const int lane = (int)(threadIdx.x & 63);
-  const LevelPack lpk = M.level_pack[ul];
-  U4 *rec = ma_rec_of(env, c, lpk);
-  const int nd = lpk.ndown, nu = lpk.nup;
-  {  // populate_mainit_at(): every filter entry "never counted", the rates zero
-    const int nfilt = marec_rates_slot(nd, nu), nfine0 = marec_fine_slot0(nd, nu), nrec = marec_slots(nd, nu);
-    const int ntot = ((nrec + MAREC_ALIGN - 1) / MAREC_ALIGN) * MAREC_ALIGN;
-    const uint32_t none2 = MAFILT_NONE | (MAFILT_NONE << 16);
-    for (int i = lane; i < ntot; i += 64)
-      rec[i] = (i < nfilt) ? U4{{none2, none2, none2, none2}} : ((i >= nfine0 && i < nrec) ? U4{{~0u, ~0u, ~0u, ~0u}} : U4{{0u, 0u, 0u, 0u}});
-  }
-  __threadfence_block();  // (other lanes write into these slots below)
-  // ---- downward: rates (radiative, collisional de-excitation, internal down), then the internal-down and radiative filters
-  double w_rad = 0., w_col = 0., w_down = 0.;
-  double b0_rad = 0., b0_down = 0.;  // block 0's running sums, kept for a direction of one block (no second evaluation of its terms)
-  for (int base = 0; base < nd; base += 63) {
-    const int nb = (nd - base < 63) ? nd - base : 63;
-    const bool valid = lane < nb;
-    double v0 = 0., v1 = 0., v2 = 0.;
-    if (valid) {
-      const MaTransTerms t = matrans_terms(env, c, lpk.alltrans_startdown + base + lane);
-      v0 = t.v0; v1 = t.v1; v2 = t.v2;
-    }
-    double ss[3];
-    wave_prefix_inorder_n<3>({v0, v1, v2}, {w_rad, w_col, w_down}, nb, lane, ss);
-    const double s0 = ss[0], s1 = ss[1], s2 = ss[2];
-    if (base == 0) { b0_rad = s0; b0_down = s2; }
-    w_rad = wave_bcast(s0, nb - 1);
-    w_col = wave_bcast(s1, nb - 1);
-    w_down = wave_bcast(s2, nb - 1);
-  }
-  if (nd > 0 && nd <= 63) {
-    wave_put_dirfilters(rec, lpk, true, nd, lane, lane < nd, b0_down, b0_rad, w_down, w_rad, lane);
-  } else {
-    double c_rad = 0., c_down = 0.;
-    for (int base = 0; base < nd; base += 63) {
-      const int nb = (nd - base < 63) ? nd - base : 63;
-      const bool valid = lane < nb;
-      double v0 = 0., v2 = 0.;
-      if (valid) {
-        const MaTransTerms t = matrans_terms(env, c, lpk.alltrans_startdown + base + lane);
-        v0 = t.v0; v2 = t.v2;
-      }
-      double ss[2];
-      wave_prefix_inorder_n<2>({v0, v2}, {c_rad, c_down}, nb, lane, ss);
-      const double s0 = ss[0], s2 = ss[1];
-      wave_put_dirfilters(rec, lpk, true, nd, base + lane, valid, s2, s0, w_down, w_rad, lane);
-      c_rad = wave_bcast(s0, nb - 1);
-      c_down = wave_bcast(s2, nb - 1);
-    }
-  }
-  // ---- upward: the internal-up rate and filter, and the level's collisional-excitation cooling filter (running sums from the
-  // cooling list's value before the level; populate_coolfilter_level_seq)
-  const int hi_i = M.level_coolhi[ul];
-  const double *cool = env.K.cooling_contrib + (krow(env, c) * M.ncoolingterms);
-  const double c_hi = (nu > 0 && hi_i >= 0) ? cool[hi_i] : 0.;
-  const double c_lo = (nu > 0 && hi_i > M.ion_coolingoffset[M.level_ion[ul]]) ? cool[hi_i - 1] : 0.;
-  const double span = c_hi - c_lo;
-  double w_up = 0.;
-  double b0_up = 0., b0_kt = 0.;
-  for (int base = 0; base < nu; base += 63) {
-    const int nb = (nu - base < 63) ? nu - base : 63;
-    double v0 = 0., kt = 0.;
-    if (lane < nb) {
-      const MaTransTerms t = matrans_terms(env, c, lpk.alltrans_startdown + nd + base + lane);
-      v0 = t.v0; kt = t.kterm;
-    }
-    double ss[1];
-    wave_prefix_inorder_n<1>({v0}, {w_up}, nb, lane, ss);
-    const double s0 = ss[0];
-    if (base == 0) { b0_up = s0; b0_kt = kt; }
-    w_up = wave_bcast(s0, nb - 1);
-  }
-  {
-    double c_up = 0., c_cool = c_lo;
-    for (int base = 0; base < nu; base += 63) {
-      const int nb = (nu - base < 63) ? nu - base : 63;
-      const bool valid = lane < nb;
-      const int ti = base + lane;
-      double v0 = 0., kt = b0_kt;
-      if (valid && nu > 63) {  // (a direction of one block keeps its terms from the pass above)
-        const MaTransTerms t = matrans_terms(env, c, lpk.alltrans_startdown + nd + base + lane);
-        v0 = t.v0; kt = t.kterm;
-      }
-      // (the internal-up sums again -- a direction of one block keeps them from the pass above -- and the cooling terms' sums from the list's
-      // value before the level, side by side)
-      double ss[2];
-      wave_prefix_inorder_n<2>({v0, kt}, {c_up, c_cool}, nb, lane, ss);
-      const double s0 = (nu <= 63) ? b0_up : ss[0];
-      wave_put_dirfilters(rec, lpk, false, nu, ti, valid, s0, 0., w_up, 0., lane);
-      c_up = wave_bcast(s0, nb - 1);
-      if (hi_i >= 0) {
-        const double sk = ss[1];
-        bool ok = (span > 0.) && (span <= DBLMAX);
-        uint32_t q = MAFILT_NONE;
-        if (valid && ti < nu - 1 && ok) q = mafilt_quant(sk - c_lo, span, &ok);
-        const unsigned long long bad = __ballot(valid && !ok);
-        if (valid) {
-          const bool lok = (bad & line_lanes(lane, ti, nu)) == 0ull;
-          U4 *line = rec + marec_slot(MADIR_COOL, ti / MAREC_PER, nd, nu);
-          if (lok) {
-            mafilt_put(line, ti % MAREC_PER, q);
-          } else if (ti % MAREC_PER == 0) {
-            *line = U4{{0u, 0u, 0u, 0u}};  // (populate_coolfilter_line: a line that is not usable is all zero, its mark too)
-          }
-        }
-        c_cool = wave_bcast(sk, nb - 1);
-      }
-    }
-  }
-  __threadfence_block();
-  if (lane == 0) {
-    double *rates = ma_rates_of(rec, nd, nu);
-    rates[ARTIS_MA_ACTION_RADDEEXC] = w_rad;
-    rates[ARTIS_MA_ACTION_COLDEEXC] = w_col;
-    rates[ARTIS_MA_ACTION_INTERNALDOWNSAME] = w_down;
-    rates[ARTIS_MA_ACTION_INTERNALUPSAME] = w_up;
-    populate_macroatom<false>(env, c, ul);  // the bound-free channels and the action filter
-  }
-}
-// every lane of the wave whose packet waits for a record it has claimed (physics.h ma_slow_fill_claim) gets it filled, lane by lane
-__device__ inline void ma_fill_wave(const Env &env, bool mine, int c, int ul) {
-  unsigned long long m = __ballot(mine);
-  while (m != 0) {
-    const int src = __ffsll((long long)m) - 1;
-    ma_fill_record_wave(env, __builtin_amdgcn_readlane(c, src), __builtin_amdgcn_readlane(ul, src));
-    m &= m - 1;
-  }
-}
-// test / debug view of one cell's records (artis_amd_debug_cellcache): a thread per level
-__global__ void __launch_bounds__(BLOCK) k_debug_macache(Env env, int c, double *maprocessrates, double *matrans, int32_t *bad) {
-  const int ul = blockIdx.x * BLOCK + threadIdx.x;
-  if (ul >= env.M.nlevels) return;
-  if (ma_resolve(env, c, env.M.level_pack[ul].rec_off) == MA_REC_NONE) return;  // (a cold level no packet has reached in this cell: no record)
-  const int b = debug_level_record(env, c, ul, maprocessrates, matrans);
-  if (b != 0) atomicAdd(bad, b);
-}
-// before a fill: no cold level of the cells to be filled has a record (tables.h "ON-DEMAND RECORDS"; the pool itself is emptied by populate_tile())
-__global__ void __launch_bounds__(BLOCK) k_ma_reset(Env env) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int ncold = env.M.ncold;
-  if (i >= fill_count(env) * ncold) return;
-  const int c = fill_cell(env, i / ncold);
-  env.K.ma_rowtab[(krow(env, c) * ncold) + (i % ncold)] = -1;
-}
-// the static part of every record of every resident row, once per engine: filter entries "never counted", lines usable
-__global__ void __launch_bounds__(BLOCK) k_mainit(Env env, int64_t nrows) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= nrows * env.M.nlevels) return;
-  populate_mainit(env, i / env.M.nlevels, (int)(i % env.M.nlevels));
-}
-// The cooling list of a (cell, ion) is one running sum over hundreds of terms (kpkt.cc:57-190): a free-free term, the
-// collisional-excitation terms k_matrans left in the population's scratch rows (most of them), and the bound-free tail. Three kernels:
-// head and tail with a lane per (cell, ion) -- 64 chains side by side, each short -- and the long middle with a ROW OF
-// 16 LANES per (cell, ion): it reads 16 terms (one cache line) at a time, forms the running sum with the sequential
-// additions of the reference's loop (lane k adds its term to lane k-1's finished sum: DPP row shifts, same order, same
-// bits), writes it back and drops the level totals into the cooling list through the static slot table. (A lane per
-// chain walked the terms with strided 8-byte accesses: 35 ms per step for the three parts, now 15.) The running sum
-// travels between the kernels in ion_cooling_C.
-__global__ void __launch_bounds__(BLOCK) k_cooling_head(Env env) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int64_t total = fill_count(env) * env.M.nions;
-  if (i >= total) return;
-  const int c = fill_cell(env, i / env.M.nions);
-  const int ui = (int)(i % env.M.nions);
-  int k = 0;
-  env.K.ion_cooling_C[(krow(env, c) * env.M.nions) + ui] = cooling_ion_head(env, c, ui, &k);
-}
-// the value of the lane below within a row of 16 lanes (the row's first lane: 0)
-__device__ inline double row_shr1(double x) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0x111 /* row_shr:1 */, 0xF, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0x111, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-// Four chains per wave, one per row of 16 lanes: a row reads 16 terms (one 128-byte line) at a time and needs 15 serial
-// steps for them; four independent chains keep the wave's issue slots four times as busy as one chain of 64 would.
-__global__ void __launch_bounds__(BLOCK) k_cooling_chain(Env env) {
-  const int64_t row_id = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 4;
-  const int r = threadIdx.x & 15;
-  const DevModel &M = env.M;
-  const int64_t nchains = fill_count(env) * M.nions;
-  const bool valid = row_id < nchains;
-  const int c = fill_cell(env, (valid ? row_id : 0) / M.nions);
-  const int ui = (int)((valid ? row_id : 0) % M.nions);
-  const int start = M.ion_uniquelevelindexstart[ui];
-  const int nlevels = M.ion_nlevels[ui];
-  const int j0 = (valid && nlevels > 0) ? M.level_upcum_start[start] : 0;
-  const int j1 = (valid && nlevels > 0) ? M.level_upcum_start[start + nlevels - 1] + M.level_nuptrans[start + nlevels - 1] : 0;
-  double carry = valid ? env.K.ion_cooling_C[(krow(env, c) * M.nions) + ui] : 0.;
-  double *upcum = env.collexc_terms + (((valid ? row_id : 0) / M.nions) * M.nupcum);  // the cell's row of the population's scratch
-  double *cool = env.K.cooling_contrib + (krow(env, c) * M.ncoolingterms);
-  for (int j = j0; __any(j < j1); j += 16) {  // rows with shorter chains idle through the longer ones' chunks
-    const bool in = (j + r) < j1;
-    const double x = in ? upcum[j + r] : 0.;
-    double acc = (r == 0) ? carry + x : x;
-#pragma unroll
-    for (int s = 1; s < 16; s++) {
-      const double prev = row_shr1(acc);  // lane s-1 of the row holds its finished sum
-      if (r == s) acc = prev + x;
-    }
-    if (in) {
-      upcum[j + r] = acc;
-      const int slot = M.upcum_coolslot[j + r];
-      if (slot >= 0) cool[slot] = acc;
-    }
-    // the sum after the row's last term, broadcast to the row (lanes past the end added 0. to it: x + 0. == x exactly)
-    const int src = ((threadIdx.x & 63) | 15) << 2;
-    carry = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(acc)), __builtin_amdgcn_ds_bpermute(src, __double2loint(acc)));
-  }
-  if (valid && r == 0 && j1 > j0) env.K.ion_cooling_C[(krow(env, c) * M.nions) + ui] = carry;
-}
-// the cooling filters of the levels' records from the running sums the chain left in the scratch rows: a thread per (cell, line)
-__global__ void __launch_bounds__(BLOCK) k_collexc_filter(Env env) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int64_t per = env.M.ncoollines;
-  if (i >= fill_count(env) * per) return;
-  const int64_t kf = i / per;
-  populate_coolfilter_line(env, fill_cell(env, kf), (int)(i % per), env.collexc_terms + (kf * env.M.nupcum));
-}
-// The bound-free tail of an ion's cooling list (kpkt.cc:122-190: a collisional-ionisation term and then a bound-free term per (ionising
-// level, target), ~120 entries, each behind three or four dependent gathers): a lane per (cell, ion) walked it serially (11 ms per step).
-// Round 4: a ROW OF 16 LANES per (cell, ion), like k_cooling_chain -- every lane forms the term of one entry (what the entry is it reads
-// from the cooling list's own static tables, checked against the loop order when the engine is created), the running sum is formed with the
-// loop's additions in the loop's order (DPP row shifts) and written back 16 entries = one 128-byte line at a time.
-// physics.h cooling_ion_tail() is the sequential form (test emulation).
-__global__ void __launch_bounds__(BLOCK) k_cooling_tail(Env env) {
-  const int64_t row_id = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 4;
-  const int r = threadIdx.x & 15;
-  const DevModel &M = env.M;
-  const int64_t nrows = fill_count(env) * M.nions;
-  const bool valid = row_id < nrows;
-  const int c = fill_cell(env, (valid ? row_id : 0) / M.nions);
-  const int ui = (int)((valid ? row_id : 0) % M.nions);
-  const int element = M.ion_element[ui];
-  const int ion = ui - M.elem_uniqueionindexstart[element];
-  const bool has = valid && ion < (M.elem_nions[element] - 1) && M.nbfcontinua > 0;
-  const double *pops = env.K.levelpops + (krow(env, c) * M.nlevels);
-  const int ionstart = M.ion_coolingoffset[ui];
-  double *contribs = env.K.cooling_contrib + (krow(env, c) * M.ncoolingterms) + ionstart;
-  const float cnne = clumpednne(env.C, c);
-  const float T_e = env.C.Te[c];
-  const int start = M.ion_uniquelevelindexstart[ui];
-  const int ustart = has ? M.ion_uniquelevelindexstart[ui + 1] : 0;
-  const double nnupperion = has ? nnion(env, c, element, ion + 1) : 0.;
-  const int k0 = has ? M.ion_cooltail_start[ui] : 0, k1 = has ? M.ion_ncoolingterms[ui] : 0;
-  double carry = valid ? env.K.ion_cooling_C[(krow(env, c) * M.nions) + ui] : 0.;
-  for (int j = k0; __any(j < k1); j += 16) {
-    const bool in = (j + r) < k1;
-    double x = 0.;
-    if (in) {
-      const int i = ionstart + j + r;
-      const int level = M.coolinglist_level[i];
-      const int t = M.coolinglist_phixstargetindex[i];
-      const int ul = start + level;
-      const int64_t o = (krow(env, c) * M.nphixstargets_total) + M.level_phixstargetstart[ul];
-      if (M.coolinglist_type[i] == ARTIS_COOLING_COLLION) {
-        const double e_trans = eps(M, ustart + phixs_upperlevel(M, ul, t)) - eps(M, ul);
-        x = pops[ul] * env.K.bf_colion[o + t] * e_trans;
-      } else {
-        double pop;
-#if ARTIS_OPT_BFCOOLING_USELEVELPOPNOTIONPOP
-        pop = pops[ustart + phixs_upperlevel(M, ul, t)];
-#else
-        const int nt = M.level_nphixstargets[ul];
-        if (nt == 1) {
-          pop = nnupperion;
-        } else {
-          double E_min = DBLMAX;
-          for (int tt = 0; tt < nt; tt++) E_min = dmin(E_min, eps(M, ustart + phixs_upperlevel(M, ul, tt)));
-          double wsum = 0.;
-          for (int tt = 0; tt < nt; tt++) {
-            const int up = phixs_upperlevel(M, ul, tt);
-            wsum += statw(M, ustart + up) * exp(-(eps(M, ustart + up) - E_min) / KB / T_e);
-          }
-          const int up = phixs_upperlevel(M, ul, t);
-          const double w = statw(M, ustart + up) * exp(-(eps(M, ustart + up) - E_min) / KB / T_e);
-          pop = nnupperion * w / wsum;
-        }
-#endif
-        x = env.K.bf_cooling[o + t] * pop * cnne;
-      }
-    }
-    double acc = (r == 0) ? carry + x : x;
-#pragma unroll
-    for (int s = 1; s < 16; s++) {
-      const double prev = row_shr1(acc);
-      if (r == s) acc = prev + x;
-    }
-    if (in) contribs[j + r] = acc;
-    const int src = ((threadIdx.x & 63) | 15) << 2;
-    carry = __hiloint2double(__builtin_amdgcn_ds_bpermute(src, __double2hiint(acc)), __builtin_amdgcn_ds_bpermute(src, __double2loint(acc)));
-  }
-  if (has && r == 0) env.K.ion_cooling_C[(krow(env, c) * M.nions) + ui] = carry;
-}
-__global__ void __launch_bounds__(BLOCK) k_cooling_prefix(Env env) {
-  const int64_t kf = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (kf >= fill_count(env)) return;
-  const int c = fill_cell(env, kf);
-  populate_cooling_prefix(env, c);
-}
-// the guides of the two cumulative lists a k-packet step draws from (tables.h "COOLING GUIDES"): a thread per entry
-__global__ void __launch_bounds__(BLOCK) k_cool_guide(Env env) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  const int64_t total = fill_count(env) * env.M.nguide;
-  if (i >= total) return;
-  populate_cool_guide(env, fill_cell(env, i / env.M.nguide), (int)(i % env.M.nguide));
-}
+#include "cellcache_kernels.h"  // ------------------------------------------------ populate kernels
 
 // ------------------------------------------------------------------ packet layout kernels
 // The slot of a packet is not its index in the caller's array: slots are handed out in the order of the packets'
@@ -2687,6 +1889,42 @@ struct SortScratch {
   int32_t *seg = nullptr;         // [SORT_HI_MAX + 1] where every bucket begins
   int32_t *chunk_base = nullptr;  // [SORT_HI_MAX + 1] pass 2's chunks before every bucket
 };
+// The cell cache's host state: which cells hold rows (cache_residency.h), the device copies of that, and what a fill works on and with (stage_cellcache.h).
+struct CellCache {
+  // Cell-cache tiling: the cache rows of `res.tile_cells` non-empty cells are resident at a time (all of them when they fit
+  // the budget: ntiles == 1). With more tiles, update_packets sweeps over them -- populate a tile, advance every packet
+  // that sits in one of its cells until it leaves the tile or is done -- until no packet is left (what the reference's
+  // single-slot cell cache does cell by cell, update_packets.cc:397-460, 551-621).
+  int ntiles = 1;
+  int tile_lo = 0, tile_hi = 0;   // one tile: all cells (the range a whole-cache fill works on)
+  int tile_valid_lo = -1;         // one tile: 0 once the cache is populated for the current cell state (-1: not)
+  // several tiles: which cell's cache each row holds, populated for the current cell state (physics.h Env::krow_tab; make_resident())
+  artis_residency::Residency res;
+  int32_t *d_krow = nullptr;         // the device's copy of res.krow
+  std::vector<int32_t> h_cell_grid;  // [npts_nonempty] the grid cell of a non-empty cell (the inverse of propcell_nonemptymgi)
+  size_t cache_bytes_per_cell = 0;
+  // the cells a fill of a tiled cache works on (make_resident()). Sparse fills: a visit for which few packets wait makes the cells in which they
+  // wait (and the cells around those) resident instead of a whole window. ARTIS_AMD_SPARSE_FILL=0: whole windows.
+  int32_t *d_fill_cells = nullptr;
+  bool sparse_fill = true;
+  int64_t sparse_max_listed = 16384;  // ... for visits that list at most this many packets (ARTIS_AMD_SPARSE_MAX; 512 in round 3:
+                                      // 4 tiles 3327 / 3205 / 3188 ms at 512 / 4096 / 16384, with parked tails 3222 / 3123 / 2982)
+  // Adaptive tiles (round 6; ARTIS_AMD_TILE_ADAPT=0: the fixed ranges of rounds 2-5). WHICH cells are resident is chosen before every visit from
+  // the number of packets that wait in every cell (k_count_waiting): the window of tile_cells consecutive cells in which most packets wait
+  // (ARTIS_AMD_TILE_BLOCK=0), or the blocks of tile_block consecutive cells in which most wait, wherever they lie (a tile = a SET of cells: rows are
+  // addressed through Env::krow_tab). A cell that is resident and still wanted keeps its row -- only the cells that are new to the set are filled.
+  // The first visits take the densest parts of the ejecta; afterwards the waiting packets sit on both sides of the earlier sets' edges, and a set laid
+  // across such an edge lets them cross it freely instead of waiting once per crossing and fixed tile.
+  bool tile_adapt = true;
+  int64_t tile_block = 0;
+  bool pool_keep = true;
+  int32_t *d_waiting = nullptr;  // [npts_nonempty + 1] packets waiting per cell; the last entry: packets that need no row
+  std::vector<int32_t> h_waiting;
+  // the population's scratch: the collisional-excitation cooling terms of `pop_batch` cells at a time (k_matrans writes them,
+  // k_cooling_chain turns them into running sums, k_collexc_filter into the records' cooling filters; nothing of it is kept)
+  double *d_collexc_terms = nullptr;
+  int64_t pop_batch = 0;
+};
 struct artis_amd_engine {
   int device = 0;
   EngineConfig cfg;           // the resolved configuration (engine_config.h resolve_config: struct field, else ARTIS_AMD_* variable, else default)
@@ -2723,22 +1961,7 @@ struct artis_amd_engine {
   VpktSeed *d_vpkt_queue = nullptr;
   int32_t *d_vpkt_count = nullptr;
   int32_t vpkt_cap = 0;
-  // Cell-cache tiling: the cache rows of `tile_cells` non-empty cells are resident at a time (all of them when they fit
-  // the budget: ntiles == 1). With more tiles, update_packets sweeps over them -- populate a tile, advance every packet
-  // that sits in one of its cells until it leaves the tile or is done -- until no packet is left (what the reference's
-  // single-slot cell cache does cell by cell, update_packets.cc:397-460, 551-621).
-  int64_t tile_cells = 0;
-  int ntiles = 1;
-  int tile_lo = 0, tile_hi = 0;   // one tile: all cells (the range a whole-cache fill works on)
-  int tile_valid_lo = -1;         // one tile: 0 once the cache is populated for the current cell state (-1: not)
-  // several tiles: which cell's cache each row holds, populated for the current cell state (physics.h Env::krow_tab; make_resident())
-  std::vector<int32_t> h_krow;     // [npts_nonempty] row of the cell, -1: not resident
-  std::vector<int32_t> h_rowcell;  // [tile_cells] cell of the row, -1: free
-  std::vector<int32_t> h_wanted;   // [npts_nonempty] stamp of the last make_resident() that asked for the cell
-  int32_t want_stamp = 0;
-  int32_t *d_krow = nullptr;
-  std::vector<int32_t> h_cell_grid;  // [npts_nonempty] the grid cell of a non-empty cell (the inverse of propcell_nonemptymgi)
-  size_t cache_bytes_per_cell = 0;
+  CellCache cc;  // the cell cache: which cells hold rows, what a fill works on (stage_cellcache.h)
   int32_t *d_target_level = nullptr;
   double *d_est = nullptr;
   int64_t est_ndoubles = 0;
@@ -2787,12 +2010,6 @@ struct artis_amd_engine {
   bool late_attr_set = false;         // k_late's dynamic-LDS attribute has been set on this engine's device
   int32_t *d_late_ring[2] = {nullptr, nullptr};  // the workgroups' queues (allocated with the lists)
   int32_t *d_late_bail = nullptr;     // the slot after the error flag
-  // the cells a fill of a tiled cache works on (make_resident()). Sparse fills: a visit for which few packets wait makes the cells in which they
-  // wait (and the cells around those) resident instead of a whole window. ARTIS_AMD_SPARSE_FILL=0: whole windows.
-  int32_t *d_fill_cells = nullptr;
-  bool sparse_fill = true;
-  int64_t sparse_max_listed = 16384;  // ... for visits that list at most this many packets (ARTIS_AMD_SPARSE_MAX; 512 in round 3:
-                                      // 4 tiles 3327 / 3205 / 3188 ms at 512 / 4096 / 16384, with parked tails 3222 / 3123 / 2982)
   bool park_tails = true;     // ARTIS_AMD_TILE_PARK=0: every visit of a tile runs its packets to their end (rounds 2-3)
   // artis_amd_config.tile_park_at: packets left of a larger visit at which it parks them (0 / <= tail_max: round 4's rule, at the tail kernel's
   // threshold). Measured on the headline at a quarter of its cache (4 tiles, adaptive windows; profiles/r06/tiling.md): 4096 / 32768 / 131072 /
@@ -2804,17 +2021,6 @@ struct artis_amd_engine {
   double ma_hotfrac = 1.;        // the share of every ion's levels that has a static record (given, or chosen by engine_fill from the cache budget)
   bool vpkt_cont_lds = true;  // ARTIS_AMD_VPKT_CONTLDS=0: k_vpkt reads the continuum table from memory (four workgroups of 256 per CU)
   bool tile_zigzag = false;  // ARTIS_AMD_TILE_ZIGZAG=1: sweeps alternate their direction (measured slower: profiles/r03/tiling.md)
-  // Adaptive tiles (round 6; ARTIS_AMD_TILE_ADAPT=0: the fixed ranges of rounds 2-5). WHICH cells are resident is chosen before every visit from
-  // the number of packets that wait in every cell (k_count_waiting): the window of tile_cells consecutive cells in which most packets wait
-  // (ARTIS_AMD_TILE_BLOCK=0), or the blocks of tile_block consecutive cells in which most wait, wherever they lie (a tile = a SET of cells: rows are
-  // addressed through Env::krow_tab). A cell that is resident and still wanted keeps its row -- only the cells that are new to the set are filled.
-  // The first visits take the densest parts of the ejecta; afterwards the waiting packets sit on both sides of the earlier sets' edges, and a set laid
-  // across such an edge lets them cross it freely instead of waiting once per crossing and fixed tile.
-  bool tile_adapt = true;
-  int64_t tile_block = 0;
-  bool pool_keep = true;
-  int32_t *d_waiting = nullptr;  // [npts_nonempty + 1] packets waiting per cell; the last entry: packets that need no row
-  std::vector<int32_t> h_waiting;
   int64_t last_visits = 0;  // visits of the last call that had packets (the driver's own count: adaptive tiles, trace)
   // do_rpkt_step() calls per packet per launch. 8 in rounds 2-3; with the r-packet kernel's reads requested ahead (round 4) the list's order
   // -- sorted by cell and frequency before every launch -- is worth more than the launches saved: 857 / 855 / 851 / 846 / 860 / 881 ms per step
@@ -2872,10 +2078,6 @@ struct artis_amd_engine {
   int tq_low = 48;              // ... its low-water mark of walking lanes (ARTIS_AMD_TQ_LOW)
   bool tq_attr_set = false;     // ... its dynamic-LDS attribute has been set on this engine's device
   bool ma_tables_lds = true;  // k_thermal<1024, true>: the static target tables in LDS when they fit (ARTIS_AMD_MATABLES_LDS=0: in HBM)
-  // the population's scratch: the collisional-excitation cooling terms of `pop_batch` cells at a time (k_matrans writes them,
-  // k_cooling_chain turns them into running sums, k_collexc_filter into the records' cooling filters; nothing of it is kept)
-  double *d_collexc_terms = nullptr;
-  int64_t pop_batch = 0;
   bool trace = false;
   uint32_t *d_visit_counts = nullptr;  // -DARTIS_VISIT_COUNTS builds: [cell][level] transitions drawn per record in the last call
   ncclComm_t comm = nullptr;  // created by artis_amd_comm_init(), owned by the engine
@@ -2939,16 +2141,16 @@ static void read_switches(artis_amd_engine *e) {
   if (const char *b = std::getenv("ARTIS_AMD_CONTLDS")) e->cont_lds = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_LINELDS")) e->line_lds = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_TILE_ZIGZAG")) e->tile_zigzag = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TILE_ADAPT")) e->tile_adapt = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_TILE_BLOCK")) e->tile_block = std::max<int64_t>(0, std::atoll(b));
-  if (const char *b = std::getenv("ARTIS_AMD_POOL_KEEP")) e->pool_keep = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TILE_ADAPT")) e->cc.tile_adapt = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_TILE_BLOCK")) e->cc.tile_block = std::max<int64_t>(0, std::atoll(b));
+  if (const char *b = std::getenv("ARTIS_AMD_POOL_KEEP")) e->cc.pool_keep = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_MATABLES_LDS")) e->ma_tables_lds = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_REFILL")) e->thermal_refill = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_SORT_NUMAJOR")) e->sort_numajor = std::atoi(b) != 0;
   if (const char *b = std::getenv("ARTIS_AMD_SORT_CELLSHIFT")) e->sort_cellshift = e->sort_numajor ? std::max(0, std::min(20, std::atoi(b))) : 0;
   if (const char *b = std::getenv("ARTIS_AMD_TQ_LOW")) e->tq_low = std::max(1, std::min(64, std::atoi(b)));
-  if (const char *b = std::getenv("ARTIS_AMD_SPARSE_FILL")) e->sparse_fill = std::atoi(b) != 0;
-  if (const char *b = std::getenv("ARTIS_AMD_SPARSE_MAX")) e->sparse_max_listed = std::max(0, std::atoi(b));
+  if (const char *b = std::getenv("ARTIS_AMD_SPARSE_FILL")) e->cc.sparse_fill = std::atoi(b) != 0;
+  if (const char *b = std::getenv("ARTIS_AMD_SPARSE_MAX")) e->cc.sparse_max_listed = std::max(0, std::atoi(b));
   if (const char *b = std::getenv("ARTIS_AMD_THERMAL_BLOCKS")) e->thermal_blocks_per_cu = std::max(1, std::min(ARTIS_THERMAL_WAVES, std::atoi(b)));
   e->trace = std::getenv("ARTIS_AMD_TRACE") != nullptr;
   if (const char *b = std::getenv("ARTIS_AMD_VPKT_CONTLDS")) e->vpkt_cont_lds = std::atoi(b) != 0;
@@ -2984,17 +2186,17 @@ Env make_env(const artis_amd_engine *e) {
     const DevModel &h = e->Mh;
     if (h.ndpop == 0) env.K.line_dpop = nullptr;  // formed on the fly (physics.h line_dpop_at)
     // the pool of on-demand records is one for all resident cells (tables.h "ON-DEMAND RECORDS"): not indexed by cell
-    env.ma_pool_cap = (uint32_t)std::min<int64_t>(((int64_t)e->tile_cells * h.ma_pool_slots) / MAPOOL_UNIT, 0x7FFFFFF0LL);
+    env.ma_pool_cap = (uint32_t)std::min<int64_t>(((int64_t)e->cc.res.tile_cells * h.ma_pool_slots) / MAPOOL_UNIT, 0x7FFFFFF0LL);
     env.ma_pool_full = e->d_count + (2 * NEXT_NKINDS - 1);  // (a spare slot of the counts the host reads after every launch)
   }
   // rows: one per cell (row = cell), or -- a cache that does not fit -- the rows of the cells that are resident now (make_resident())
-  env.krow_tab = e->ntiles > 1 ? e->d_krow : nullptr;
-  env.tile_all = e->ntiles > 1 ? 0 : 1;
+  env.krow_tab = e->cc.ntiles > 1 ? e->cc.d_krow : nullptr;
+  env.tile_all = e->cc.ntiles > 1 ? 0 : 1;
   env.tile_lo = 0;
   env.tile_hi = e->Mh.npts_nonempty;
   env.fill_cells = nullptr;  // (set by populate_tile() of a tiled cache for its own launches)
   env.nfill = 0;
-  env.collexc_terms = e->d_collexc_terms;
+  env.collexc_terms = e->cc.d_collexc_terms;
   {  // few cells: per-cell estimators accumulate in LDS (physics.h Env::cellest_lds)
     const int nc = e->Mh.npts_nonempty;
     env.cellest_n_t = (e->cellest_in_lds && nc <= THERMAL_CELLEST_CAP) ? nc : 0;
@@ -3015,7 +2217,7 @@ Env make_env(const artis_amd_engine *e) {
   env.bfev = e->bf_defer ? e->d_bfev : nullptr;
   env.bfev_count = e->d_bfev_count;
   env.bfev_cap = e->bfev_cap;
-  env.bfrate_kept = (e->bf_defer && e->ntiles == 1) ? e->d_bfrate_kept : nullptr;
+  env.bfrate_kept = (e->bf_defer && e->cc.ntiles == 1) ? e->d_bfrate_kept : nullptr;
   env.gamma_gi = e->d_gamma_gi;
   env.gamma_n = e->d_gamma_n;
   env.errflag = e->d_err;
@@ -3127,7 +2329,7 @@ void free_packet_buffers(artis_amd_engine *e) {
 // k_late may take the end of this engine's populations: a build with the kernel, k_tail allowed (no virtual packets, no deferred bound-free
 // events), the whole cache resident, no cold levels, and tables that fit the LDS
 bool late_possible(const artis_amd_engine *e) {
-  return ARTIS_LATE_KERNEL && e->late_max > 0 && e->tail_max > 0 && e->ntiles == 1 && e->Mh.ncold == 0 && e->Mh.nlevels > 0 && e->Mh.nlevels < 32768 &&
+  return ARTIS_LATE_KERNEL && e->late_max > 0 && e->tail_max > 0 && e->cc.ntiles == 1 && e->Mh.ncold == 0 && e->Mh.nlevels > 0 && e->Mh.nlevels < 32768 &&
          e->Mh.nalltrans > 0 && e->Mh.nbfcontinua > 0 && late_lds_bytes(e->Mh.nlevels, e->Mh.nalltrans, e->Mh.nbfcontinua) <= 160 * 1024 - 1024;
 }
 int ensure_packet_buffers(artis_amd_engine *e, int64_t n) {
@@ -3641,13 +2843,13 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
       e->M.ndpop = 0;
     }
     e->cache_budget = L.budget;
-    e->cache_bytes_per_cell = L.per_cell;
-    e->tile_cells = L.tile_cells;
-    e->ntiles = L.ntiles;
-    e->tile_lo = 0;
-    e->tile_hi = (int)std::min<int64_t>(ncell_all, e->tile_cells);
+    e->cc.cache_bytes_per_cell = L.per_cell;
+    e->cc.res.tile_cells = L.tile_cells;
+    e->cc.ntiles = L.ntiles;
+    e->cc.tile_lo = 0;
+    e->cc.tile_hi = (int)std::min<int64_t>(ncell_all, e->cc.res.tile_cells);
   }
-  const int64_t nrows = e->tile_cells;  // rows allocated
+  const int64_t nrows = e->cc.res.tile_cells;  // rows allocated
 #define CA(f, T, per)                                                                       \
   {                                                                                         \
     T *d = nullptr;                                                                         \
@@ -3708,7 +2910,7 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
   e->E.vspecpol = nvspec ? e->E.scalars + ARTIS_NSCALARS + 2 * nbinest + nbfest + 2 * nlineest : nullptr;
   e->E.vgrid_flux = nvgrid ? e->E.vspecpol + nvspec : nullptr;
 #if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
-  if (nbfest > 0 && h.nbfcontinua > 0 && e->ntiles == 1) {
+  if (nbfest > 0 && h.nbfcontinua > 0 && e->cc.ntiles == 1) {
     const size_t bytes = sizeof(double) * (size_t)ncell * (size_t)h.nbfcontinua;
     HIP_TRY(hipMalloc((void **)&e->d_bfrate_kept, bytes));
     HIP_TRY(hipMemset(e->d_bfrate_kept, 0, bytes));
@@ -3722,16 +2924,14 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
   e->d_late_bail = e->d_err + 1;  // (k_late's count of waves that gave up waiting: travels with the counters)
   HIP_TRY(hipHostMalloc((void **)&e->h_counts, sizeof(int32_t) * (2 * NEXT_NKINDS + 2), hipHostMallocDefault));
   HIP_TRY(hipMalloc((void **)&e->d_cursors, sizeof(int32_t) * (MAX_CHUNKS + 1)));  // + the launch's "list used up" flag
-  HIP_TRY(hipMalloc((void **)&e->d_fill_cells, sizeof(int32_t) * (size_t)(ncell_all > 0 ? ncell_all : 1)));
-  if (e->ntiles > 1) {  // rows for a set of cells at a time: the table of rows, no cell resident yet
-    HIP_TRY(hipMalloc((void **)&e->d_krow, sizeof(int32_t) * (size_t)ncell_all));
-    e->h_krow.assign((size_t)ncell_all, -1);
-    e->h_wanted.assign((size_t)ncell_all, 0);
-    e->h_rowcell.assign((size_t)e->tile_cells, -1);
-    HIP_TRY(hipMemset(e->d_krow, 0xFF, sizeof(int32_t) * (size_t)ncell_all));
-    e->h_cell_grid.assign((size_t)ncell_all, 0);
+  HIP_TRY(hipMalloc((void **)&e->cc.d_fill_cells, sizeof(int32_t) * (size_t)(ncell_all > 0 ? ncell_all : 1)));
+  if (e->cc.ntiles > 1) {  // rows for a set of cells at a time: the table of rows, no cell resident yet
+    HIP_TRY(hipMalloc((void **)&e->cc.d_krow, sizeof(int32_t) * (size_t)ncell_all));
+    e->cc.res.init(ncell_all);
+    HIP_TRY(hipMemset(e->cc.d_krow, 0xFF, sizeof(int32_t) * (size_t)ncell_all));
+    e->cc.h_cell_grid.assign((size_t)ncell_all, 0);
     for (int g = 0; g < h.ngrid; g++)
-      if (h.propcell_nonemptymgi[g] >= 0) e->h_cell_grid[(size_t)h.propcell_nonemptymgi[g]] = g;
+      if (h.propcell_nonemptymgi[g] >= 0) e->cc.h_cell_grid[(size_t)h.propcell_nonemptymgi[g]] = g;
   }
   {
     hipDeviceProp_t prop;
@@ -3747,7 +2947,7 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
   read_switches(e);
   {
     // the static part of every macro-atom record (tables.h: filter entries that are never counted) is written once
-    const int64_t nrows_ = e->tile_cells;  // every resident row; the static parts do not depend on the cell
+    const int64_t nrows_ = e->cc.res.tile_cells;  // every resident row; the static parts do not depend on the cell
     Env env0 = make_env(e);
     env0.K = e->K;
     hipLaunchKernelGGL(k_mainit, dim3(nblocks(nrows_ * e->Mh.nlevels)), dim3(BLOCK), 0, nullptr, env0, nrows_);
@@ -3756,13 +2956,13 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
   }
   {
     // the population works through the cells in batches whose cooling terms fit its scratch (pop_batch_cells)
-    e->pop_batch = pop_batch_cells(e->Mh, e->tile_cells, e->cfg);
-    HIP_TRY(hipMalloc((void **)&e->d_collexc_terms, pop_scratch_alloc_bytes(e->Mh, e->pop_batch)));
+    e->cc.pop_batch = pop_batch_cells(e->Mh, e->cc.res.tile_cells, e->cfg);
+    HIP_TRY(hipMalloc((void **)&e->cc.d_collexc_terms, pop_scratch_alloc_bytes(e->Mh, e->cc.pop_batch)));
   }
   if (e->trace) trace_config(e);
   if (e->trace)
     fprintf(stderr, "[artis_amd] record tiers: static records for %.2f of every ion's levels, %d cold levels, pool of %d slots per resident cell; %d tile(s) of %lld cells, %zu B per cell\n",
-            e->ma_hotfrac, e->Mh.ncold, e->Mh.ma_pool_slots, e->ntiles, (long long)e->tile_cells, e->cache_bytes_per_cell);
+            e->ma_hotfrac, e->Mh.ncold, e->Mh.ma_pool_slots, e->cc.ntiles, (long long)e->cc.res.tile_cells, e->cc.cache_bytes_per_cell);
   return ARTIS_OK;
 }
 }  // namespace
@@ -3781,8 +2981,8 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   rf_free(e->rf);
   ib_free(e->ib);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
-  void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->d_krow, e->d_fill_cells, e->d_waiting,
-                  e->d_bfrate_kept, e->d_collexc_terms, e->d_visit_counts};
+  void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->cc.d_krow, e->cc.d_fill_cells, e->cc.d_waiting,
+                  e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : {e->ev0, e->ev1, e->ev2, e->ev3})
@@ -3901,248 +3101,7 @@ int artis_amd_set_cellstate(artis_amd_engine *e, const artis_cellstate *cells, c
 
 }  // extern "C"
 
-namespace {
-// populate the cell cache: of every cell (nfill < 0: one tile, row = cell), or of the cells e->d_fill_cells[0..nfill) (a tiled cache: their rows are
-// in e->d_krow, make_resident())
-int populate_tile(artis_amd_engine *e, hipStream_t s, int64_t nfill = -1) {
-  const DevModel &h = e->Mh;
-  const int lo = 0, hi = h.npts_nonempty;
-  e->tile_lo = lo;
-  e->tile_hi = hi;
-  e->tile_valid_lo = -1;
-  Env env = make_env(e);
-  if (nfill >= 0) {
-    env.fill_cells = e->d_fill_cells;
-    env.nfill = (int32_t)nfill;
-  }
-  const int64_t ncell_fill = nfill >= 0 ? nfill : hi - lo;
-  if (ncell_fill <= 0) return ARTIS_OK;
-  // The pool of on-demand records: a fill of the whole cache empties it. A fill of some cells of a tiled cache leaves it alone -- the cells that stay
-  // resident keep their cold levels' records; the rows that are filled start without any (k_ma_reset below), and the units the cells before them held
-  // stay handed out until the pool is used up and emptied (reset_pool_if_due() of the propagation loop), which costs fills, never an answer.
-  // ARTIS_AMD_POOL_KEEP=0: emptied with every fill (round 5). (Emptying it only with the fills that replace half of the rows or more -- when most of what
-  // it holds belongs to cells that leave -- was measured too: no better, 1520 against 1498 ms at a quarter of the cache; profiles/r06/tiling.md.)
-  if (h.ncold > 0 && (nfill < 0 || !e->pool_keep)) {
-    HIP_TRY(hipMemsetAsync(e->K.ma_pool_used, 0, sizeof(uint32_t), s));
-    if (nfill >= 0) HIP_TRY(hipMemsetAsync(e->K.ma_rowtab, 0xFF, sizeof(int32_t) * (size_t)(e->tile_cells * (int64_t)h.ncold), s));
-  }
-  // in batches of pop_batch cells (the scratch of cooling terms holds that many rows); the kernels of a batch see it as
-  // their whole fill: a sub-range of the tile, or a stretch of the list of a sparse fill
-  const Env env_tile = env;
-  for (int64_t b0 = 0; b0 < ncell_fill; b0 += e->pop_batch) {
-  const int64_t ncell = std::min<int64_t>(e->pop_batch, ncell_fill - b0);
-  env = env_tile;
-  if (nfill >= 0) {
-    env.fill_cells = e->d_fill_cells + b0;
-    env.nfill = (int32_t)ncell;
-  } else {
-    env.tile_lo = lo + (int)b0;
-    env.tile_hi = lo + (int)(b0 + ncell);
-  }
-  if (h.ncold > 0) hipLaunchKernelGGL(k_ma_reset, dim3(nblocks(ncell * h.ncold)), dim3(BLOCK), 0, s, env);
-  hipLaunchKernelGGL(k_levelpops, dim3(nblocks(ncell * h.nlevels)), dim3(BLOCK), 0, s, env);
-  if (h.ndpop > 0) hipLaunchKernelGGL(k_line_dpop, dim3(nblocks(ncell * h.nlines)), dim3(BLOCK), 0, s, env);
-  hipLaunchKernelGGL(k_cell_scalars, dim3(nblocks(ncell)), dim3(BLOCK), 0, s, env);
-  if (h.nbfcontinua > 0) hipLaunchKernelGGL(k_allcont, dim3(nblocks(ncell * h.nkeepwords * 64)), dim3(BLOCK), 0, s, env);
-  if (h.nbfcontinua > 0) hipLaunchKernelGGL(k_keptlist, dim3(nblocks(ncell * 64)), dim3(BLOCK), 0, s, env);
-  if (h.nphixstargets_total > 0)
-    hipLaunchKernelGGL(k_corrphotoion, dim3(nblocks(ncell * h.nphixstargets_total)), dim3(BLOCK), 0, s, env, e->d_target_level);
-  if (h.nalltrans > 0) hipLaunchKernelGGL(k_matrans, dim3(nblocks(ncell * h.nscanblk * 64)), dim3(BLOCK), 0, s, env);
-  if (h.nrecomblevels > 0) hipLaunchKernelGGL(k_macroatom_recomb, dim3(nblocks(ncell * (int64_t)h.nrecomblevels * 16)), dim3(BLOCK), 0, s, env);
-  hipLaunchKernelGGL(k_macroatom, dim3(nblocks(ncell * h.nlevels)), dim3(BLOCK), 0, s, env);
-  if (h.nmalongsegs > 0) hipLaunchKernelGGL(k_mafilter_long, dim3(nblocks(ncell * (int64_t)h.nmalongsegs * 64)), dim3(BLOCK), 0, s, env);
-#if ARTIS_EXPOPAC_TABLES
-  if (e->expopac_own) {  // needs line_dpop and chi_ff_nnionpart of the tile's cells (k_line_dpop, k_cell_scalars above)
-    hipLaunchKernelGGL(k_expopac, dim3(nblocks((int64_t)ncell * ARTIS_EXPOPAC_NBINS)), dim3(BLOCK), 0, s, env);
-    if (ARTIS_OPT_RPKT_BB_THERMALISATION) hipLaunchKernelGGL(k_expopac_planck, dim3(nblocks(ncell)), dim3(BLOCK), 0, s, env);
-  }
-#endif
-  hipLaunchKernelGGL(k_cooling_head, dim3(nblocks((int64_t)ncell * h.nions)), dim3(BLOCK), 0, s, env);
-  hipLaunchKernelGGL(k_cooling_chain, dim3(nblocks((int64_t)ncell * h.nions * 16)), dim3(BLOCK), 0, s, env);
-  if (h.ncoollines > 0) hipLaunchKernelGGL(k_collexc_filter, dim3(nblocks(ncell * (int64_t)h.ncoollines)), dim3(BLOCK), 0, s, env);
-  hipLaunchKernelGGL(k_cooling_tail, dim3(nblocks((int64_t)ncell * h.nions * 16)), dim3(BLOCK), 0, s, env);
-  hipLaunchKernelGGL(k_cooling_prefix, dim3(nblocks(ncell)), dim3(BLOCK), 0, s, env);
-  if (h.nguide > 0) hipLaunchKernelGGL(k_cool_guide, dim3(nblocks(ncell * h.nguide)), dim3(BLOCK), 0, s, env);
-  }  // batches
-  const int64_t ncell = ncell_fill;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(s));
-  // UPDATECELL (stats.h:47): one populate per cell
-  unsigned long long add = (unsigned long long)ncell, cur = 0;
-  HIP_TRY(hipMemcpy(&cur, e->d_stats + ARTIS_STAT_UPDATECELL, sizeof(cur), hipMemcpyDeviceToHost));
-  cur += add;
-  HIP_TRY(hipMemcpy(e->d_stats + ARTIS_STAT_UPDATECELL, &cur, sizeof(cur), hipMemcpyHostToDevice));
-  int32_t err = 0;
-  HIP_TRY(hipMemcpy(&err, e->d_err, sizeof(err), hipMemcpyDeviceToHost));
-  if (err != 0) {
-    (void)hipMemset(e->d_err, 0, sizeof(int32_t));  // the flag is reported once; the next call starts clean
-    g_last_error = "cell cache population raised error flag " + std::to_string(err);
-    return ARTIS_ERR_NOTCONVERGED;
-  }
-  e->tile_valid_lo = nfill >= 0 ? -1 : 0;
-  return ARTIS_OK;
-}
-
-// a tiled cache: no cell is resident (a new cell state: what the rows hold belongs to the old one)
-int forget_rows(artis_amd_engine *e, hipStream_t s) {
-  if (e->ntiles <= 1) return ARTIS_OK;
-  std::fill(e->h_krow.begin(), e->h_krow.end(), -1);
-  std::fill(e->h_rowcell.begin(), e->h_rowcell.end(), -1);
-  HIP_TRY(hipMemsetAsync(e->d_krow, 0xFF, sizeof(int32_t) * e->h_krow.size(), s));
-  if (e->Mh.ncold > 0) {  // ... and no cold level has a record
-    HIP_TRY(hipMemsetAsync(e->K.ma_pool_used, 0, sizeof(uint32_t), s));
-    HIP_TRY(hipMemsetAsync(e->K.ma_rowtab, 0xFF, sizeof(int32_t) * (size_t)(e->tile_cells * (int64_t)e->Mh.ncold), s));
-  }
-  return ARTIS_OK;
-}
-
-// a tiled cache: make the cells want[0..) resident (at most tile_cells of them). A wanted cell that is resident keeps its row; the others take the
-// free rows, then the rows of cells that are not wanted (which stay resident as long as nobody needs their rows); the cells that got a row are filled.
-// *nfilled: how many that were.
-int make_resident(artis_amd_engine *e, const std::vector<int32_t> &want, hipStream_t s, int64_t *nfilled) {
-  *nfilled = 0;
-  if (e->ntiles <= 1 || want.empty()) return ARTIS_OK;
-  if ((int64_t)want.size() > e->tile_cells) {
-    g_last_error = "make_resident: more cells than rows";
-    return ARTIS_ERR_ARG;
-  }
-  const int32_t stamp = ++e->want_stamp;
-  std::vector<int32_t> fresh;
-  for (const int32_t c : want) {
-    e->h_wanted[(size_t)c] = stamp;
-    if (e->h_krow[(size_t)c] < 0) fresh.push_back(c);
-  }
-  if (fresh.empty()) return ARTIS_OK;
-  size_t k = 0;
-  for (int pass = 0; pass < 2 && k < fresh.size(); pass++)
-    for (size_t r = 0; r < e->h_rowcell.size() && k < fresh.size(); r++) {
-      const int32_t held = e->h_rowcell[r];
-      if (pass == 0 ? held >= 0 : (held < 0 || e->h_wanted[(size_t)held] == stamp)) continue;
-      if (held >= 0) e->h_krow[(size_t)held] = -1;
-      e->h_rowcell[r] = fresh[k];
-      e->h_krow[(size_t)fresh[k]] = (int32_t)r;
-      k++;
-    }
-  if (k < fresh.size()) {
-    g_last_error = "make_resident: no row left";
-    return ARTIS_ERR_ARG;
-  }
-  HIP_TRY(hipMemcpyAsync(e->d_krow, e->h_krow.data(), sizeof(int32_t) * e->h_krow.size(), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(e->d_fill_cells, fresh.data(), sizeof(int32_t) * fresh.size(), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));  // (fresh is a local)
-  const int rc = populate_tile(e, s, (int64_t)fresh.size());
-  if (rc != ARTIS_OK) {  // (what the rows of the new cells hold is not to be used)
-    for (const int32_t c : fresh) {
-      e->h_rowcell[(size_t)e->h_krow[(size_t)c]] = -1;
-      e->h_krow[(size_t)c] = -1;
-    }
-    (void)hipMemcpy(e->d_krow, e->h_krow.data(), sizeof(int32_t) * e->h_krow.size(), hipMemcpyHostToDevice);
-    return rc;
-  }
-  *nfilled = (int64_t)fresh.size();
-  return ARTIS_OK;
-}
-
-// Which cells should be resident for the next visit of a tiled run? waiting[c]: packets that wait in non-empty cell c (k_count_waiting).
-//  - few packets wait (at most sparse_max of them, in less than half as many cells as there are rows): the cells in which they wait and the cells around
-//    those, one step in every grid direction (an r-packet crosses a few cells per visit) -- a "sparse" visit
-//  - tile_block == 0: the window of tile_cells consecutive cells in which most packets wait
-//  - else: the blocks of tile_block consecutive cells in which most packets wait, wherever they lie, as many as there are rows for
-// *holds: the packets that wait in the chosen cells.
-void choose_cells(artis_amd_engine *e, const std::vector<int32_t> &waiting, std::vector<int32_t> &want, int64_t *holds, bool *sparse,
-                  int64_t win_lo = -1) {
-  const DevModel &h = e->Mh;
-  const int64_t ncell_all = h.npts_nonempty, nrows = e->tile_cells;
-  want.clear();
-  *sparse = false;
-  *holds = 0;
-  int64_t lo = win_lo;
-  if (win_lo < 0 && e->tile_block > 0 && e->tile_block < nrows) {
-    const int64_t B = e->tile_block, nblk = (ncell_all + B - 1) / B;
-    std::vector<std::pair<int64_t, int64_t>> score((size_t)nblk);
-    for (int64_t b = 0; b < nblk; b++) {
-      int64_t sum = 0;
-      for (int64_t c = b * B; c < std::min(ncell_all, (b + 1) * B); c++) sum += waiting[(size_t)c];
-      score[(size_t)b] = {-sum, b};
-    }
-    std::sort(score.begin(), score.end());
-    for (const auto &sb : score) {
-      const int64_t c0 = sb.second * B, c1 = std::min(ncell_all, c0 + B);
-      if (sb.first == 0 || (int64_t)want.size() + (c1 - c0) > nrows) break;
-      for (int64_t c = c0; c < c1; c++) want.push_back((int32_t)c);
-      *holds -= sb.first;
-    }
-    std::sort(want.begin(), want.end());
-  } else {
-    if (win_lo < 0) {
-      int64_t sum = 0, best = -1;
-      lo = 0;
-      for (int64_t c = 0; c < ncell_all; c++) {
-        sum += waiting[(size_t)c];
-        if (c >= nrows) sum -= waiting[(size_t)(c - nrows)];
-        if ((c >= nrows - 1 || c == ncell_all - 1) && sum > best) {
-          best = sum;
-          lo = std::max<int64_t>(0, c - nrows + 1);
-        }
-      }
-      lo = std::min<int64_t>(lo, std::max<int64_t>(0, ncell_all - nrows));
-    }
-    for (int64_t c = lo; c < std::min(ncell_all, lo + nrows); c++) {
-      want.push_back((int32_t)c);
-      *holds += waiting[(size_t)c];
-    }
-  }
-  if (!e->sparse_fill || *holds > e->sparse_max_listed) return;
-  // a sparse visit: of the chosen cells, those in which packets wait, and the cells around them (whichever cells those are)
-  std::vector<int32_t> few;
-  const int32_t stamp = -(++e->want_stamp);  // (marks of this choice: negative, never those of make_resident())
-  std::vector<int32_t> &mark = e->h_wanted;
-  const int ndim = (h.gridtype == ARTIS_GRID_SPHERICAL1D) ? 1 : ((h.gridtype == ARTIS_GRID_CYLINDRICAL2D) ? 2 : 3);
-  for (const int32_t c : want) {
-    if (waiting[(size_t)c] <= 0) continue;
-    const int g = e->h_cell_grid[(size_t)c];
-    int lo3[3] = {0, 0, 0}, hi3[3] = {0, 0, 0};
-    for (int d = 0; d < ndim; d++) {
-      const int idx = (g / h.coordstride[d]) % h.ncoordgrid[d];
-      lo3[d] = idx > 0 ? -1 : 0;
-      hi3[d] = idx < h.ncoordgrid[d] - 1 ? 1 : 0;
-    }
-    for (int dz = lo3[2]; dz <= hi3[2]; dz++)
-      for (int dy = lo3[1]; dy <= hi3[1]; dy++)
-        for (int dx = lo3[0]; dx <= hi3[0]; dx++) {
-          const int cn = h.propcell_nonemptymgi[g + (dx * h.coordstride[0]) + (dy * h.coordstride[1]) + (dz * h.coordstride[2])];
-          if (cn < 0 || mark[(size_t)cn] == stamp) continue;
-          mark[(size_t)cn] = stamp;
-          few.push_back(cn);
-        }
-  }
-  if (few.empty() || (int64_t)few.size() * 2 >= nrows) return;
-  want.swap(few);
-  *sparse = true;
-}
-}  // namespace
-
 extern "C" {
-
-int artis_amd_populate_cellcache(artis_amd_engine *e, void *hip_stream) {
-  if (!e || !e->have_cells) {
-    g_last_error = "no cell state uploaded";
-    return ARTIS_ERR_ARG;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  e->tile_valid_lo = -1;
-  // with one tile the whole cache is filled now; with several, artis_amd_update_packets_device() makes cells resident as packets need them
-  if (e->ntiles == 1) return populate_tile(e, (hipStream_t)hip_stream);
-  return forget_rows(e, (hipStream_t)hip_stream);
-}
-
-int artis_amd_cache_tiles(artis_amd_engine *e, int32_t *ntiles, int64_t *cells_per_tile, int64_t *bytes_per_cell) {
-  if (!e) return ARTIS_ERR_ARG;
-  if (ntiles) *ntiles = e->ntiles;
-  if (cells_per_tile) *cells_per_tile = e->tile_cells;
-  if (bytes_per_cell) *bytes_per_cell = (int64_t)e->cache_bytes_per_cell;
-  return ARTIS_OK;
-}
 
 int artis_amd_engine_config(artis_amd_engine *e, artis_amd_config *effective) {
   if (!e || !effective) {
@@ -4434,7 +3393,7 @@ int artis_amd_update_packets(artis_amd_engine *e, artis_packet *packets, int64_t
   {
     // keep UPDATECELL of the populate that belongs to this timestep (with several cache tiles the populates happen
     // inside the update and count themselves)
-    unsigned long long ncell = (e->ntiles == 1) ? (unsigned long long)e->Mh.npts_nonempty : 0ull;
+    unsigned long long ncell = (e->cc.ntiles == 1) ? (unsigned long long)e->Mh.npts_nonempty : 0ull;
     HIP_TRY(hipMemcpy(e->d_stats + ARTIS_STAT_UPDATECELL, &ncell, sizeof(ncell), hipMemcpyHostToDevice));
   }
   rc = artis_amd_update_packets_device(e, nullptr);
@@ -4563,72 +3522,6 @@ int artis_amd_debug_visit_counts(artis_amd_engine *e, uint32_t *counts, int64_t 
   return ARTIS_OK;
 }
 
-int artis_amd_debug_cellcache(artis_amd_engine *e, int c, double *levelpops, double *maprocessrates, double *matrans,
-                              double *allcont_nnlevel, double *allcont_departure, double *allcont_edgepart,
-                              uint64_t *allcont_keepbits, double *corrphotoioncoeff, double *cooling_contrib,
-                              double *ion_cooling_contribs, double *chi_ff_nnionpart) {
-  if (!e || !e->have_cells || c < 0 || c >= e->Mh.npts_nonempty) {
-    g_last_error = "bad cell index or no cell state";
-    return ARTIS_ERR_ARG;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  const DevModel &h = e->Mh;
-  const int cell = c;
-  if (e->ntiles == 1) {  // the cache has to be filled
-    if (e->tile_valid_lo != 0) {
-      int rc = populate_tile(e, nullptr);
-      if (rc != ARTIS_OK) return rc;
-    }
-  } else {  // the cell has to be resident
-    int64_t nfilled = 0;
-    int rc = make_resident(e, std::vector<int32_t>{(int32_t)c}, nullptr, &nfilled);
-    if (rc != ARTIS_OK) return rc;
-    c = e->h_krow[(size_t)c];  // its row
-  }
-#define DL(dst, f, T, per)                                                                                            \
-  if (dst && (per) > 0) HIP_TRY(hipMemcpy(dst, e->K.f + (int64_t)c * (per), sizeof(T) * (size_t)(per), hipMemcpyDeviceToHost));
-  DL(levelpops, levelpops, double, h.nlevels)
-  if (maprocessrates || matrans) {
-    // the rates from the records; the cumulative sums -- which the records hold as filters only -- re-added on the device from
-    // the transitions' terms, the way an undecided draw gets them. A record whose filters are not those of the sequential
-    // form fails the call.
-    double *d_rates = nullptr, *d_trans = nullptr;
-    int32_t *d_bad = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_rates, sizeof(double) * (size_t)(h.nlevels * 9 + 1)));
-    HIP_TRY(hipMalloc((void **)&d_trans, sizeof(double) * (size_t)(h.nmatransblock + 1)));
-    HIP_TRY(hipMalloc((void **)&d_bad, sizeof(int32_t)));
-    HIP_TRY(hipMemset(d_bad, 0, sizeof(int32_t)));
-    const Env env = make_env(e);
-    hipLaunchKernelGGL(k_debug_macache, dim3(nblocks(h.nlevels)), dim3(BLOCK), 0, nullptr, env, cell, d_rates, d_trans, d_bad);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    int32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost));
-    if (maprocessrates) HIP_TRY(hipMemcpy(maprocessrates, d_rates, sizeof(double) * (size_t)h.nlevels * 9, hipMemcpyDeviceToHost));
-    if (matrans) HIP_TRY(hipMemcpy(matrans, d_trans, sizeof(double) * (size_t)h.nmatransblock, hipMemcpyDeviceToHost));
-    (void)hipFree(d_rates);
-    (void)hipFree(d_trans);
-    (void)hipFree(d_bad);
-    if (bad != 0) {
-      g_last_error = std::to_string(bad) + " filter entries of the cell's macro-atom records differ from the sequential form";
-      return ARTIS_ERR_NOTCONVERGED;
-    }
-  }
-  DL(allcont_nnlevel, allcont_nnlevel, double, h.nbfcontinua)
-  DL(allcont_departure, allcont_departure, double, h.nbfcontinua)
-  DL(allcont_edgepart, allcont_edgepart, double, h.nbfcontinua)
-  if (allcont_keepbits && h.nbfcontinua > 0)  // rows are padded to nkeepwords; the caller's buffer holds ceil(nbfcontinua/64) words
-    HIP_TRY(hipMemcpy(allcont_keepbits, e->K.allcont_keepbits + (int64_t)c * h.nkeepwords, sizeof(uint64_t) * (size_t)((h.nbfcontinua + 63) / 64),
-                      hipMemcpyDeviceToHost));
-  DL(corrphotoioncoeff, corrphotoioncoeff, double, h.nphixstargets_total)
-  DL(cooling_contrib, cooling_contrib, double, h.ncoolingterms)
-  DL(ion_cooling_contribs, ion_cooling_contribs, double, h.nions)
-  DL(chi_ff_nnionpart, chi_ff_nnionpart, double, 1)
-#undef DL
-  return ARTIS_OK;
-}
-
-
 int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const int32_t *list, int32_t n, int64_t nkeys, int32_t *out) {
   if (!e || n < 0 || (n > 0 && (!keys || !list || !out))) {
     g_last_error = "null argument or negative length";
@@ -4681,7 +3574,8 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance
+// ------------------------------------------------------------------ the cell cache's host side; the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance
+#include "stage_cellcache.h"
 #include "stage_propagate.h"
 #include "stage_common.h"
 #include "stage_spectra.h"

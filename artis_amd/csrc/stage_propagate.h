@@ -74,7 +74,7 @@ struct PropRun {
   const int r_nubins = e->sort_nu ? SORT_NUBINS : 1;  // frequency bins in the keys of the r-packet list
   // cell groups of the frequency-major keys: the ONE number both the keys (Lists::numajor) and the sort's key count are made of
   const int32_t r_ngroups = (e->sort_cellshift > 0) ? ((e->Mh.ngrid >> e->sort_cellshift) + 1) : e->Mh.ngrid;
-  const bool adaptive = e->tile_adapt && e->ntiles > 1;
+  const bool adaptive = e->cc.tile_adapt && e->cc.ntiles > 1;
   int64_t guard = 0;
   // (ARTIS_AMD_TRACE: where the host's time of the call goes -- waiting for the stream, submitting sorts, submitting launches)
   double wall_sync = 0., wall_sort = 0., wall_launch = 0.;
@@ -127,7 +127,7 @@ struct PropRun {
   int reset_pool_if_due() {
     if (!pool_reset_due || e->Mh.ncold <= 0) return ARTIS_OK;
     pool_reset_due = false;
-    HIP_TRY(hipMemsetAsync(e->K.ma_rowtab, 0xFF, sizeof(int32_t) * (size_t)(e->tile_cells * (int64_t)e->Mh.ncold), s));  // (every row: k_ma_reset)
+    HIP_TRY(hipMemsetAsync(e->K.ma_rowtab, 0xFF, sizeof(int32_t) * (size_t)(e->cc.res.tile_cells * (int64_t)e->Mh.ncold), s));  // (every row: k_ma_reset)
     HIP_TRY(hipMemsetAsync(e->K.ma_pool_used, 0, sizeof(uint32_t), s));
     e->last.pool_resets++;
     if (e->trace) fprintf(stderr, "[artis_amd] the pool of on-demand records was used up: emptied (%lld)\n", (long long)e->last.pool_resets);
@@ -138,25 +138,25 @@ struct PropRun {
   // the others are filled; *nothing_left is set where no packet waits anywhere. Untiled: the whole cache, if the cell state has changed since its last fill.
   int prepare_visit(int tile, bool *nothing_left) {
     const int64_t ncell_all = e->Mh.npts_nonempty;
-    if (e->ntiles > 1) {
+    if (e->cc.ntiles > 1) {
       env = make_env(e);
-      HIP_TRY(hipMemsetAsync(e->d_waiting, 0, sizeof(int32_t) * (size_t)(ncell_all + 1), s));
-      hipLaunchKernelGGL(k_count_waiting, dim3(nblocks(e->npackets)), dim3(BLOCK), 0, s, env, e->d_waiting, e->d_waiting + ncell_all);
-      HIP_TRY(hipMemcpyAsync(e->h_waiting.data(), e->d_waiting, sizeof(int32_t) * (size_t)(ncell_all + 1), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemsetAsync(e->cc.d_waiting, 0, sizeof(int32_t) * (size_t)(ncell_all + 1), s));
+      hipLaunchKernelGGL(k_count_waiting, dim3(nblocks(e->npackets)), dim3(BLOCK), 0, s, env, e->cc.d_waiting, e->cc.d_waiting + ncell_all);
+      HIP_TRY(hipMemcpyAsync(e->cc.h_waiting.data(), e->cc.d_waiting, sizeof(int32_t) * (size_t)(ncell_all + 1), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
       int64_t total = 0;
-      for (int64_t c = 0; c < ncell_all; c++) total += e->h_waiting[(size_t)c];
-      if (total == 0 && e->h_waiting[(size_t)ncell_all] == 0) {
+      for (int64_t c = 0; c < ncell_all; c++) total += e->cc.h_waiting[(size_t)c];
+      if (total == 0 && e->cc.h_waiting[(size_t)ncell_all] == 0) {
         *nothing_left = true;
         return ARTIS_OK;
       }
       int64_t holds = 0, nfilled = 0;
       bool sparse = false;
-      choose_cells(e, e->h_waiting, want, &holds, &sparse, adaptive ? -1 : (int64_t)tile * e->tile_cells);
+      choose_cells(e, e->cc.h_waiting, want, &holds, &sparse, adaptive ? -1 : (int64_t)tile * e->cc.res.tile_cells);
       if (holds == 0) want.clear();  // (no packet waits for a row of these cells: the visit is for the packets that need none, if any)
       if (e->trace)
         fprintf(stderr, "[artis_amd] visit %lld: %lld packets wait in cells, %d need no row; %zu cells chosen%s hold %lld\n", (long long)e->last_visits,
-                (long long)total, e->h_waiting[(size_t)ncell_all], want.size(), sparse ? " (sparse)" : "", (long long)holds);
+                (long long)total, e->cc.h_waiting[(size_t)ncell_all], want.size(), sparse ? " (sparse)" : "", (long long)holds);
       HIP_TRY(hipEventRecord(e->ev2, s));
       STEP(make_resident(e, want, s, &nfilled));
       if (nfilled > 0) {
@@ -169,7 +169,7 @@ struct PropRun {
         e->last.cells_filled += nfilled;
         if (sparse) e->last.sparse_fills++;
       }
-    } else if (e->tile_valid_lo != 0) {
+    } else if (e->cc.tile_valid_lo != 0) {
       STEP(populate_tile(e, s));
     }
     env = make_env(e);
@@ -342,7 +342,7 @@ struct PropRun {
     *lst = e->d_lists[kind][cur[kind]];
     if (kind == NEXT_RPKT || kind == NEXT_GAMMA || (kind == NEXT_MA && e->sort_ma)) {
       STEP(sort_by_key(e, s, e->d_lists[kind][cur[kind]], e->d_keys[kind][cur[kind]], cnt[kind], lst,
-                       kind == NEXT_RPKT ? r_nubins : (kind == NEXT_MA ? e->ma_bins : 1), e->tile_cells,
+                       kind == NEXT_RPKT ? r_nubins : (kind == NEXT_MA ? e->ma_bins : 1), e->cc.res.tile_cells,
                        kind == NEXT_MA ? (env.cellest_n_t > 0 ? INT32_MAX : e->sort_maxpc_t) : (env.cellest_n_r > 0 ? INT32_MAX : e->sort_maxpc_r),
                        (kind == NEXT_RPKT && r_nubins > 1 && e->sort_numajor) ? r_ngroups * r_nubins : 0, into));
     }
@@ -428,7 +428,7 @@ struct PropRun {
   // Tiled runs: does the visit leave what is left of it waiting in its cells? (Their state is in the packet store; the next classify pass lists
   // them again.) tail_now: the tail kernel would take them with its next launch.
   bool should_park(int sweep, int tile, int64_t tail_n, bool tail_now) {
-    if (!e->park_tails || e->ntiles <= 1 || visit_launches == 0) return false;
+    if (!e->park_tails || e->cc.ntiles <= 1 || visit_launches == 0) return false;
     // (round 6) a visit that began larger parks what is left of it once that has fallen to park_at packets -- BEFORE the long run
     // of small, latency-bound launches that its last packets would otherwise cost every visit: they wait in their cells and are listed
     // again, merged with the other windows' stragglers, by a later visit (a visit that BEGINS with that few runs them to their end)
@@ -455,11 +455,11 @@ struct PropRun {
     listed = count_listed();
     e->last.listed += listed;
     visit_launches = 0;
-    if (e->trace) fprintf(stderr, "[artis_amd] sweep %d tile %d of %d\n", sweep, tile, e->ntiles);
+    if (e->trace) fprintf(stderr, "[artis_amd] sweep %d tile %d of %d\n", sweep, tile, e->cc.ntiles);
     // the tail kernel takes the end of a population that began larger (a population that begins below the threshold runs on
     // the split kernels throughout, unless ARTIS_AMD_TAIL_ALWAYS=1)
     // (tiled runs: the later sweeps bring a tile a few stragglers at a time; each such visit is a tail from its first launch)
-    const bool tail_ok = e->tail_max > 0 && (e->tail_always || listed > e->tail_max || sweep > 0 || (adaptive && e->last_visits > e->ntiles));
+    const bool tail_ok = e->tail_max > 0 && (e->tail_always || listed > e->tail_max || sweep > 0 || (adaptive && e->last_visits > e->cc.ntiles));
     // k_late takes the r-packets and thermal packets of a population that began larger than late_max once that few are left (same rule; a small
     // population stays on the split kernels unless ARTIS_AMD_LATE_ALWAYS=1); the kinds it ejects run on their own kernels between its launches
     const bool late_ok = late_eligible() && (e->late_always || listed > e->late_max);
@@ -509,17 +509,17 @@ extern "C" int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_st
     e->bfrate_kept_dirty = true;
   }
   const PropRun::clk::time_point wall_t0 = PropRun::clk::now();
-  if (e->ntiles > 1 && e->d_waiting == nullptr) {
-    HIP_TRY(hipMalloc((void **)&e->d_waiting, sizeof(int32_t) * (size_t)(e->Mh.npts_nonempty + 1)));
-    e->h_waiting.assign((size_t)e->Mh.npts_nonempty + 1, 0);
+  if (e->cc.ntiles > 1 && e->cc.d_waiting == nullptr) {
+    HIP_TRY(hipMalloc((void **)&e->cc.d_waiting, sizeof(int32_t) * (size_t)(e->Mh.npts_nonempty + 1)));
+    e->cc.h_waiting.assign((size_t)e->Mh.npts_nonempty + 1, 0);
   }
   e->last_visits = 0;
   for (int sweep = 0;; sweep++) {
     bool any_active = false, all_done = false;
-    for (int tstep = 0; tstep < e->ntiles; tstep++) {
+    for (int tstep = 0; tstep < e->cc.ntiles; tstep++) {
       // sweeps alternate their direction: a packet that left its tile against the direction of one sweep is met by the next
       // one on its way back (with one direction it waits a whole sweep per backward crossing)
-      const int tile = (e->tile_zigzag && (sweep & 1)) ? e->ntiles - 1 - tstep : tstep;
+      const int tile = (e->tile_zigzag && (sweep & 1)) ? e->cc.ntiles - 1 - tstep : tstep;
       STEP(run.prepare_visit(tile, &all_done));
       if (all_done) break;
       STEP(run.classify());
@@ -528,7 +528,7 @@ extern "C" int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_st
       STEP(run.run_visit(sweep, tile));
     }
     if (any_active) e->last.sweeps++;
-    if (e->ntiles == 1 || !any_active || all_done) break;
+    if (e->cc.ntiles == 1 || !any_active || all_done) break;
   }
   for (int k = 1; k < NEXT_NKINDS; k++) e->last.propagate_ms += e->last.kms[k];
   e->last.propagate_ms += e->last.kms_tail + e->last.kms_late;

@@ -119,7 +119,7 @@ void setup(Emu &e, const artis_model *m, const artis_cellstate *cs, const artis_
 #endif
 }
 
-// the populate kernels, in launch order (artis_engine.hip: k_levelpops, k_line_dpop, k_cell_scalars, k_allcont, k_corrphotoion,
+// the populate kernels, in launch order (cellcache_kernels.h, launched by stage_cellcache.h launch_fill_batch: k_levelpops, k_line_dpop, k_cell_scalars, k_allcont, k_corrphotoion,
 // k_matrans, k_macroatom, k_cooling_head / _chain, k_collexc_filter, k_cooling_tail, k_cooling_prefix)
 void populate_all(Emu &e) {
   const DevModel &M = e.env.M;
