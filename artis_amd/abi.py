@@ -579,3 +579,64 @@ def grid_update_config(use_fit: bool, rho, elem_massfracs, thick, elem_meanweigh
         keep[k] = np.ascontiguousarray(v, dtype=dt)
         setattr(u, k, keep[k].ctypes.data_as(pt))
     return u, keep
+
+
+# decay and abundance update (include/artis_amd.h artis_amd_decay_*)
+DECAYTYPE_ALPHA, DECAYTYPE_ELECTRONCAPTURE, DECAYTYPE_BETAPLUS, DECAYTYPE_BETAMINUS, DECAYTYPE_NONE, DECAYTYPE_SPONTFISSION = range(6)
+
+
+class DecayModel(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("nnuclides", C.c_int32), ("npaths", C.c_int32), ("nuc_z", _I32P), ("nuc_a", _I32P),
+                ("nuc_meanlife", _F64P), ("path_start", _I32P), ("path_nucindex", _I32P), ("path_branchproduct", _F64P),
+                ("path_last_decaytype", _I32P), ("t_model", C.c_double), ("initnucmassfrac", _F32P),
+                ("elem_untrackedstable_initmassfrac", _F32P), ("elem_initstablemeannucmass", _F32P), ("rho_tmin", _F32P)]
+
+
+class DecayCoeffs(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("endnuc_coeff", _F64P), ("he4_coeff", _F64P), ("survivingfrac", _F64P)]
+
+
+class DecayResult(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("rho", _F32P), ("elem_massfracs", _F32P), ("elem_meanweight", _F32P), ("endnuc_coeff", _F64P),
+                ("he4_coeff", _F64P), ("survivingfrac", _F64P), ("path_scale", _F64P), ("path_x_dom", _F64P), ("nuc_massfracs", _F64P),
+                ("npts_nonempty", C.c_int32), ("nelements", C.c_int32), ("nnuclides", C.c_int32), ("npaths", C.c_int32),
+                ("he4_nucindex", C.c_int32), ("have_nuclides", C.c_int32), ("kernel_ms", C.c_double * 3), ("t_mid", C.c_double)]
+
+
+_DECAY_MODEL_ARRAYS = (("nuc_z", np.int32), ("nuc_a", np.int32), ("nuc_meanlife", np.float64), ("path_start", np.int32),
+                       ("path_nucindex", np.int32), ("path_branchproduct", np.float64), ("path_last_decaytype", np.int32),
+                       ("initnucmassfrac", np.float32), ("elem_untrackedstable_initmassfrac", np.float32),
+                       ("elem_initstablemeannucmass", np.float32), ("rho_tmin", np.float32))
+
+
+def decay_model(d: dict):
+    """(DecayModel, the arrays it points into: keep them alive while it is used) from a dict over artis_decay_model's fields
+    (synth.decay_model); an array that is None or missing stays a NULL pointer"""
+    types = dict(DecayModel._fields_)
+    keep = {}
+    m = DecayModel(struct_size=C.sizeof(DecayModel), nnuclides=len(d["nuc_z"]), npaths=len(d["path_start"]) - 1, t_model=float(d["t_model"]))
+    for k, dt in _DECAY_MODEL_ARRAYS:
+        if d.get(k) is None:
+            continue
+        a = np.ascontiguousarray(d[k], dtype=dt).reshape(-1)
+        keep[k] = a if a.size else np.zeros(1, dt)
+        setattr(m, k, keep[k].ctypes.data_as(types[k]))
+    return m, keep
+
+
+def decay_coeffs(endnuc_coeff, he4_coeff, survivingfrac):
+    """(DecayCoeffs, the arrays it points into)"""
+    keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (endnuc_coeff, he4_coeff, survivingfrac)]
+    c = DecayCoeffs(struct_size=C.sizeof(DecayCoeffs), endnuc_coeff=keep[0].ctypes.data_as(_F64P), he4_coeff=keep[1].ctypes.data_as(_F64P),
+                    survivingfrac=keep[2].ctypes.data_as(_F64P))
+    return c, keep
+
+
+def decay_arrays(ncell: int, nelements: int, nnuclides: int, npaths: int, nuclides: bool) -> dict:
+    """zeroed host arrays for the outputs of artis_decay_result (the keys are its field names)"""
+    out = dict(rho=np.zeros(ncell, np.float32), elem_massfracs=np.zeros(ncell * nelements, np.float32),
+               elem_meanweight=np.zeros(ncell * nelements, np.float32), endnuc_coeff=np.zeros(npaths), he4_coeff=np.zeros(npaths),
+               survivingfrac=np.zeros(nnuclides), path_scale=np.zeros(npaths), path_x_dom=np.zeros(npaths))
+    if nuclides:
+        out["nuc_massfracs"] = np.zeros(ncell * nnuclides)
+    return out

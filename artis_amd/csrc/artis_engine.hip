@@ -30,6 +30,7 @@
 #include "physics.h"
 #include "radfield_fit.h"
 #include "ion_balance.h"
+#include "decay_update.h"
 #include "spectra.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -1863,6 +1864,8 @@ struct RfState;
 void rf_free(RfState *st);
 struct IbState;
 void ib_free(IbState *st);
+struct DecayState;
+void decay_free(DecayState *st);
 
 }  // namespace
 
@@ -1932,6 +1935,7 @@ struct artis_amd_engine {
   SpecState *spec = nullptr;  // artis_amd_spectra_*: nothing until the first call
   RfState *rf = nullptr;      // artis_amd_radfield_*: nothing until the first call
   IbState *ib = nullptr;      // artis_amd_grid_update*: nothing until the first call
+  DecayState *decay = nullptr;  // artis_amd_decay_*: nothing until artis_amd_decay_setup
   bool fit_since_step = false;  // an artis_amd_radfield_fit since the last propagation call (artis_amd_grid_update use_fit)
   ModelOwned own;
   std::vector<void *> model_allocs;
@@ -2980,6 +2984,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   spec_free(e->spec);
   rf_free(e->rf);
   ib_free(e->ib);
+  decay_free(e->decay);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->cc.d_krow, e->cc.d_fill_cells, e->cc.d_waiting,
                   e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts};
@@ -3574,10 +3579,11 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ the cell cache's host side; the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance
+// ------------------------------------------------------------------ the cell cache's host side; the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance, decay update
 #include "stage_cellcache.h"
 #include "stage_propagate.h"
 #include "stage_common.h"
 #include "stage_spectra.h"
 #include "stage_radfield.h"
 #include "stage_ionbal.h"
+#include "stage_decay.h"

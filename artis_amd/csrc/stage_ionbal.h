@@ -132,11 +132,13 @@ int ib_init(artis_amd_engine *e) {
   return ARTIS_OK;
 }
 
-}  // namespace
+// where the new timestep's matter comes from when not from the host: device arrays (artis_amd_grid_update_decayed, stage_decay.h)
+struct IbMatter {
+  const float *rho, *massfrac, *meanweight;
+};
 
-extern "C" {
-
-int artis_amd_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream) {
+// artis_amd_grid_update (matter == nullptr: u's host arrays) and artis_amd_grid_update_decayed (matter: copied device to device into the same scratch)
+int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream, const IbMatter *matter) {
   if (!e || !u || !ts_next) return stage_error(ARTIS_ERR_ARG, "grid_update: null engine, update or timestep");
 #ifdef ARTIS_PRESET_NLTENEBULAR
   return stage_error(ARTIS_ERR_UNSUPPORTED, "grid_update: this build has NLTE populations (the nebular family): the ion balance is the host's");
@@ -147,8 +149,9 @@ int artis_amd_grid_update(artis_amd_engine *e, const artis_grid_update *u, const
   if (u->use_fit && (!e->rf || !e->rf->valid || !e->fit_since_step))
     return stage_error(ARTIS_ERR_ARG, "grid_update: use_fit = 1 needs an artis_amd_radfield_fit since the last propagation call");
   if (!u->use_fit && (!u->TJ || !u->TR || !u->W || !u->Te)) return stage_error(ARTIS_ERR_ARG, "grid_update: use_fit = 0 needs TJ, TR, W and Te");
-  if (!u->rho || !u->elem_massfracs || !u->thick) return stage_error(ARTIS_ERR_ARG, "grid_update: rho, elem_massfracs and thick are required");
-  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !u->elem_meanweight)
+  if (!matter && (!u->rho || !u->elem_massfracs || !u->thick)) return stage_error(ARTIS_ERR_ARG, "grid_update: rho, elem_massfracs and thick are required");
+  if (matter && !u->thick) return stage_error(ARTIS_ERR_ARG, "grid_update: thick is required");
+  if (!matter && ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !u->elem_meanweight)
     return stage_error(ARTIS_ERR_ARG, "grid_update: this build has USE_CALCULATED_MEANATOMICWEIGHT: elem_meanweight is required");
   if (!ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !e->M.elem_meannucmass)
     return stage_error(ARTIS_ERR_ARG, "grid_update: the element number densities need artis_model.elem_meannucmass");
@@ -159,10 +162,12 @@ int artis_amd_grid_update(artis_amd_engine *e, const artis_grid_update *u, const
   st->valid = false;
   hipStream_t s = (hipStream_t)hip_stream;
   const int64_t n = st->ncell, ni = st->nions, ne = st->nelements;
-  HIP_TRY(stage_copy(st->d_rho, u->rho, n, hipMemcpyHostToDevice, &s));
-  HIP_TRY(stage_copy(st->d_massfrac, u->elem_massfracs, n * ne, hipMemcpyHostToDevice, &s));
+  const hipMemcpyKind from_matter = matter ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIP_TRY(stage_copy(st->d_rho, matter ? matter->rho : u->rho, n, from_matter, &s));
+  HIP_TRY(stage_copy(st->d_massfrac, matter ? matter->massfrac : u->elem_massfracs, n * ne, from_matter, &s));
   HIP_TRY(stage_copy(st->d_thick, u->thick, n, hipMemcpyHostToDevice, &s));
-  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT) HIP_TRY(stage_copy(st->d_meanweight, u->elem_meanweight, n * ne, hipMemcpyHostToDevice, &s));
+  if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT)
+    HIP_TRY(stage_copy(st->d_meanweight, matter ? matter->meanweight : u->elem_meanweight, n * ne, from_matter, &s));
   HIP_TRY(stage_copy(st->d_kappagrey, u->kappagrey, n, hipMemcpyHostToDevice, &s));
   HIP_TRY(stage_copy(st->d_clump, u->clumpfactor, n, hipMemcpyHostToDevice, &s));
   HIP_TRY(stage_copy(st->d_ffegrp, u->ffegrp, n, hipMemcpyHostToDevice, &s));
@@ -299,6 +304,14 @@ int artis_amd_grid_update(artis_amd_engine *e, const artis_grid_update *u, const
   rc = artis_amd_populate_cellcache(e, hip_stream);
   st->kernel_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int artis_amd_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream) {
+  return ib_grid_update(e, u, ts_next, hip_stream, nullptr);
 }
 
 int artis_amd_grid_update_download(artis_amd_engine *e, artis_grid_update_result *out) {

@@ -68,6 +68,10 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_radfield_download.argtypes = [C.c_void_p, C.POINTER(abi.Radfield)]
     L.artis_amd_grid_update.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
     L.artis_amd_grid_update_download.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdateResult)]
+    L.artis_amd_decay_setup.argtypes = [C.c_void_p, C.POINTER(abi.DecayModel)]
+    L.artis_amd_decay_update.argtypes = [C.c_void_p, C.c_double, C.POINTER(abi.DecayCoeffs), C.c_int, C.c_void_p]
+    L.artis_amd_decay_download.argtypes = [C.c_void_p, C.POINTER(abi.DecayResult)]
+    L.artis_amd_grid_update_decayed.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -94,6 +98,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_spectra_compute", "artis_amd_spectra_devptr", "artis_amd_spectra_download",
     "artis_amd_radfield_fit", "artis_amd_radfield_download",
     "artis_amd_grid_update", "artis_amd_grid_update_download",
+    "artis_amd_decay_setup", "artis_amd_decay_update", "artis_amd_decay_download", "artis_amd_grid_update_decayed",
     "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
     "artis_amd_sizeof_plan", "artis_amd_engine_plan",
 ]
@@ -297,6 +302,60 @@ class Engine:
         out["total_evals"] = int(info.total_evals)
         out["kernel_ms"] = tuple(float(x) for x in info.kernel_ms)
         return out
+
+    # decay and abundance update of the grid update (include/artis_amd.h artis_amd_decay_*)
+    def decay_setup(self, decay_model: dict):
+        """Validate and upload a decay network with the cells' initial composition: a dict over artis_decay_model's fields
+        (synth.decay_model). A second call replaces the first."""
+        m, keep = abi.decay_model(decay_model)
+        self._check(self.L.artis_amd_decay_setup(self.h, C.byref(m)))
+        del keep
+
+    def decay_update(self, t_mid: float, coeffs=None, want_nuclides: bool = False, stream: int = 0) -> dict:
+        """rho, element mass fractions and mean weights of every cell at t_mid on the device; coeffs: a dict with endnuc_coeff, he4_coeff
+        and survivingfrac from the host (used as they are), or None (the device forms them). Returns the download."""
+        c, keep = (None, None) if coeffs is None else abi.decay_coeffs(coeffs["endnuc_coeff"], coeffs["he4_coeff"], coeffs["survivingfrac"])
+        self._check(self.L.artis_amd_decay_update(self.h, float(t_mid), C.byref(c) if c is not None else None, int(bool(want_nuclides)),
+                                                  C.c_void_p(stream)))
+        del keep
+        return self.decay_download()
+
+    def decay_download(self) -> dict:
+        """numpy arrays under the field names of artis_decay_result (elem_* [ncell, nelements], nuc_massfracs [ncell, nnuclides] when the
+        update was asked for them), "he4_nucindex", "kernel_ms" (coefficients, cells, nuclides) and "t_mid".
+        """
+        info = abi.DecayResult(struct_size=C.sizeof(abi.DecayResult))
+        self._check(self.L.artis_amd_decay_download(self.h, C.byref(info)))  # sizes first
+        n, ne, nn, npaths = info.npts_nonempty, info.nelements, info.nnuclides, info.npaths
+        out = abi.decay_arrays(n, ne, nn, npaths, bool(info.have_nuclides))
+        types = dict(abi.DecayResult._fields_)
+        for k, v in out.items():
+            if v.size:
+                setattr(info, k, v.ctypes.data_as(types[k]))
+        self._check(self.L.artis_amd_decay_download(self.h, C.byref(info)))
+        out["elem_massfracs"] = out["elem_massfracs"].reshape(n, ne)
+        out["elem_meanweight"] = out["elem_meanweight"].reshape(n, ne)
+        if "nuc_massfracs" in out:
+            out["nuc_massfracs"] = out["nuc_massfracs"].reshape(n, nn)
+        out.update(he4_nucindex=int(info.he4_nucindex), kernel_ms=tuple(float(x) for x in info.kernel_ms), t_mid=float(info.t_mid))
+        return out
+
+    def decay_download_times(self):
+        """the HIP-event times [ms] of the last decay_update's kernels (coefficients, cells, nuclides), without copying an array"""
+        info = abi.DecayResult(struct_size=C.sizeof(abi.DecayResult))
+        self._check(self.L.artis_amd_decay_download(self.h, C.byref(info)))
+        return tuple(float(x) for x in info.kernel_ms)
+
+    def grid_update_decayed(self, ts_next: abi.Timestep, thick, use_fit: bool = True, TJ=None, TR=None, W=None, Te=None, kappagrey=None,
+                            clumpfactor=None, ffegrp=None, stream: int = 0, _matter=None) -> dict:
+        """grid_update with rho, elem_massfracs and elem_meanweight of the last decay_update(ts_next.mid), which never leave the device.
+        (_matter: (rho, elem_massfracs, elem_meanweight) handed over all the same, which the library refuses: for the tests.)"""
+        rho, mf, mw = _matter if _matter is not None else (None, None, None)
+        u, keep = abi.grid_update_config(use_fit, rho, mf, thick, mw, TJ, TR, W, Te, kappagrey, clumpfactor, ffegrp)
+        self._check(self.L.artis_amd_grid_update_decayed(self.h, C.byref(u), C.cast(ts_next.ref(), C.c_void_p), C.c_void_p(stream)))
+        self._ts = ts_next
+        del keep
+        return self.grid_update_download()
 
     def debug_cellcache(self, c: int) -> dict:
         d = self.model.d

@@ -950,3 +950,134 @@ def nebular_cellstate(atomic: dict, cells: dict, ncell: int, seed: int = 201, nb
     W[rng.random((ncell, nb)) < 0.05] = -1.0
     TR = np.asarray(cells["TR"], dtype=np.float64)[:, None] * rng.uniform(0.7, 1.3, size=(ncell, nb))
     return dict(levelpops=pops.ravel(), corrphotoioncoeff=corr.ravel(), radfieldbin_W=W.ravel(), radfieldbin_T_R=TR.ravel())
+
+
+# ---- decay networks for artis_amd_decay_* (include/artis_amd.h). Half-lives and branchings are synthetic where it helps a test: the
+# update is arithmetic over whatever network the host hands over.
+_DECAY_ORDER = (abi.DECAYTYPE_ALPHA, abi.DECAYTYPE_ELECTRONCAPTURE, abi.DECAYTYPE_BETAPLUS, abi.DECAYTYPE_BETAMINUS)  # decay.h:30
+
+
+def _daughter(z: int, a: int, decaytype: int):
+    if decaytype == abi.DECAYTYPE_ALPHA:
+        return z - 2, a - 4
+    if decaytype in (abi.DECAYTYPE_ELECTRONCAPTURE, abi.DECAYTYPE_BETAPLUS):
+        return z - 1, a
+    return z + 1, a
+
+
+def _small_network(he4: bool):
+    """[(z, a, meanlife [s], {decaytype: branch probability})]: four supernova chains with EC / beta+ branches to one daughter, a
+    uranium-like series of 16 nuclides (mean lives from 2e17 s to 2.4e-4 s; Po218 branches alpha / beta-, so two paths share top and end),
+    one synthetic alpha emitter whose daughter is Fe56, a synthetic Co55 -> Fe55, and He4"""
+    EC, BP, BM, AL = abi.DECAYTYPE_ELECTRONCAPTURE, abi.DECAYTYPE_BETAPLUS, abi.DECAYTYPE_BETAMINUS, abi.DECAYTYPE_ALPHA
+    nucs = [
+        (28, 56, 8.80 * DAY, {EC: 1.0}), (27, 56, 113.7 * DAY, {EC: 0.81, BP: 0.19}), (26, 56, -1.0, {}),
+        (28, 57, 51.36 * 3600, {EC: 0.56, BP: 0.44}), (27, 57, 392.03 * DAY, {EC: 1.0}), (26, 57, -1.0, {}),
+        (26, 52, 0.497429 * DAY, {EC: 0.44, BP: 0.56}), (25, 52, 0.0211395 * DAY, {EC: 0.03, BP: 0.97}), (24, 52, -1.0, {}),
+        (24, 48, 1.29602 * DAY, {EC: 0.98, BP: 0.02}), (23, 48, 23.0442 * DAY, {EC: 0.5, BP: 0.5}), (22, 48, -1.0, {}),
+        (27, 55, 25.3 * 3600, {EC: 0.24, BP: 0.76}), (26, 55, -1.0, {}),
+        (28, 60, 3.1e6, {AL: 1.0}),
+        (92, 238, 2.03e17, {AL: 1.0}), (90, 234, 3.0e6, {BM: 1.0}), (91, 234, 3.5e4, {BM: 1.0}), (92, 234, 1.1e13, {AL: 1.0}),
+        (90, 230, 3.4e12, {AL: 1.0}), (88, 226, 7.3e10, {AL: 1.0}), (86, 222, 4.77e5, {AL: 1.0}), (84, 218, 268.0, {AL: 0.98, BM: 0.02}),
+        (82, 214, 2320.0, {BM: 1.0}), (85, 218, 2.16, {AL: 1.0}), (83, 214, 1723.0, {BM: 1.0}), (84, 214, 2.37e-4, {AL: 1.0}),
+        (82, 210, 1.01e9, {BM: 1.0}), (83, 210, 6.2e5, {BM: 1.0}), (84, 210, 1.73e7, {AL: 1.0}), (82, 206, -1.0, {}),
+    ]
+    if he4:
+        nucs.append((2, 4, -1.0, {}))
+    return nucs
+
+
+def _chain_network(nchains: int, length: int, seed: int, zends=(26, 27, 28)):
+    """nchains isobaric beta- chains of `length` nuclides each (the last one stable), ending on the elements zends in turn: a network
+    of kilonova size whose long rows fall on elements a model holds"""
+    rng = np.random.default_rng(seed)
+    nucs = []
+    for k in range(nchains):
+        zend, a = zends[k % len(zends)], 60 + k
+        lives = np.sort(10.0 ** rng.uniform(-1.0, 8.0, length - 1))
+        for i in range(length - 1):
+            nucs.append((zend - (length - 1) + i, a, float(lives[i]), {abi.DECAYTYPE_BETAMINUS: 1.0}))
+        nucs.append((zend, a, -1.0, {}))
+    return nucs
+
+
+def decay_network(kind: str = "small", seed: int = 11) -> dict:
+    """Nuclides and ALL decay paths of a network: every sub-path from every radioactive top, found depth first by decay type in the
+    order of decay.h:30 and sorted as decay.cc:401-420 sorts them (by (A, Z) along the path without its last nuclide, the shorter
+    first; stable). kind: "small" (31 nuclides + He4), "small_nohe4", "large" (200 chains of 15: 3000 nuclides, 21000 paths).
+    Keys: the network fields of artis_decay_model."""
+    import functools
+
+    if kind in ("small", "small_nohe4"):
+        nucs = _small_network(kind == "small")
+    elif kind == "large":
+        nucs = _chain_network(200, 15, seed)
+    else:
+        raise ValueError(kind)
+    index = {(z, a): i for i, (z, a, _, _) in enumerate(nucs)}
+    paths = []  # (nucindex list, branchproduct, last decay type)
+
+    def extend(path, branch):
+        z, a, life, decays = nucs[path[-1]]
+        if life <= 0:
+            return
+        for dt in _DECAY_ORDER:
+            if decays.get(dt, 0.0) == 0.0:
+                continue
+            dz, da = _daughter(z, a, dt)
+            d = index[(dz, da)]
+            assert d not in path, "loop in the decay network"
+            paths.append((path + [d], branch * decays[dt], dt))
+            extend(path + [d], branch * decays[dt])
+
+    for i, (z, a, life, _) in enumerate(nucs):
+        if life > 0:
+            extend([i], 1.0)
+
+    def cmp(p1, p2):
+        n1, n2 = len(p1[0]), len(p2[0])
+        for i in range(min(n1, n2) - 1):
+            k1, k2 = (nucs[p1[0][i]][1], nucs[p1[0][i]][0]), (nucs[p2[0][i]][1], nucs[p2[0][i]][0])
+            if k1 != k2:
+                return -1 if k1 < k2 else 1
+        return (n1 > n2) - (n1 < n2)
+
+    paths = sorted(paths, key=functools.cmp_to_key(cmp))
+    start = np.concatenate([[0], np.cumsum([len(p[0]) for p in paths])]).astype(np.int32)
+    return dict(nuc_z=np.array([n[0] for n in nucs], np.int32), nuc_a=np.array([n[1] for n in nucs], np.int32),
+                nuc_meanlife=np.array([n[2] for n in nucs], np.float64), path_start=start,
+                path_nucindex=np.array([i for p in paths for i in p[0]], np.int32),
+                path_branchproduct=np.array([p[1] for p in paths], np.float64),
+                path_last_decaytype=np.array([p[2] for p in paths], np.int32))
+
+
+def decay_model(model: abi.Model, cs: abi.CellState, aux: dict, network: dict, t_model: float = DAY, seed: int = 21, zero_cell: int = 1) -> dict:
+    """A dict over artis_decay_model's fields for a grid made by build(): every cell's element mass fractions split over the
+    element's nuclides (random shares) and an untracked stable rest; an element without a nuclide is all untracked, except in cell
+    zero_cell, where it has none (its mean weight falls back to the stable mean); nuclides of elements the model lacks get small
+    mass fractions of their own. rho_tmin is the model's."""
+    rng = np.random.default_rng(seed)
+    n, ne = int(model["npts_nonempty"]), int(model["nelements"])
+    Z = [int(z) for z in model["elem_anumber"]]
+    nz = np.asarray(network["nuc_z"])
+    nn = len(nz)
+    mf = np.asarray(cs["elem_massfracs"], np.float64).reshape(n, ne)
+    X = np.zeros((n, nn))
+    untracked = np.zeros((n, ne))
+    for el, z in enumerate(Z):
+        mine = np.nonzero(nz == z)[0]
+        if len(mine) == 0:
+            untracked[:, el] = mf[:, el]
+            untracked[zero_cell % n, el] = 0.0
+            continue
+        shares = rng.uniform(0.05, 1.0, (n, len(mine) + 1))
+        shares /= shares.sum(axis=1, keepdims=True)
+        X[:, mine] = mf[:, [el]] * shares[:, :-1]
+        untracked[:, el] = mf[:, el] * shares[:, -1]
+    others = np.nonzero(~np.isin(nz, Z))[0]
+    X[:, others] = 10.0 ** rng.uniform(-6.0, -4.0, (n, len(others)))
+    out = dict(network)
+    out.update(t_model=float(t_model), initnucmassfrac=X.astype(np.float32), elem_untrackedstable_initmassfrac=untracked.astype(np.float32),
+               elem_initstablemeannucmass=(np.array([_AMASS.get(z, 2.0 * z) for z in Z]) * MH).astype(np.float32),
+               rho_tmin=np.asarray(model["rho_tmin"], np.float32))
+    return out

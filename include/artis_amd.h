@@ -479,7 +479,9 @@ typedef struct artis_amd_engine artis_amd_engine;
 #define ARTIS_ERR_RCCL (-6)
 
 const char *artis_amd_last_error(void);
-/* 6 -- and it stays 6 with the engine configuration (artis_amd_config, artis_amd_plan and their four functions below): functions were added,
+/* 6 -- and it stays 6 with the decay and abundance update (artis_decay_model, artis_decay_coeffs, artis_decay_result and the four functions
+ * artis_amd_decay_setup / _update / _download and artis_amd_grid_update_decayed): new functions and new structs only, no existing one changed.
+ * It stayed 6 with the engine configuration (artis_amd_config, artis_amd_plan and their four functions below): functions were added,
  * no existing struct or function changed, so a caller built against the earlier header of version 6 runs unchanged.
  * 6: artis_amd_record_tiers() added (no struct changed); 5: virtual-packet configuration and spectra appended;
  * 4: artis_cellstate.elem_meanweight appended (3: cell state and estimators of the nltenebular options) */
@@ -857,7 +859,8 @@ typedef struct artis_grid_update {
   const float *TJ, *TR, *W; /* [npts_nonempty], required when use_fit == 0 */
   const float *Te;          /* [npts_nonempty] or NULL: T_e of cells the fit did not set (its fitted cells: the host's T_e
                                solve); NULL keeps the cell's current T_e. use_fit == 0: required */
-  /* the new timestep's matter, which the host's decay / abundance update (update_grid.cc:714-720) still produces */
+  /* the new timestep's matter: the host's decay / abundance update (update_grid.cc:714-720), or -- all three NULL, through
+   * artis_amd_grid_update_decayed -- the engine's own (artis_amd_decay_update) */
   const float *rho;               /* [npts_nonempty] */
   const float *elem_massfracs;    /* [npts_nonempty*nelements] */
   const float *elem_meanweight;   /* [npts_nonempty*nelements]: USE_CALCULATED_MEANATOMICWEIGHT builds only (elsewhere the
@@ -887,6 +890,63 @@ typedef struct artis_grid_update_result {
 int artis_amd_grid_update(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream);
 /* Copy the result of the last artis_amd_grid_update to the host (also after a refused call: its flags and counts). */
 int artis_amd_grid_update_download(artis_amd_engine *eng, artis_grid_update_result *out);
+
+/* ---- decay and abundance update ---------------------------------------------------------
+ * The composition part of the reference's grid update (update_grid.cc:710-720) on the device: decay::calc_nuc_massfrac_coeffs
+ * (decay.cc:1284: per decay path the Bateman sum at t_mid - t_model, decay.h:56 without the expansion factor; per nuclide the
+ * surviving fraction), decay::update_abundances (decay.cc:1230: per cell the nuclides' mass fractions as the sparse product of those
+ * coefficients with the cell's initial nuclide mass fractions, summed to element mass fractions and mean weights) and set_rho
+ * (update_grid.cc:718). Every output element has one writer and is the sequential sum of its contributions in decay-path order: the
+ * result is bitwise reproducible, and with the host's coefficients handed in it is the host's bit for bit. Works in every build. */
+typedef struct artis_decay_model {
+  int64_t struct_size;                /* sizeof(artis_decay_model) */
+  int32_t nnuclides;
+  int32_t npaths;
+  const int32_t *nuc_z, *nuc_a;       /* [nnuclides] */
+  const double *nuc_meanlife;         /* [nnuclides] seconds; <= 0: stable */
+  const int32_t *path_start;          /* [npaths + 1] into path_nucindex */
+  const int32_t *path_nucindex;       /* flat: every path's nuclides, top ... end (decay.cc DecayPath::nucindex) */
+  const double *path_branchproduct;   /* [npaths] */
+  const int32_t *path_last_decaytype; /* [npaths] ARTIS_DECAYTYPE_* of the step into the end nuclide */
+  double t_model;                     /* grid::get_t_model() */
+  const float *initnucmassfrac;                   /* [npts_nonempty][nnuclides] grid::get_modelinitnucmassfrac, in non-empty order */
+  const float *elem_untrackedstable_initmassfrac; /* [npts_nonempty][nelements] */
+  const float *elem_initstablemeannucmass;        /* [nelements] */
+  const float *rho_tmin;                          /* [npts_nonempty] */
+} artis_decay_model;
+typedef struct artis_decay_coeffs {
+  int64_t struct_size;          /* sizeof(artis_decay_coeffs) */
+  const double *endnuc_coeff;   /* [npaths] NucMassFracCoeffs::decaypath_endnuc_coeff */
+  const double *he4_coeff;      /* [npaths] */
+  const double *survivingfrac;  /* [nnuclides] */
+} artis_decay_coeffs;
+typedef struct artis_decay_result {
+  int64_t struct_size; /* sizeof(artis_decay_result) */
+  /* host arrays to fill; NULL: skip */
+  float *rho;                                         /* [npts_nonempty] */
+  float *elem_massfracs, *elem_meanweight;            /* [npts_nonempty*nelements] */
+  double *endnuc_coeff, *he4_coeff, *survivingfrac;   /* the coefficients the device used */
+  double *path_scale, *path_x_dom;                    /* [npaths] of the end nuclide's Bateman sum: lambdaproduct * largest |term|, and lambda * (t_mid - t_model)
+                                                         of that term (zero when the coefficients were handed in) */
+  double *nuc_massfracs;                              /* [npts_nonempty][nnuclides]; ARTIS_ERR_ARG unless the update was asked for them */
+  /* reported */
+  int32_t npts_nonempty, nelements, nnuclides, npaths;
+  int32_t he4_nucindex, have_nuclides;
+  double kernel_ms[3]; /* HIP-event time: [0] k_decay_coeffs, [1] k_decay_cells, [2] k_decay_nuclides */
+  double t_mid;
+} artis_decay_result;
+/* Validate the network (ARTIS_ERR_ARG with a text naming the path: a path shorter than 2, a nuclide index out of range, a nuclide before
+ * a path's end with meanlife <= 0, two equal decay constants in a path, a non-finite or negative input), build the product's rows,
+ * upload everything. A second call replaces the first. */
+int artis_amd_decay_setup(artis_amd_engine *eng, const artis_decay_model *model);
+/* The update at t_mid on hip_stream (synchronous). coeffs_or_null: the host's coefficients, used as they are; NULL: the device forms
+ * them. want_nuclides: also every nuclide's mass fraction. ARTIS_ERR_ARG without a set-up or for t_mid < t_model. */
+int artis_amd_decay_update(artis_amd_engine *eng, double t_mid, const artis_decay_coeffs *coeffs_or_null, int want_nuclides, void *hip_stream);
+/* Copy the results of the last update to the host (sizes in the reported fields even when every pointer is NULL). */
+int artis_amd_decay_download(artis_amd_engine *eng, artis_decay_result *out);
+/* artis_amd_grid_update with the matter of the last artis_amd_decay_update: u->rho, u->elem_massfracs and u->elem_meanweight must be NULL;
+ * ARTIS_ERR_ARG unless a decay update is valid and its t_mid == ts_next->mid. */
+int artis_amd_grid_update_decayed(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream);
 
 #ifdef __cplusplus
 }
