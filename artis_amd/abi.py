@@ -640,3 +640,67 @@ def decay_arrays(ncell: int, nelements: int, nnuclides: int, npaths: int, nuclid
     if nuclides:
         out["nuc_massfracs"] = np.zeros(ncell * nnuclides)
     return out
+
+
+# deposition rates and thickness (include/artis_amd.h artis_amd_deposition_*)
+DEP_NCHANNELS, DEP_NVECTORS, DEP_NTOTALS = 5, 11, 15
+CELL_THIN, CELL_THICK, CELL_THICK_VPKT_ONLY = 0, 1, 2  # ARTIS_CELL_*
+DEP_CHANNELS = ("gamma", "positron", "electron", "alpha", "spfission")
+DEP_VECTORS = DEP_CHANNELS + tuple(f"qdot_{k}" for k in ("alpha", "electroncapture", "betaplus", "betaminus", "none", "spfission"))
+DEP_TOTALS = ("gamma_dep", "positron_dep", "electron_dep", "alpha_dep") + tuple(f"eps_{k}_ana_power" for k in DEP_CHANNELS) + DEP_VECTORS[5:]
+
+
+class DepositionModel(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("nnuclides", C.c_int32), ("npts_nonempty", C.c_int32), ("nuc_endecay_gamma", _F64P),
+                ("nuc_endecay_particle", _F64P), ("nuc_endecay_q", _F64P), ("nuc_branchprob", _F64P), ("assocvolume_tmin", _F64P),
+                ("radial_pos_tmin", _F64P)]
+
+
+class DepositionParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("mid", C.c_double), ("width", C.c_double), ("nts", C.c_int32), ("nprocs", C.c_int32),
+                ("nts_next", C.c_int32), ("num_grey_timesteps", C.c_int32), ("optical_depth_is_thick", C.c_double),
+                ("optical_depth_is_thick_vpkt", C.c_double), ("power_vectors", _F64P)]
+
+
+class DepositionResult(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("eps_ana", _F64P), ("dep", _F64P), ("ntlepton_deposition_rate_density", _F64P),
+                ("grey_depth", _F32P), ("thick", _I32P), ("power_vectors", _F64P), ("totmassnuclide", _F64P),
+                ("totals", C.c_double * DEP_NTOTALS), ("mtot", C.c_double), ("npts_nonempty", C.c_int32), ("nnuclides", C.c_int32),
+                ("nradioactive", C.c_int32), ("nts_next", C.c_int32), ("t_mid", C.c_double), ("kernel_ms", C.c_double * 3)]
+
+
+_DEP_MODEL_ARRAYS = ("nuc_endecay_gamma", "nuc_endecay_particle", "nuc_endecay_q", "nuc_branchprob", "assocvolume_tmin", "radial_pos_tmin")
+
+
+def deposition_model(d: dict):
+    """(DepositionModel, the arrays it points into: keep them alive while it is used) from a dict over artis_deposition_model's array
+    fields (synth.decay_energies, synth.assocvolume_tmin, synth.radial_pos_tmin); an array that is None or missing stays a NULL
+    pointer; the counts are the arrays' unless the dict names them"""
+    keep = {}
+    m = DepositionModel(struct_size=C.sizeof(DepositionModel), nnuclides=int(d.get("nnuclides", len(d["nuc_endecay_gamma"]))),
+                        npts_nonempty=int(d.get("npts_nonempty", len(d["assocvolume_tmin"]))))
+    for k in _DEP_MODEL_ARRAYS:
+        if d.get(k) is None:
+            continue
+        a = np.ascontiguousarray(d[k], dtype=np.float64).reshape(-1)
+        keep[k] = a if a.size else np.zeros(1)
+        setattr(m, k, keep[k].ctypes.data_as(_F64P))
+    return m, keep
+
+
+def deposition_params(mid: float, width: float, nts: int, nts_next: int, num_grey_timesteps: int, optical_depth_is_thick: float,
+                      optical_depth_is_thick_vpkt: float = 0.0, nprocs: int = 1, power_vectors=None):
+    """(DepositionParams, the array it points into)"""
+    keep = None if power_vectors is None else np.ascontiguousarray(power_vectors, dtype=np.float64).reshape(-1)
+    p = DepositionParams(struct_size=C.sizeof(DepositionParams), mid=mid, width=width, nts=nts, nprocs=nprocs, nts_next=nts_next,
+                         num_grey_timesteps=num_grey_timesteps, optical_depth_is_thick=optical_depth_is_thick,
+                         optical_depth_is_thick_vpkt=optical_depth_is_thick_vpkt,
+                         power_vectors=keep.ctypes.data_as(_F64P) if keep is not None else None)
+    return p, keep
+
+
+def deposition_arrays(ncell: int, nnuclides: int) -> dict:
+    """zeroed host arrays for the outputs of artis_deposition_result (the keys are its field names)"""
+    return dict(eps_ana=np.zeros(DEP_NCHANNELS * ncell), dep=np.zeros(DEP_NCHANNELS * ncell), ntlepton_deposition_rate_density=np.zeros(ncell),
+                grey_depth=np.zeros(ncell, np.float32), thick=np.zeros(ncell, np.int32), power_vectors=np.zeros(DEP_NVECTORS * nnuclides),
+                totmassnuclide=np.zeros(nnuclides))

@@ -31,6 +31,7 @@
 #include "radfield_fit.h"
 #include "ion_balance.h"
 #include "decay_update.h"
+#include "deposition.h"
 #include "spectra.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -1866,6 +1867,8 @@ struct IbState;
 void ib_free(IbState *st);
 struct DecayState;
 void decay_free(DecayState *st);
+struct DepState;
+void dep_free(DepState *st);
 
 }  // namespace
 
@@ -1936,6 +1939,7 @@ struct artis_amd_engine {
   RfState *rf = nullptr;      // artis_amd_radfield_*: nothing until the first call
   IbState *ib = nullptr;      // artis_amd_grid_update*: nothing until the first call
   DecayState *decay = nullptr;  // artis_amd_decay_*: nothing until artis_amd_decay_setup
+  DepState *dep = nullptr;      // artis_amd_deposition_*: nothing until artis_amd_deposition_setup
   bool fit_since_step = false;  // an artis_amd_radfield_fit since the last propagation call (artis_amd_grid_update use_fit)
   ModelOwned own;
   std::vector<void *> model_allocs;
@@ -2985,6 +2989,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   rf_free(e->rf);
   ib_free(e->ib);
   decay_free(e->decay);
+  dep_free(e->dep);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->cc.d_krow, e->cc.d_fill_cells, e->cc.d_waiting,
                   e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts};
@@ -3579,7 +3584,7 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ the cell cache's host side; the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance, decay update
+// ------------------------------------------------------------------ the cell cache's host side; the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance, decay update, deposition rates
 #include "stage_cellcache.h"
 #include "stage_propagate.h"
 #include "stage_common.h"
@@ -3587,3 +3592,4 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 #include "stage_radfield.h"
 #include "stage_ionbal.h"
 #include "stage_decay.h"
+#include "stage_deposition.h"

@@ -71,6 +71,9 @@ struct DecayState {
   double t_model = 0., t_mid = 0.;
   bool valid = false, have_nuclides = false;
   double kernel_ms[3] = {};
+  uint64_t serial = 0;  // counts the updates (stage_deposition.h: which one a deposition update was made on)
+  std::vector<int32_t> h_path_top, h_path_end;  // [npaths] every path's first and last nuclide, and the mean lives: what
+  std::vector<double> h_meanlife;               // artis_amd_deposition_setup builds its rows from
 };
 
 void decay_free(DecayState *st) { delete st; }
@@ -92,6 +95,8 @@ int artis_amd_decay_setup(artis_amd_engine *e, const artis_decay_model *d) {
   const artis_decay::Rows r = artis_decay::build_rows(*d, anumber.data(), ne);
   decay_free(e->decay);  // a second set-up replaces the first
   e->decay = nullptr;
+  dep_free(e->dep);  // ... and the deposition set-up that was made on it goes with it
+  e->dep = nullptr;
   DecayState *st = new DecayState();
   st->ncell = n;
   const int64_t nn = d->nnuclides, np = d->npaths, nflat = (int64_t)r.path_lambda.size(), nrow = (int64_t)r.row_coef.size();
@@ -155,6 +160,11 @@ int artis_amd_decay_setup(artis_amd_engine *e, const artis_decay_model *d) {
   T.elem_nuc = st->d_elem_nuc;
   T.elem_initstablemeannucmass = st->d_initstable;
   st->t_model = d->t_model;
+  st->h_meanlife.assign(d->nuc_meanlife, d->nuc_meanlife + nn);
+  for (int64_t p = 0; p < np; p++) {
+    st->h_path_top.push_back(d->path_nucindex[d->path_start[p]]);
+    st->h_path_end.push_back(d->path_nucindex[d->path_start[p + 1] - 1]);
+  }
   return ARTIS_OK;
 }
 
@@ -230,6 +240,7 @@ int artis_amd_decay_update(artis_amd_engine *e, double t_mid, const artis_decay_
   for (int k = 0; k < 3; k++) HIP_TRY(st->block.elapsed_ms(k, &st->kernel_ms[k]));
   st->t_mid = t_mid;
   st->have_nuclides = want_nuclides != 0;
+  st->serial++;
   st->valid = true;
   return ARTIS_OK;
 }

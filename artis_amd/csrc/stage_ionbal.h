@@ -132,9 +132,11 @@ int ib_init(artis_amd_engine *e) {
   return ARTIS_OK;
 }
 
-// where the new timestep's matter comes from when not from the host: device arrays (artis_amd_grid_update_decayed, stage_decay.h)
+// where the new timestep's matter comes from when not from the host: device arrays (artis_amd_grid_update_decayed, stage_decay.h), and
+// with them the next step's thickness flags (artis_amd_grid_update_deposited, stage_deposition.h; null: the host's u->thick)
 struct IbMatter {
   const float *rho, *massfrac, *meanweight;
+  const int32_t *thick = nullptr;
 };
 
 // artis_amd_grid_update (matter == nullptr: u's host arrays) and artis_amd_grid_update_decayed (matter: copied device to device into the same scratch)
@@ -150,7 +152,7 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
     return stage_error(ARTIS_ERR_ARG, "grid_update: use_fit = 1 needs an artis_amd_radfield_fit since the last propagation call");
   if (!u->use_fit && (!u->TJ || !u->TR || !u->W || !u->Te)) return stage_error(ARTIS_ERR_ARG, "grid_update: use_fit = 0 needs TJ, TR, W and Te");
   if (!matter && (!u->rho || !u->elem_massfracs || !u->thick)) return stage_error(ARTIS_ERR_ARG, "grid_update: rho, elem_massfracs and thick are required");
-  if (matter && !u->thick) return stage_error(ARTIS_ERR_ARG, "grid_update: thick is required");
+  if (matter && !matter->thick && !u->thick) return stage_error(ARTIS_ERR_ARG, "grid_update: thick is required");
   if (!matter && ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !u->elem_meanweight)
     return stage_error(ARTIS_ERR_ARG, "grid_update: this build has USE_CALCULATED_MEANATOMICWEIGHT: elem_meanweight is required");
   if (!ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !e->M.elem_meannucmass)
@@ -165,7 +167,10 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
   const hipMemcpyKind from_matter = matter ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(stage_copy(st->d_rho, matter ? matter->rho : u->rho, n, from_matter, &s));
   HIP_TRY(stage_copy(st->d_massfrac, matter ? matter->massfrac : u->elem_massfracs, n * ne, from_matter, &s));
-  HIP_TRY(stage_copy(st->d_thick, u->thick, n, hipMemcpyHostToDevice, &s));
+  if (matter && matter->thick)
+    HIP_TRY(stage_copy(st->d_thick, matter->thick, n, hipMemcpyDeviceToDevice, &s));
+  else
+    HIP_TRY(stage_copy(st->d_thick, u->thick, n, hipMemcpyHostToDevice, &s));
   if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT)
     HIP_TRY(stage_copy(st->d_meanweight, matter ? matter->meanweight : u->elem_meanweight, n * ne, from_matter, &s));
   HIP_TRY(stage_copy(st->d_kappagrey, u->kappagrey, n, hipMemcpyHostToDevice, &s));

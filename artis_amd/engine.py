@@ -72,6 +72,11 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_decay_update.argtypes = [C.c_void_p, C.c_double, C.POINTER(abi.DecayCoeffs), C.c_int, C.c_void_p]
     L.artis_amd_decay_download.argtypes = [C.c_void_p, C.POINTER(abi.DecayResult)]
     L.artis_amd_grid_update_decayed.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
+    L.artis_amd_deposition_setup.argtypes = [C.c_void_p, C.POINTER(abi.DepositionModel)]
+    L.artis_amd_deposition_update.argtypes = [C.c_void_p, C.POINTER(abi.DepositionParams), C.c_void_p]
+    L.artis_amd_deposition_download.argtypes = [C.c_void_p, C.POINTER(abi.DepositionResult)]
+    L.artis_amd_deposition_devptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.artis_amd_grid_update_deposited.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -99,6 +104,8 @@ EXPORTED_SYMBOLS = [
     "artis_amd_radfield_fit", "artis_amd_radfield_download",
     "artis_amd_grid_update", "artis_amd_grid_update_download",
     "artis_amd_decay_setup", "artis_amd_decay_update", "artis_amd_decay_download", "artis_amd_grid_update_decayed",
+    "artis_amd_deposition_setup", "artis_amd_deposition_update", "artis_amd_deposition_download", "artis_amd_deposition_devptr",
+    "artis_amd_grid_update_deposited",
     "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
     "artis_amd_sizeof_plan", "artis_amd_engine_plan",
 ]
@@ -353,6 +360,57 @@ class Engine:
         rho, mf, mw = _matter if _matter is not None else (None, None, None)
         u, keep = abi.grid_update_config(use_fit, rho, mf, thick, mw, TJ, TR, W, Te, kappagrey, clumpfactor, ffegrp)
         self._check(self.L.artis_amd_grid_update_decayed(self.h, C.byref(u), C.cast(ts_next.ref(), C.c_void_p), C.c_void_p(stream)))
+        self._ts = ts_next
+        del keep
+        return self.grid_update_download()
+
+    # deposition rates and thickness of the grid update (include/artis_amd.h artis_amd_deposition_*)
+    def deposition_setup(self, deposition_model: dict):
+        """Validate and upload the nuclides' decay energies and branch probabilities with the cells' volumes and radial positions: a dict
+        over artis_deposition_model's array fields (synth.decay_energies, synth.assocvolume_tmin, synth.radial_pos_tmin). Needs
+        decay_setup; a second call replaces the first."""
+        m, keep = abi.deposition_model(deposition_model)
+        self._check(self.L.artis_amd_deposition_setup(self.h, C.byref(m)))
+        del keep
+
+    def deposition_update(self, mid: float, width: float, nts: int, nts_next: int, num_grey_timesteps: int, optical_depth_is_thick: float,
+                          optical_depth_is_thick_vpkt: float = 0.0, nprocs: int = 1, power_vectors=None, stream: int = 0) -> dict:
+        """Emission powers, deposition rates, grey depth and thickness flag of every cell and the timestep totals on the device, from the
+        last decay_update and the estimators of the step (mid, width, nts) just propagated; power_vectors: [11, nnuclides] from the host
+        (used as they are), or None (the device forms them). Returns the download."""
+        p, keep = abi.deposition_params(mid, width, nts, nts_next, num_grey_timesteps, optical_depth_is_thick, optical_depth_is_thick_vpkt,
+                                        nprocs, power_vectors)
+        self._check(self.L.artis_amd_deposition_update(self.h, C.byref(p), C.c_void_p(stream)))
+        del keep
+        return self.deposition_download()
+
+    def deposition_download(self, arrays: bool = True) -> dict:
+        """numpy arrays under the field names of artis_deposition_result (eps_ana, dep [5, ncell]; power_vectors [11, nnuclides]), "totals"
+        as a dict over abi.DEP_TOTALS, "mtot", "nradioactive", "nts_next", "t_mid" and "kernel_ms" (powers, cells, totals);
+        arrays=False: only the reported fields"""
+        info = abi.DepositionResult(struct_size=C.sizeof(abi.DepositionResult))
+        self._check(self.L.artis_amd_deposition_download(self.h, C.byref(info)))  # sizes first
+        n, nn = info.npts_nonempty, info.nnuclides
+        out = abi.deposition_arrays(n, nn) if arrays else {}
+        types = dict(abi.DepositionResult._fields_)
+        for k, v in out.items():
+            if v.size:
+                setattr(info, k, v.ctypes.data_as(types[k]))
+        if arrays:
+            self._check(self.L.artis_amd_deposition_download(self.h, C.byref(info)))
+            out["eps_ana"] = out["eps_ana"].reshape(abi.DEP_NCHANNELS, n)
+            out["dep"] = out["dep"].reshape(abi.DEP_NCHANNELS, n)
+            out["power_vectors"] = out["power_vectors"].reshape(abi.DEP_NVECTORS, nn)
+        out.update(totals={k: float(info.totals[i]) for i, k in enumerate(abi.DEP_TOTALS)}, mtot=float(info.mtot), nradioactive=int(info.nradioactive),
+                   nts_next=int(info.nts_next), t_mid=float(info.t_mid), kernel_ms=tuple(float(x) for x in info.kernel_ms))
+        return out
+
+    def grid_update_deposited(self, ts_next: abi.Timestep, use_fit: bool = True, TJ=None, TR=None, W=None, Te=None, kappagrey=None,
+                              clumpfactor=None, ffegrp=None, stream: int = 0, _thick=None) -> dict:
+        """grid_update_decayed with the thickness flags of the last deposition_update too: no array of the new timestep comes from the
+        host. (_thick: flags handed over all the same, which the library refuses: for the tests.)"""
+        u, keep = abi.grid_update_config(use_fit, None, None, _thick, None, TJ, TR, W, Te, kappagrey, clumpfactor, ffegrp)
+        self._check(self.L.artis_amd_grid_update_deposited(self.h, C.byref(u), C.cast(ts_next.ref(), C.c_void_p), C.c_void_p(stream)))
         self._ts = ts_next
         del keep
         return self.grid_update_download()

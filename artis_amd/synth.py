@@ -1004,12 +1004,15 @@ def _chain_network(nchains: int, length: int, seed: int, zends=(26, 27, 28)):
 def decay_network(kind: str = "small", seed: int = 11) -> dict:
     """Nuclides and ALL decay paths of a network: every sub-path from every radioactive top, found depth first by decay type in the
     order of decay.h:30 and sorted as decay.cc:401-420 sorts them (by (A, Z) along the path without its last nuclide, the shorter
-    first; stable). kind: "small" (31 nuclides + He4), "small_nohe4", "large" (200 chains of 15: 3000 nuclides, 21000 paths).
+    first; stable). kind: "small" (31 nuclides + He4), "small_nohe4", "medium" (20 chains of 15: 300 nuclides, 2100 paths), "large" (200
+    chains of 15: 3000 nuclides, 21000 paths).
     Keys: the network fields of artis_decay_model."""
     import functools
 
     if kind in ("small", "small_nohe4"):
         nucs = _small_network(kind == "small")
+    elif kind == "medium":
+        nucs = _chain_network(20, 15, seed)
     elif kind == "large":
         nucs = _chain_network(200, 15, seed)
     else:
@@ -1080,4 +1083,59 @@ def decay_model(model: abi.Model, cs: abi.CellState, aux: dict, network: dict, t
     out.update(t_model=float(t_model), initnucmassfrac=X.astype(np.float32), elem_untrackedstable_initmassfrac=untracked.astype(np.float32),
                elem_initstablemeannucmass=(np.array([_AMASS.get(z, 2.0 * z) for z in Z]) * MH).astype(np.float32),
                rho_tmin=np.asarray(model["rho_tmin"], np.float32))
+    return out
+
+
+def decay_energies(network: dict, seed: int = 31) -> dict:
+    """The energy fields of artis_deposition_model for a network of decay_network(): nuc_endecay_gamma [nnuclides] and
+    nuc_endecay_particle, nuc_endecay_q, nuc_branchprob [nnuclides, 6] in DECAYTYPE order [erg]. A nuclide's decay types and branch
+    probabilities are those of its two-nuclide paths. Synthetic energies of MeV order: a gamma spectrum for most radioactive nuclides
+    (every fourth one has none), kinetic energy for beta+, beta- and alpha decays, none for electron captures and stable nuclides;
+    the Q value of a decay type covers its particle and gamma energy and a neutrino's share."""
+    rng = np.random.default_rng(seed)
+    MEV = 1.602176634e-6
+    nn = len(network["nuc_z"])
+    start, idx = np.asarray(network["path_start"]), np.asarray(network["path_nucindex"])
+    branch = np.zeros((nn, 6))
+    for p in np.nonzero(np.diff(start) == 2)[0]:
+        branch[idx[start[p]], int(network["path_last_decaytype"][p])] += float(network["path_branchproduct"][p])
+    radioactive = np.asarray(network["nuc_meanlife"]) > 0
+    gamma = np.where(radioactive, rng.uniform(0.05, 3.0, nn) * MEV, 0.0)
+    gamma[np.nonzero(radioactive)[0][3::4]] = 0.0
+    particle = rng.uniform(0.1, 6.0, (nn, 6)) * MEV
+    particle[:, [abi.DECAYTYPE_ELECTRONCAPTURE, abi.DECAYTYPE_NONE]] = 0.0
+    particle[:, abi.DECAYTYPE_SPONTFISSION] *= 30.0
+    particle = np.where(branch > 0, particle, 0.0)
+    q = np.where(branch > 0, particle + gamma[:, None] + rng.uniform(0.0, 1.0, (nn, 6)) * MEV, 0.0)
+    return dict(nuc_endecay_gamma=gamma, nuc_endecay_particle=particle, nuc_endecay_q=q, nuc_branchprob=np.minimum(branch, 1.0))
+
+
+def radial_pos_tmin(model: abi.Model) -> np.ndarray:
+    """grid::get_modelcell_mean_radial_pos_tmin (grid.cc:1675) of every non-empty cell of a grid made here: get_cellradialposmid
+    (grid.cc:390) of the one propagation cell that maps to it, kept as a float as the reference keeps its sum. 3D Cartesian: the
+    distance of the cell's middle from the origin; 2D cylindrical: of the middle in r_cyl and z; 1D spherical: the shell's
+    volume-averaged radius 3/4 (r_out^4 - r_in^4) / (r_out^3 - r_in^3)."""
+    gt, rmax = int(model["gridtype"]), float(model["rmax"])
+    nc = [int(x) for x in model["ncoordgrid"]]
+    mins = [np.asarray(a, dtype=np.float64) for a in model["coord_pos_min_tmin"]]
+    outer = [np.concatenate([m[1:], [rmax]]) if len(m) else m for m in mins]
+    mids = [0.5 * (lo + hi) for lo, hi in zip(mins, outer)]
+    if gt == abi.GRID_CARTESIAN3D:
+        iz, iy, ix = np.meshgrid(np.arange(nc[2]), np.arange(nc[1]), np.arange(nc[0]), indexing="ij")  # cellindex = ix + n iy + n n iz
+        r = np.sqrt(mids[0][ix.ravel()] ** 2 + mids[1][iy.ravel()] ** 2 + mids[2][iz.ravel()] ** 2)
+    elif gt == abi.GRID_CYLINDRICAL2D:
+        iz, ir = np.meshgrid(np.arange(nc[1]), np.arange(nc[0]), indexing="ij")  # cellindex = ir + nr iz
+        r = np.sqrt(mids[0][ir.ravel()] ** 2 + mids[1][iz.ravel()] ** 2)
+    else:
+        r = 0.75 * (outer[0] ** 4 - mins[0] ** 4) / (outer[0] ** 3 - mins[0] ** 3)
+    prop = np.asarray(model["propcell_nonemptymgi"])
+    out = np.zeros(int(model["npts_nonempty"]))
+    out[prop[prop >= 0]] = r[prop >= 0]
+    return out.astype(np.float32).astype(np.float64)
+
+
+def deposition_model(model: abi.Model, network: dict, seed: int = 31) -> dict:
+    """A dict over artis_deposition_model's array fields for a grid made by build() and a network of decay_network()"""
+    out = decay_energies(network, seed)
+    out.update(assocvolume_tmin=assocvolume_tmin(model), radial_pos_tmin=radial_pos_tmin(model))
     return out

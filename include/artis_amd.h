@@ -479,7 +479,9 @@ typedef struct artis_amd_engine artis_amd_engine;
 #define ARTIS_ERR_RCCL (-6)
 
 const char *artis_amd_last_error(void);
-/* 6 -- and it stays 6 with the decay and abundance update (artis_decay_model, artis_decay_coeffs, artis_decay_result and the four functions
+/* 6 -- and it stays 6 with the deposition rates and thickness flags (artis_deposition_model, artis_deposition_params, artis_deposition_result and
+ * the five functions artis_amd_deposition_setup / _update / _download / _devptr and artis_amd_grid_update_deposited): additive again.
+ * It stayed 6 with the decay and abundance update (artis_decay_model, artis_decay_coeffs, artis_decay_result and the four functions
  * artis_amd_decay_setup / _update / _download and artis_amd_grid_update_decayed): new functions and new structs only, no existing one changed.
  * It stayed 6 with the engine configuration (artis_amd_config, artis_amd_plan and their four functions below): functions were added,
  * no existing struct or function changed, so a caller built against the earlier header of version 6 runs unchanged.
@@ -947,6 +949,71 @@ int artis_amd_decay_download(artis_amd_engine *eng, artis_decay_result *out);
 /* artis_amd_grid_update with the matter of the last artis_amd_decay_update: u->rho, u->elem_massfracs and u->elem_meanweight must be NULL;
  * ARTIS_ERR_ARG unless a decay update is valid and its t_mid == ts_next->mid. */
 int artis_amd_grid_update_decayed(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream);
+
+/* ---- deposition rates and thickness --------------------------------------------------------
+ * What the reference's grid update computes from the decay coefficients and the deposition estimators, on the device: the analytic
+ * emission power of every source nuclide in five channels and the six qdot vectors (decay.cc:1105-1168), per cell the analytic emission
+ * rates, the normalised deposition estimators and the non-thermal leptons' deposition rate density (nonthermal.cc:2340, sn3d.cc:532-563),
+ * the grey depth and the thickness flag of the next step's packets (update_grid.cc:606-627), and the timestep totals of deposition.out
+ * (sn3d.cc:240-286). Every sum is the sequential sum of the reference, in its order: the result is bitwise reproducible. Works in every
+ * build. The vectors' order everywhere: gamma, positron, electron, alpha, spfission, then qdot of ARTIS_DECAYTYPE_* 0..5. */
+#define ARTIS_DEP_NCHANNELS 5
+#define ARTIS_DEP_NVECTORS 11
+#define ARTIS_DEP_NTOTALS 15
+typedef struct artis_deposition_model {
+  int64_t struct_size;                /* sizeof(artis_deposition_model) */
+  int32_t nnuclides, npts_nonempty;   /* the decay set-up's (checked) */
+  const double *nuc_endecay_gamma;    /* [nnuclides] erg per decay (decay.cc nucdecayenergygamma) */
+  const double *nuc_endecay_particle; /* [nnuclides][6] in ARTIS_DECAYTYPE_* order (nucdecayenergyparticle) */
+  const double *nuc_endecay_q;        /* [nnuclides][6] (nucdecayenergyqval) */
+  const double *nuc_branchprob;       /* [nnuclides][6] (get_nuc_decaybranchprob) */
+  const double *assocvolume_tmin;     /* [npts_nonempty] grid::get_modelcell_assocvolume_tmin */
+  const double *radial_pos_tmin;      /* [npts_nonempty] grid::get_modelcell_mean_radial_pos_tmin (grid.cc:1675) */
+} artis_deposition_model;
+typedef struct artis_deposition_params {
+  int64_t struct_size;     /* sizeof(artis_deposition_params) */
+  double mid, width;       /* of the step just propagated: what its estimators are normalised with */
+  int32_t nts, nprocs;     /* ... its number; globals::nprocs */
+  int32_t nts_next;        /* the step the flags are for: THICK needs nts_next < num_grey_timesteps */
+  int32_t num_grey_timesteps;
+  double optical_depth_is_thick;
+  double optical_depth_is_thick_vpkt; /* read in builds with VPKT_ON */
+  const double *power_vectors;        /* NULL: the device forms them; else [ARTIS_DEP_NVECTORS][nnuclides], used as they are */
+} artis_deposition_params;
+typedef struct artis_deposition_result {
+  int64_t struct_size; /* sizeof(artis_deposition_result) */
+  /* host arrays to fill; NULL: skip */
+  double *eps_ana;                           /* [5][npts_nonempty] erg/s/cm^3: eps_{gamma, positron, electron, alpha, spfission}_ana */
+  double *dep;                               /* [5][npts_nonempty] dep_* in the same order */
+  double *ntlepton_deposition_rate_density;  /* [npts_nonempty] */
+  float *grey_depth;                         /* [npts_nonempty] */
+  int32_t *thick;                            /* [npts_nonempty] ARTIS_CELL_* for the next step's packets */
+  double *power_vectors;                     /* [ARTIS_DEP_NVECTORS][nnuclides] erg/s per gram of the source nuclide */
+  double *totmassnuclide;                    /* [nnuclides] g */
+  /* reported */
+  double totals[ARTIS_DEP_NTOTALS]; /* gamma_dep, positron_dep, electron_dep, alpha_dep [erg]; then the vectors' products with totmassnuclide
+                                       [erg/s]: eps_{gamma, positron, electron, alpha, spfission}_ana_power, qdot of the six decay types */
+  double mtot;
+  int32_t npts_nonempty, nnuclides, nradioactive, nts_next;
+  double t_mid;
+  double kernel_ms[3]; /* HIP-event time: [0] k_dep_powers (and the packing), [1] k_dep_cells, [2] k_dep_totals */
+} artis_deposition_result;
+/* Needs artis_amd_decay_setup (a new one invalidates this set-up). Validates (ARTIS_ERR_ARG with a text naming the nuclide: a negative or
+ * non-finite energy, a branch probability outside [0, 1]; a non-positive assocvolume_tmin, a negative or non-finite radial_pos_tmin, sizes
+ * that are not the decay set-up's), builds the rows of the paths by top nuclide and the list of radioactive nuclides, forms
+ * totmassnuclide and mtot. A second call replaces the first. */
+int artis_amd_deposition_setup(artis_amd_engine *eng, const artis_deposition_model *model);
+/* The update on hip_stream (synchronous), from the last artis_amd_decay_update (its t_mid, rho and coefficients), the estimator block as it
+ * stands (as after artis_amd_allreduce_estimators) and the cell state's kappagrey. ARTIS_ERR_ARG without either set-up or a valid decay update. */
+int artis_amd_deposition_update(artis_amd_engine *eng, const artis_deposition_params *params, void *hip_stream);
+/* Copy the results of the last update to the host (sizes in the reported fields even when every pointer is NULL). */
+int artis_amd_deposition_download(artis_amd_engine *eng, artis_deposition_result *out);
+/* The result block on the device, for the stages that read it: eps_ana [5][n], dep [5][n], ntlepton [n] (doubles, contiguous from *eps_ana),
+ * grey_depth (float [n]) and thick (int32 [n]). Any pointer may be NULL. */
+int artis_amd_deposition_devptr(artis_amd_engine *eng, const double **eps_ana, const float **grey_depth, const int32_t **thick, int64_t *npts_nonempty);
+/* artis_amd_grid_update_decayed with the flags of the last artis_amd_deposition_update, device to device: u->thick must be NULL too.
+ * ARTIS_ERR_ARG unless a deposition update is valid, was made for nts_next == ts_next->nts and on the decay update of ts_next->mid. */
+int artis_amd_grid_update_deposited(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream);
 
 #ifdef __cplusplus
 }
