@@ -1281,7 +1281,7 @@ inline size_t tq_lds_bytes(int tb, int nlevels, int nalltrans) {
 //   geometry   one workgroup of LATE_TB = 512 threads per compute unit (2 waves per SIMD, no spilled register; 768 threads: 3 waves, 34 spilled, measured);
 //   ownership  workgroup b owns a fixed contiguous share of the (sorted) r-packet list and of the thermal list; a packet never changes workgroup, and
 //              nothing waits on another workgroup;
-//   queues     per workgroup one ring per role (r-packet, thermal) in its slice of a scratch array, capacity = the workgroup's share (a packet sits in
+//   queues     per workgroup one ring per role (r-packet, thermal, slow path) in its slice of a scratch array, capacity = the workgroup's share (a packet sits in
 //              at most one queue); head, reserved and published tail in LDS. A producer stores the packet (the bodies' pkt_store / chi_store /
 //              pkt_store_thermal), writes the entries it reserved, and publishes them in reservation order with a workgroup-scope release; a consumer
 //              reads the published tail with a workgroup-scope acquire, reads the entries, and takes them with a compare-and-swap on the head (entries
@@ -1291,7 +1291,11 @@ inline size_t tq_lds_bytes(int tb, int nlevels, int nalltrans) {
 //              from the role's queue; a lane keeps its packet until its kind changes or it ends -- no budget. The waves start split between the roles
 //              in proportion to the workgroup's two shares (at least one wave each where both are non-empty); a wave whose lanes are all idle and whose
 //              queue is empty takes the other role if that queue is not empty;
-//   ejection   a packet whose next kind is the slow path, a blackbody step, a gamma-ray kind, or that is done, is stored and appended to the ordinary
+//   slow path  the third role: the rare bound-free actions (k_slow's body: the wave selects the free-bound frequencies of its lanes' emissions, then
+//              advance_slow()), one pull - action - store - put per pass, nothing held between passes. The last wave of a workgroup serves only this
+//              queue (ARTIS_LATE_SLOW_WAVE; it polls with s_sleep while the workgroup has packets), and every other wave whose lanes are all idle looks
+//              at the slow queue first: a packet with a pending action waits for a poll, not for the launch to end and two more to begin;
+//   ejection   a packet whose next kind is a blackbody step, a gamma-ray kind, or that is done, is stored and appended to the ordinary
 //              lists (append_by_kind) exactly as a split kernel would; the host's loop runs those kinds and what comes back is listed again;
 //   the end    `live` (LDS) counts the workgroup's packets that have not been ejected; a wave leaves when it is 0;
 //   estimators plain f64 global atomics (the lists are short here): no per-wave caches, no few-cells LDS arrays;
@@ -1306,18 +1310,31 @@ inline size_t tq_lds_bytes(int tb, int nlevels, int nalltrans) {
 #ifndef ARTIS_LATE_TB
 #define ARTIS_LATE_TB 512  // 2 waves per SIMD at up to 256 VGPRs: no spilled register (768: 3 waves at 168 VGPRs, 34 spilled; profiles/r08/late_kernel.md)
 #endif
+#ifndef ARTIS_LATE_SLOW_INLINE
+// the slow role's body inside k_late's loop, or called from it. Classic options: 255 VGPRs and no spilled register inlined, 26 spilled around the call.
+// The builds with interpolated cross-sections, whose slow path alone takes 256 VGPRs + 22 AGPRs (k_slow): 398 spilled inlined, 95 called
+// (profiles/r10/late_slow_role.md)
+#define ARTIS_LATE_SLOW_INLINE ARTIS_OPT_PHIXS_CLASSIC_NO_INTERPOLATION
+#endif
+#ifndef ARTIS_LATE_SLOW_WAVE
+#define ARTIS_LATE_SLOW_WAVE 1  // the last wave of each workgroup serves the slow-path queue only; 0: idle waves alone do (profiles/r10/late_slow_role.md)
+#endif
 constexpr int LATE_TB = ARTIS_LATE_TB;
 constexpr size_t LATE_LDS_HEAD = (sizeof(stat_t) * ARTIS_NSTATS) + 64;  // statistics, then the queues' counters
 inline size_t late_lds_bytes(int nlevels, int nalltrans, int nbfcontinua) {
   return LATE_LDS_HEAD + (sizeof(LevelPack) * (size_t)nlevels) + (((sizeof(uint32_t) * (size_t)((nalltrans + 1) / 2)) + 15) & ~(size_t)15) +
          (sizeof(ContPack) * (size_t)nbfcontinua);
 }
+constexpr int LATE_NQ = 3;  // roles and their queues: 0 = r-packets, 1 = thermal packets, 2 = the slow path
 struct LateArgs {
-  const int32_t *list[2];  // the r-packet and the thermal list, consumed whole
-  int32_t n[2];
-  int32_t *ring[2];        // scratch: [n[0] + n[1]] each; workgroup b's slice begins at the sum of its two shares' beginnings
+  const int32_t *list[LATE_NQ];  // the r-packet, the thermal and the slow-path list, consumed whole
+  int32_t n[LATE_NQ];
+  int32_t *ring[LATE_NQ];        // scratch: [n[0] + n[1] + n[2]] each; workgroup b's slice begins at the sum of its three shares' beginnings
   int32_t *bailouts;
   int32_t poll_cap;
+#ifdef ARTIS_PROFILE_LATE
+  int32_t *stamp;  // [packets] when a packet entered the slow queue (clocks / 16, low word)
+#endif
 };
 #if ARTIS_LATE_KERNEL
 struct LateRing {
@@ -1378,33 +1395,91 @@ __device__ inline int32_t late_pull(const LateRing &Q, bool need) {
   return ok ? v : -1;
 }
 // k_late's policy for the loop bodies it shares with the split kernels (rpkt_round.inc, thermal_round.inc): no budget; a packet that stays an
-// r-packet or a thermal packet goes to the workgroup's queue of that role, every other packet leaves the kernel
+// r-packet or a thermal packet, or has a slow-path action pending, goes to the workgroup's queue of that role, every other packet leaves the kernel
 struct LateSink {
-  LateRing q[2];
+  LateRing q[LATE_NQ];
   int32_t *live;
   int32_t *errflag;
+#ifdef ARTIS_PROFILE_LATE
+  int32_t *stamp;
+#endif
   // left: this lane gave up packet pi, whose next kind is `kind`. Wave-uniform control flow.
   __device__ void put(bool left, int kind, int32_t pi, const Pkt &p, const Lists &next) const {
     const bool to_r = left && kind == NEXT_RPKT;
     const bool to_t = left && (kind == NEXT_MA || kind == NEXT_KPKT);
+    const bool to_s = left && kind == NEXT_SLOW;
+#ifdef ARTIS_PROFILE_LATE
+    if (to_s) stamp[pi] = (int32_t)(clock64() >> 4);
+#endif
     late_push(q[0], to_r, pi, errflag);
     late_push(q[1], to_t, pi, errflag);
-    const bool out = left && !to_r && !to_t;
+    late_push(q[2], to_s, pi, errflag);
+    const bool out = left && !to_r && !to_t && !to_s;
     append_by_kind(out ? kind : NEXT_DONE, pi, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion));
     const unsigned long long om = __ballot(out);
     if (om != 0 && (int)(threadIdx.x & 63) == __ffsll((long long)om) - 1) atomicSub(live, __popcll(om));  // after the append: `live` 0 = all is on the lists
   }
 };
+// One pass of the slow-path role: k_slow's body for the packets the wave's lanes have just pulled (got >= 0), without the cold-record fill (no cold
+// levels where k_late runs). The wave selects the free-bound frequencies whatever their number, as in k_tail. Wave-uniform control flow.
+#if ARTIS_LATE_SLOW_INLINE
+__device__ inline
+#else
+__device__ __noinline__
+#endif
+void late_slow_round(const Env &env, const LateSink &sink, const Lists &next, int32_t got) {
+  const bool mine = got >= 0;
+  const int32_t pi = mine ? got : 0;
+  Pkt p;
+  p.cellindex = 0; p.nu_cmf = 0.; p.ma_element = 0; p.ma_ion = 0;
+  FbSel sel;
+  sel.mode = 1;
+  sel.valid = false;
+  sel.element = sel.lowerion = sel.lower = sel.t = 0;
+  sel.T_e = 0.f;
+  sel.zrand = sel.nu = 0.;
+  if (mine) pkt_load(env.P, pi, p);
+#ifdef ARTIS_PROFILE_LATE
+  // (-DARTIS_PROFILE_LATE) stats slots: 42 clocks / 16 the packets waited in the slow queue, 43 the packets, 44 / 45 those that waited longer than
+  // 2^12 / 2^16 units (31 us / 0.5 ms at 2.1 GHz), 46 passes of the role, 47 clocks / 16 of the passes (per wave)
+  const long long tpass0 = clock64();
+  if (mine) {
+    const uint32_t w = (uint32_t)((int32_t)(tpass0 >> 4) - sink.stamp[pi]);
+    atomicAdd(&env.stats[42], (stat_t)w);
+    atomicAdd(&env.stats[43], (stat_t)1);
+    if (w > (1u << 12)) atomicAdd(&env.stats[44], (stat_t)1);
+    if (w > (1u << 16)) atomicAdd(&env.stats[45], (stat_t)1);
+  }
+#endif
+  if (mine && slow_selects_continuum_nu(p)) {
+    Pkt t = p;
+    (void)advance_slow(env, t, pi, &sel);
+  }
+  fbsel_wave(env, sel);
+  int kind = NEXT_DONE;
+  if (mine) {
+    kind = advance_slow(env, p, pi, sel.valid ? &sel : nullptr);
+    pkt_store(env.P, pi, p);
+  }
+  sink.put(mine, kind, pi, p, next);
+#ifdef ARTIS_PROFILE_LATE
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&env.stats[46], (stat_t)1);
+    atomicAdd(&env.stats[47], (stat_t)((clock64() - tpass0) >> 4));
+  }
+#endif
+}
 __global__ void __launch_bounds__(LATE_TB, 1) k_late(Env env, LateArgs a, Lists next, unsigned long long *gstats) {
   extern __shared__ __attribute__((aligned(16))) unsigned char late_lds[];
-  // this workgroup's shares of the two lists (contiguous; neighbouring shares on one XCD: xcd_chunk) and its slice of the rings
+  // this workgroup's shares of the three lists (contiguous; neighbouring shares on one XCD: xcd_chunk) and its slice of the rings
   const int64_t nwg = gridDim.x, b = xcd_chunk(blockIdx.x, nwg);
   const int32_t r0 = (int32_t)(((int64_t)a.n[0] * b) / nwg), r1 = (int32_t)(((int64_t)a.n[0] * (b + 1)) / nwg);
   const int32_t t0 = (int32_t)(((int64_t)a.n[1] * b) / nwg), t1 = (int32_t)(((int64_t)a.n[1] * (b + 1)) / nwg);
-  const int32_t own = (r1 - r0) + (t1 - t0);
+  const int32_t s0 = (int32_t)(((int64_t)a.n[2] * b) / nwg), s1 = (int32_t)(((int64_t)a.n[2] * (b + 1)) / nwg);
+  const int32_t own = (r1 - r0) + (t1 - t0) + (s1 - s0);
   if (own == 0) return;  // (the whole workgroup)
   stat_t *lstats = (stat_t *)late_lds;
-  int32_t *ctr = (int32_t *)(late_lds + (sizeof(stat_t) * ARTIS_NSTATS));  // head r, t | reserved r, t | published r, t | live
+  int32_t *ctr = (int32_t *)(late_lds + (sizeof(stat_t) * ARTIS_NSTATS));  // head r, t | reserved r, t | published r, t | live | head, reserved, published s
   LevelPack *lds_levelpack = (LevelPack *)(late_lds + LATE_LDS_HEAD);
   uint16_t *lds_tlevel = (uint16_t *)(lds_levelpack + env.M.nlevels);
   ContPack *lds_cont = (ContPack *)((unsigned char *)lds_tlevel + (((sizeof(uint32_t) * (size_t)((env.M.nalltrans + 1) / 2)) + 15) & ~(size_t)15));
@@ -1420,15 +1495,28 @@ __global__ void __launch_bounds__(LATE_TB, 1) k_late(Env env, LateArgs a, Lists 
     D2 *dst = (D2 *)lds_cont;
     for (int i = threadIdx.x; i < env.M.nbfcontinua * 2; i += LATE_TB) dst[i] = src[i];
   }
-  LateSink sink{{{a.ring[0] + (r0 + t0), (uint32_t)own, ctr + 0, ctr + 2, ctr + 4}, {a.ring[1] + (r0 + t0), (uint32_t)own, ctr + 1, ctr + 3, ctr + 5}},
-                ctr + 6, env.errflag};
+  const int32_t slice = r0 + t0 + s0;
+  LateSink sink{{{a.ring[0] + slice, (uint32_t)own, ctr + 0, ctr + 2, ctr + 4}, {a.ring[1] + slice, (uint32_t)own, ctr + 1, ctr + 3, ctr + 5},
+                 {a.ring[2] + slice, (uint32_t)own, ctr + 7, ctr + 8, ctr + 9}},
+                ctr + 6, env.errflag
+#ifdef ARTIS_PROFILE_LATE
+                , a.stamp
+#endif
+  };
   // the queues begin with the workgroup's shares
   for (int i = threadIdx.x; i < r1 - r0; i += LATE_TB) sink.q[0].ring[i] = a.list[0][r0 + i];
   for (int i = threadIdx.x; i < t1 - t0; i += LATE_TB) sink.q[1].ring[i] = a.list[1][t0 + i];
+  for (int i = threadIdx.x; i < s1 - s0; i += LATE_TB) {
+    sink.q[2].ring[i] = a.list[2][s0 + i];
+#ifdef ARTIS_PROFILE_LATE
+    a.stamp[a.list[2][s0 + i]] = (int32_t)(clock64() >> 4);
+#endif
+  }
   if (threadIdx.x == 0) {
-    ctr[0] = ctr[1] = 0;
+    ctr[0] = ctr[1] = ctr[7] = 0;
     ctr[2] = ctr[4] = r1 - r0;
     ctr[3] = ctr[5] = t1 - t0;
+    ctr[8] = ctr[9] = s1 - s0;
     ctr[6] = own;
   }
   env.M.level_pack = lds_levelpack;
@@ -1444,10 +1532,18 @@ __global__ void __launch_bounds__(LATE_TB, 1) k_late(Env env, LateArgs a, Lists 
   env.stats = lstats;
   const double ts_end = env.S.ts_end;
   constexpr int NW = LATE_TB / 64;
-  // roles: 0 = r-packets, 1 = thermal packets
-  int nw_r = (int)((((int64_t)(r1 - r0) * NW) + (own / 2)) / own);
-  if (r1 > r0 && t1 > t0) nw_r = max(1, min(NW - 1, nw_r));
-  int role = __builtin_amdgcn_readfirstlane(((int)(threadIdx.x >> 6) < nw_r) ? 0 : 1);
+  constexpr int NW_RT = ARTIS_LATE_SLOW_WAVE ? NW - 1 : NW;  // the waves that begin in the r-packet and thermal roles
+  // roles: 0 = r-packets, 1 = thermal packets, 2 = the slow path (`home`: the role of the first two a wave came from)
+  const int32_t own_rt = (r1 - r0) + (t1 - t0);
+  int nw_r = own_rt > 0 ? (int)((((int64_t)(r1 - r0) * NW_RT) + (own_rt / 2)) / own_rt) : 0;
+  if (r1 > r0 && t1 > t0) nw_r = max(1, min(NW_RT - 1, nw_r));
+  const bool slow_wave = ARTIS_LATE_SLOW_WAVE && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == NW - 1;
+  int home = __builtin_amdgcn_readfirstlane(((int)(threadIdx.x >> 6) < nw_r) ? 0 : 1);
+  int role = slow_wave ? 2 : home;
+  const auto waiting = [&](int q) {  // entries published and not yet taken
+    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(sink.q[q].pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) -
+                                          __hip_atomic_load(sink.q[q].head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+  };
   bool have = false;
   int32_t pi = 0;
   int n_it = 0;  // (the bodies count the lane's steps / units; no budget reads them here)
@@ -1458,7 +1554,13 @@ __global__ void __launch_bounds__(LATE_TB, 1) k_late(Env env, LateArgs a, Lists 
   long long tprev = 0;
   while (true) {
     const int32_t got = late_pull(sink.q[role], !have);
-    if (got >= 0) {
+    if (role == 2) {  // (no lane of a wave in this role holds a packet between passes)
+      if (__any(got >= 0)) {
+        late_slow_round(env, sink, next, got);
+        polls = 0;
+        continue;
+      }
+    } else if (got >= 0) {
       pi = got;
       if (role == 0) {
         pkt_load(env.P, pi, p);
@@ -1470,14 +1572,18 @@ __global__ void __launch_bounds__(LATE_TB, 1) k_late(Env env, LateArgs a, Lists 
       have = true;
     }
     if (!__any(have)) {
-      const int mine = __hip_atomic_load(ctr + 4 + role, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) -
-                       __hip_atomic_load(ctr + role, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const int other = __hip_atomic_load(ctr + 5 - role, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) -
-                        __hip_atomic_load(ctr + 1 - role, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (__builtin_amdgcn_readfirstlane(mine) > 0) continue;  // (another wave was faster: ask again)
-      if (__builtin_amdgcn_readfirstlane(other) > 0) {
-        role = 1 - role;
+      // a wave whose lanes are all idle: the slow queue first (a packet there waits for nothing else), then its own role's, then the other's
+      if (waiting(2) > 0) {
+        role = 2;
         continue;
+      }
+      if (!slow_wave) {
+        role = home;
+        if (waiting(home) > 0) continue;  // (another wave was faster: ask again)
+        if (waiting(1 - home) > 0) {
+          role = home = 1 - home;
+          continue;
+        }
       }
       if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) break;
       if (++polls > a.poll_cap) {  // the other waves hold what is left and carry it to its end
@@ -1877,7 +1983,7 @@ void dep_free(DepState *st);
 struct LastCall {
   double propagate_ms = 0., kms[NEXT_NKINDS] = {}, kms_tail = 0., fill_ms = 0.;  // summed launch durations: all, per kind, the tail kernel's; tile fills'
   double kms_late = 0.;          // ... k_late's
-  int64_t late_launches = 0;
+  int64_t late_launches = 0, tail_launches = 0;
   int64_t late_bailouts = 0;     // waves of k_late that gave up waiting for work (ARTIS_AMD_TRACE prints them)
   int64_t klaunches[NEXT_NKINDS] = {}, kthreads[NEXT_NKINDS] = {}, nlaunches = 0;
   // tiled runs: sweeps over the tiles, tile fills (sparse ones, cells filled), packets listed per (sweep, tile), packets parked
@@ -2016,8 +2122,11 @@ struct artis_amd_engine {
   bool late_always = false;
   bool late_strict = false;           // ARTIS_AMD_LATE_STRICT=1: a wave of k_late that gave up waiting fails the call (tests)
   bool late_attr_set = false;         // k_late's dynamic-LDS attribute has been set on this engine's device
-  int32_t *d_late_ring[2] = {nullptr, nullptr};  // the workgroups' queues (allocated with the lists)
+  int32_t *d_late_ring[LATE_NQ] = {nullptr, nullptr, nullptr};  // the workgroups' queues (allocated with the lists)
   int32_t *d_late_bail = nullptr;     // the slot after the error flag
+#ifdef ARTIS_PROFILE_LATE
+  int32_t *d_late_stamp = nullptr;    // (k_late's profile: LateArgs::stamp; lives as long as the process)
+#endif
   bool park_tails = true;     // ARTIS_AMD_TILE_PARK=0: every visit of a tile runs its packets to their end (rounds 2-3)
   // artis_amd_config.tile_park_at: packets left of a larger visit at which it parks them (0 / <= tail_max: round 4's rule, at the tail kernel's
   // threshold). Measured on the headline at a quarter of its cache (4 tiles, adaptive windows; profiles/r06/tiling.md): 4096 / 32768 / 131072 /
@@ -2313,7 +2422,7 @@ int sort_list(artis_amd_engine *e, hipStream_t s, const int32_t *list, const int
 
 void free_packet_buffers(artis_amd_engine *e) {
   void **singles[] = {&e->d_pkt, &e->d_pkt_snapshot, (void **)&e->d_sorted, (void **)&e->d_perm, (void **)&e->d_gamma_ws,
-                      (void **)&e->d_late_ring[0], (void **)&e->d_late_ring[1],
+                      (void **)&e->d_late_ring[0], (void **)&e->d_late_ring[1], (void **)&e->d_late_ring[2],
                       (void **)&e->d_gamma_gi, (void **)&e->d_gamma_n, (void **)&e->d_bfev, (void **)&e->d_bfev_count,
                       (void **)&e->d_vpkt_queue, (void **)&e->d_vpkt_count};
   e->bfev_cap = 0;
@@ -2354,8 +2463,8 @@ int ensure_packet_buffers(artis_amd_engine *e, int64_t n) {
     }
   HIP_TRY(hipMalloc((void **)&e->d_sorted, listbytes));
   HIP_TRY(hipMalloc((void **)&e->d_perm, listbytes));
-  if (late_possible(e)) {  // (80 MB at 1e7 packets: only for an engine that can launch k_late)
-    for (int k = 0; k < 2; k++) HIP_TRY(hipMalloc((void **)&e->d_late_ring[k], listbytes));
+  if (late_possible(e)) {  // (120 MB at 1e7 packets: only for an engine that can launch k_late)
+    for (int k = 0; k < LATE_NQ; k++) HIP_TRY(hipMalloc((void **)&e->d_late_ring[k], listbytes));
   }
   if (const int rc = sort_scratch_alloc(e->sort_scratch, n)) return rc;
   e->ws_capacity = n > 0 ? n : 1;
@@ -3514,7 +3623,10 @@ int artis_amd_last_kernel_ms_by_kind(artis_amd_engine *e, double ms[8], int64_t 
   ms[5] = e->last.kms_tail;
   ms[6] = e->last.fill_ms;
   ms[7] = e->last.kms_late;
-  if (launches) launches[7] = e->last.late_launches;
+  if (launches) {
+    launches[5] = e->last.tail_launches;
+    launches[7] = e->last.late_launches;
+  }
   return ARTIS_OK;
 }
 

@@ -297,6 +297,7 @@ struct PropRun {
     HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
     e->last.nlaunches++;
     (tail ? e->last.kms_tail : e->last.kms[kind]) += ms;
+    if (tail) e->last.tail_launches++;
     if (!tail) {
       e->last.klaunches[kind]++;
       e->last.kthreads[kind] += n;
@@ -349,21 +350,26 @@ struct PropRun {
     return ARTIS_OK;
   }
   bool late_eligible() const { return late_possible(e) && e->d_late_ring[0] != nullptr; }  // (late_possible(): with the packet buffers)
-  // The r-packet and the thermal list go to k_late whole (sorted first, as for the split kernels: a workgroup's share is local in cell and
-  // frequency) and no packet comes back to them: what the kernel ejects goes to the CURRENT slow-path, blackbody and gamma-ray lists, which no
-  // wave reads during the launch (their entries so far stay where they are; the appends follow them).
+  // The r-packet, the thermal and the slow-path list go to k_late whole (the first two sorted, as for the split kernels: a workgroup's share is
+  // local in cell and frequency; the slow-path list as it stands, as for k_slow) and no packet comes back to them: what the kernel ejects goes
+  // to the CURRENT blackbody and gamma-ray lists, which no wave reads during the launch (their entries so far stay where they are; the appends
+  // follow them).
   int run_late() {
 #if ARTIS_LATE_KERNEL
     LateArgs a;
-    const int kinds[2] = {NEXT_RPKT, NEXT_MA};
+    const int kinds[LATE_NQ] = {NEXT_RPKT, NEXT_MA, NEXT_SLOW};
     const clk::time_point t_sort = clk::now();
-    for (int i = 0; i < 2; i++) {
+    for (int i = 0; i < LATE_NQ; i++) {
       // (the second sort's output must not be the first's: the kind's alternate list is free, this launch has no kind of its own)
       STEP(sort_current(kinds[i], &a.list[i], e->d_lists[kinds[i]][1 - cur[kinds[i]]]));
       a.n[i] = cnt[kinds[i]];
       a.ring[i] = e->d_late_ring[i];
     }
     wall_sort += since(t_sort);
+#ifdef ARTIS_PROFILE_LATE
+    if (e->d_late_stamp == nullptr) HIP_TRY(hipMalloc((void **)&e->d_late_stamp, sizeof(int32_t) * (size_t)std::max<int64_t>(e->npackets, 1)));
+    a.stamp = e->d_late_stamp;
+#endif
     a.bailouts = e->d_late_bail;
     a.poll_cap = 1 << 20;  // x s_sleep 64: seconds
     const size_t lds = late_lds_bytes(e->Mh.nlevels, e->Mh.nalltrans, e->Mh.nbfcontinua);
@@ -371,7 +377,7 @@ struct PropRun {
       HIP_TRY(hipFuncSetAttribute((const void *)k_late, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
       e->late_attr_set = true;
     }
-    for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(e->d_count + kinds[i], 0, sizeof(int32_t), s));
+    for (int i = 0; i < LATE_NQ; i++) HIP_TRY(hipMemsetAsync(e->d_count + kinds[i], 0, sizeof(int32_t), s));
     HIP_TRY(hipMemsetAsync(e->d_late_bail, 0, sizeof(int32_t), s));
     HIP_TRY(hipEventRecord(e->ev0, s));
     e->last.thermal_variants |= ARTIS_AMD_THERMAL_LATE;
@@ -386,8 +392,8 @@ struct PropRun {
     e->last.late_launches++;
     e->last.late_bailouts += bail;
     if (e->trace)
-      fprintf(stderr, "[artis_amd] launch %lld late n=%d+%d %.3f ms -> slow %d gamma %d bb %d; %d waves gave up waiting\n", (long long)e->last.nlaunches, a.n[0],
-              a.n[1], ms, cnt[NEXT_SLOW], cnt[NEXT_GAMMA], cnt[NEXT_BB], bail);
+      fprintf(stderr, "[artis_amd] launch %lld late n=%d+%d+%d %.3f ms -> slow %d gamma %d bb %d; %d waves gave up waiting\n", (long long)e->last.nlaunches,
+              a.n[0], a.n[1], a.n[2], ms, cnt[NEXT_SLOW], cnt[NEXT_GAMMA], cnt[NEXT_BB], bail);
     if (bail != 0 && e->late_strict) {
       g_last_error = "k_late: " + std::to_string(bail) + " waves gave up waiting for work (ARTIS_AMD_LATE_STRICT=1)";
       return ARTIS_ERR_NOTCONVERGED;
@@ -461,23 +467,24 @@ struct PropRun {
     // (tiled runs: the later sweeps bring a tile a few stragglers at a time; each such visit is a tail from its first launch)
     const bool tail_ok = e->tail_max > 0 && (e->tail_always || listed > e->tail_max || sweep > 0 || (adaptive && e->last_visits > e->cc.ntiles));
     // k_late takes the r-packets and thermal packets of a population that began larger than late_max once that few are left (same rule; a small
-    // population stays on the split kernels unless ARTIS_AMD_LATE_ALWAYS=1); the kinds it ejects run on their own kernels between its launches
+    // population stays on the split kernels unless ARTIS_AMD_LATE_ALWAYS=1), slow-path actions included; the kinds it ejects (blackbody, gamma-ray)
+    // run on their own kernels between its launches. An engine that takes k_late has no use for k_tail: k_late ends the population.
     const bool late_ok = late_eligible() && (e->late_always || listed > e->late_max);
     while (count_listed() > 0) {
+      // (r-packet + thermal + k-packet lists; and the blackbody list must not be longer than that either: a step's first round has most packets
+      // there, about to become r-packets, beside a short thermal list)
+      if (late_ok && cnt[NEXT_KPKT] == 0 && (int64_t)cnt[NEXT_RPKT] + cnt[NEXT_MA] <= e->late_max && cnt[NEXT_BB] <= e->late_max) {
+        if (cnt[NEXT_RPKT] + cnt[NEXT_MA] + cnt[NEXT_SLOW] > 0) STEP(run_late());
+        for (int kind : order)
+          if (kind == NEXT_GAMMA || kind == NEXT_BB)
+            if (cnt[kind] > 0) STEP(run_kind(kind));
+        continue;
+      }
       const int64_t tail_n = count_tail();
       const bool tail_now = tail_ok && tail_n > 0 && tail_n <= e->tail_max && cnt[NEXT_KPKT] == 0;
       if (should_park(sweep, tile, tail_n, tail_now)) break;
       if (tail_now) {
         STEP(run_tail(tail_n));
-        continue;
-      }
-      // (r-packet + thermal + k-packet lists; and the blackbody list must not be longer than that either: a step's first round has most packets
-      // there, about to become r-packets, beside a short thermal list)
-      if (late_ok && cnt[NEXT_KPKT] == 0 && (int64_t)cnt[NEXT_RPKT] + cnt[NEXT_MA] <= e->late_max && cnt[NEXT_BB] <= e->late_max) {
-        if (cnt[NEXT_RPKT] + cnt[NEXT_MA] > 0) STEP(run_late());
-        for (int kind : order)
-          if (kind == NEXT_SLOW || kind == NEXT_GAMMA || kind == NEXT_BB)
-            if (cnt[kind] > 0) STEP(run_kind(kind));
         continue;
       }
       for (int kind : order)

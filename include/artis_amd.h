@@ -660,7 +660,7 @@ int artis_amd_last_pool_usage(artis_amd_engine *eng, int64_t *units_used, int64_
 #define ARTIS_AMD_THERMAL_REFILL 8        /* k_thermal_q (ARTIS_AMD_REFILL=1) */
 #define ARTIS_AMD_THERMAL_COLD 16         /* ... instantiated with the on-demand records' look-ups (the model has cold levels) */
 #define ARTIS_AMD_THERMAL_TAIL 32         /* k_tail took the population's last packets */
-#define ARTIS_AMD_THERMAL_LATE 64         /* k_late carried the end of the population: r-packets and thermal packets in one persistent launch */
+#define ARTIS_AMD_THERMAL_LATE 64         /* k_late carried the end of the population: r-packets, thermal packets and slow-path actions in one persistent launch */
 int artis_amd_last_thermal_variants(artis_amd_engine *eng, int32_t *mask);
 /* How the kernels of the last artis_amd_update_packets_device call added to the per-cell estimators, as a mask: the form follows from the
  * number of non-empty cells (few-cells caps: k_rpkt 512 with the continuum table in LDS, 3072 without it; k_thermal 4096; k_gamma 2048),
@@ -712,7 +712,7 @@ int artis_amd_debug_sort_list(artis_amd_engine *eng, const int32_t *keys, const 
 
 /* Summed launch durations (HIP events on the launch stream) of the last artis_amd_update_packets_device() call by kind of kernel:
  * 0 k_rpkt (+ k_bfest_dense), 1 k_thermal, 2 k_slow, 3 k_gamma, 4 k_blackbody, 5 k_tail, 6 tile fills inside the call; 7 k_late.
- * launches may be NULL. */
+ * launches may be NULL (it counts the launches of every kind but the tile fills). */
 int artis_amd_last_kernel_ms_by_kind(artis_amd_engine *eng, double ms[8], int64_t launches[8]);
 
 /* Measurement builds only (-DARTIS_VISIT_COUNTS, tools/visit_sparsity.py): how many macro-atom transitions the last
