@@ -704,3 +704,50 @@ def deposition_arrays(ncell: int, nnuclides: int) -> dict:
     return dict(eps_ana=np.zeros(DEP_NCHANNELS * ncell), dep=np.zeros(DEP_NCHANNELS * ncell), ntlepton_deposition_rate_density=np.zeros(ncell),
                 grey_depth=np.zeros(ncell, np.float32), thick=np.zeros(ncell, np.int32), power_vectors=np.zeros(DEP_NVECTORS * nnuclides),
                 totmassnuclide=np.zeros(nnuclides))
+
+
+# pellet initialisation (include/artis_amd.h artis_amd_packet_init*)
+PINIT_NKERNELS = 7
+PINIT_KERNELS = ("energy", "checkpoints", "cumulative", "place", "decay", "normalise", "install")
+PINIT_CHANNEL_UNSET = -2
+
+
+class PacketInitModel(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("nuc_decay_daughters_probsum", _F64P), ("gamma_start", _I32P), ("gamma_energy", _F64P),
+                ("gamma_probability", _F64P), ("initenergyq", _F64P), ("tmax", C.c_double), ("initial_packets_on", C.c_int32),
+                ("use_model_initial_energy", C.c_int32), ("uniform_pellet_energies", C.c_int32), ("max_trials_per_launch", C.c_int32)]
+
+
+class PacketInitResult(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("en_cumulative", _F64P), ("energy_vector", _F64P), ("endecay_per_mass", _F64P), ("channel", _I32P),
+                ("trials", _I32P), ("npackets", C.c_int64), ("ngrid", C.c_int32), ("npts_nonempty", C.c_int32), ("npaths", C.c_int32),
+                ("ncheckpoints", C.c_int32), ("etot_simtime", C.c_double), ("e_cmf_per_packet", C.c_double), ("e_cmf_total", C.c_double),
+                ("e_ratio", C.c_double), ("continuation_launches", C.c_int32), ("max_trials", C.c_int32), ("kernel_ms", C.c_double * PINIT_NKERNELS)]
+
+
+_PINIT_MODEL_ARRAYS = (("nuc_decay_daughters_probsum", np.float64), ("gamma_start", np.int32), ("gamma_energy", np.float64),
+                       ("gamma_probability", np.float64), ("initenergyq", np.float64))
+
+
+def packet_init_model(d: dict):
+    """(PacketInitModel, the arrays it points into: keep them alive while it is used) from a dict over artis_packet_init_model's fields
+    (synth.packet_init_model); an array that is None or missing stays a NULL pointer, a switch that is missing takes the value most
+    option sets have (initial packets off, uniform pellet energies on, the default trial budget)"""
+    types = dict(PacketInitModel._fields_)
+    keep = {}
+    m = PacketInitModel(struct_size=C.sizeof(PacketInitModel), tmax=float(d["tmax"]), initial_packets_on=int(d.get("initial_packets_on", 0)),
+                        use_model_initial_energy=int(d.get("use_model_initial_energy", 0)), uniform_pellet_energies=int(d.get("uniform_pellet_energies", 1)),
+                        max_trials_per_launch=int(d.get("max_trials_per_launch", 0)))
+    for k, dt in _PINIT_MODEL_ARRAYS:
+        if d.get(k) is None:
+            continue
+        a = np.ascontiguousarray(d[k], dtype=dt).reshape(-1)
+        keep[k] = a if a.size else np.zeros(1, dt)
+        setattr(m, k, keep[k].ctypes.data_as(types[k]))
+    return m, keep
+
+
+def packet_init_arrays(ngrid: int, ncell: int, npaths: int, npackets: int) -> dict:
+    """zeroed host arrays for the outputs of artis_packet_init_result (the keys are its field names)"""
+    return dict(en_cumulative=np.zeros(ngrid), energy_vector=np.zeros(npaths), endecay_per_mass=np.zeros(ncell), channel=np.zeros(npackets, np.int32),
+                trials=np.zeros(npackets, np.int32))

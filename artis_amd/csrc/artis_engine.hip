@@ -32,6 +32,7 @@
 #include "ion_balance.h"
 #include "decay_update.h"
 #include "deposition.h"
+#include "packet_init.h"
 #include "spectra.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -1975,6 +1976,8 @@ struct DecayState;
 void decay_free(DecayState *st);
 struct DepState;
 void dep_free(DepState *st);
+struct PinitState;
+void pinit_free(PinitState *st);
 
 }  // namespace
 
@@ -2046,6 +2049,7 @@ struct artis_amd_engine {
   IbState *ib = nullptr;      // artis_amd_grid_update*: nothing until the first call
   DecayState *decay = nullptr;  // artis_amd_decay_*: nothing until artis_amd_decay_setup
   DepState *dep = nullptr;      // artis_amd_deposition_*: nothing until artis_amd_deposition_setup
+  PinitState *pinit = nullptr;  // artis_amd_packet_init*: nothing until artis_amd_packet_init_setup
   bool fit_since_step = false;  // an artis_amd_radfield_fit since the last propagation call (artis_amd_grid_update use_fit)
   ModelOwned own;
   std::vector<void *> model_allocs;
@@ -2502,6 +2506,32 @@ int ensure_aos(artis_amd_engine *e, int64_t n) {
   e->aos_valid = false;
   HIP_TRY(hipMalloc((void **)&e->d_aos, sizeof(artis_packet) * (size_t)(n > 0 ? n : 1)));
   e->aos_capacity = n;
+  return ARTIS_OK;
+}
+
+// The npackets structs in d_aos become the resident population (buffers made by ensure_packet_buffers / ensure_aos): slots in the order of
+// the packets' cells, records from the structs. What artis_amd_packets_upload does after its copy, and artis_amd_packet_init after its kernels.
+int install_resident_aos(artis_amd_engine *e, int64_t npackets) {
+  // a snapshot belongs to the population (and slot permutation) it was taken of
+  if (e->d_pkt_snapshot) (void)hipFree(e->d_pkt_snapshot);
+  e->d_pkt_snapshot = nullptr;
+  if (npackets > 0) {
+    e->aos_valid = true;
+    e->use_perm = false;
+    if (e->slot_order_by_cell && e->sort_lists && npackets >= 2 * BLOCK) {
+      // counting sort of the packet indices by propagation cell (the work-list sort kernels; the lists are free now)
+      int32_t *ident = e->d_lists[NEXT_RPKT][0], *keys = e->d_lists[NEXT_RPKT][1];
+      const int32_t n32 = (int32_t)npackets;
+      const int32_t nkeys = e->Mh.ngrid;
+      hipStream_t s = nullptr;
+      hipLaunchKernelGGL(k_aos_cellkeys, dim3(nblocks(npackets)), dim3(BLOCK), 0, s, e->d_aos, npackets, nkeys, ident, keys);
+      if (const int rc2 = sort_list(e, s, ident, keys, n32, nkeys, e->d_perm)) return rc2;
+      e->use_perm = true;
+    }
+    hipLaunchKernelGGL(k_aos_to_rec, dim3(nblocks(npackets)), dim3(BLOCK), 0, nullptr, e->d_aos, e->P, e->use_perm ? e->d_perm : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+  }
   return ARTIS_OK;
 }
 
@@ -3099,6 +3129,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   ib_free(e->ib);
   decay_free(e->decay);
   dep_free(e->dep);
+  pinit_free(e->pinit);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->cc.d_krow, e->cc.d_fill_cells, e->cc.d_waiting,
                   e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts};
@@ -3312,28 +3343,8 @@ int artis_amd_packets_upload(artis_amd_engine *e, const artis_packet *packets, i
   if (rc != ARTIS_OK) return rc;
   rc = ensure_aos(e, npackets);
   if (rc != ARTIS_OK) return rc;
-  // a snapshot belongs to the population (and slot permutation) it was taken of
-  if (e->d_pkt_snapshot) (void)hipFree(e->d_pkt_snapshot);
-  e->d_pkt_snapshot = nullptr;
-  if (npackets > 0) {
-    HIP_TRY(hipMemcpy(e->d_aos, packets, sizeof(artis_packet) * (size_t)npackets, hipMemcpyHostToDevice));
-    e->aos_valid = true;
-    e->use_perm = false;
-    if (e->slot_order_by_cell && e->sort_lists && npackets >= 2 * BLOCK) {
-      // counting sort of the packet indices by propagation cell (the work-list sort kernels; the lists are free now)
-      int32_t *ident = e->d_lists[NEXT_RPKT][0], *keys = e->d_lists[NEXT_RPKT][1];
-      const int32_t n32 = (int32_t)npackets;
-      const int32_t nkeys = e->Mh.ngrid;
-      hipStream_t s = nullptr;
-      hipLaunchKernelGGL(k_aos_cellkeys, dim3(nblocks(npackets)), dim3(BLOCK), 0, s, e->d_aos, npackets, nkeys, ident, keys);
-      if (const int rc2 = sort_list(e, s, ident, keys, n32, nkeys, e->d_perm)) return rc2;
-      e->use_perm = true;
-    }
-    hipLaunchKernelGGL(k_aos_to_rec, dim3(nblocks(npackets)), dim3(BLOCK), 0, nullptr, e->d_aos, e->P, e->use_perm ? e->d_perm : nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-  }
-  return ARTIS_OK;
+  if (npackets > 0) HIP_TRY(hipMemcpy(e->d_aos, packets, sizeof(artis_packet) * (size_t)npackets, hipMemcpyHostToDevice));
+  return install_resident_aos(e, npackets);
 }
 
 int artis_amd_packets_download(artis_amd_engine *e, artis_packet *packets, int64_t npackets) {
@@ -3696,7 +3707,7 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 
 }  // extern "C"
 
-// ------------------------------------------------------------------ the cell cache's host side; the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance, decay update, deposition rates
+// ------------------------------------------------------------------ the cell cache's host side; the propagation driver; the timestep-end stages: spectra, radiation-field fit, ion balance, decay update, deposition rates; the pellet initialisation
 #include "stage_cellcache.h"
 #include "stage_propagate.h"
 #include "stage_common.h"
@@ -3705,3 +3716,4 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 #include "stage_ionbal.h"
 #include "stage_decay.h"
 #include "stage_deposition.h"
+#include "stage_packet_init.h"

@@ -97,6 +97,8 @@ int artis_amd_decay_setup(artis_amd_engine *e, const artis_decay_model *d) {
   e->decay = nullptr;
   dep_free(e->dep);  // ... and the deposition set-up that was made on it goes with it
   e->dep = nullptr;
+  pinit_free(e->pinit);  // ... and the pellet set-up made on both
+  e->pinit = nullptr;
   DecayState *st = new DecayState();
   st->ncell = n;
   const int64_t nn = d->nnuclides, np = d->npaths, nflat = (int64_t)r.path_lambda.size(), nrow = (int64_t)r.row_coef.size();

@@ -104,6 +104,7 @@ struct DepState {
   uint64_t decay_serial = 0;  // the decay update this one was made on
   bool valid = false;
   double kernel_ms[3] = {};
+  std::vector<double> h_endecay_gamma, h_endecay_particle;  // [nnuclides], [nnuclides][6] as handed in: what artis_amd_packet_init_setup reads
 };
 
 void dep_free(DepState *st) { delete st; }
@@ -157,6 +158,8 @@ int artis_amd_deposition_setup(artis_amd_engine *e, const artis_deposition_model
   HIP_TRY(hipSetDevice(e->device));
   dep_free(e->dep);  // a second set-up replaces the first
   e->dep = nullptr;
+  pinit_free(e->pinit);  // ... and the pellet set-up that was made on the first goes with it
+  e->pinit = nullptr;
   DepState *st = new DepState();
   st->ncell = n;
   const int64_t nrad = (int64_t)r.rad_nuc.size(), nv = artis_dep::NVECTORS, nch = artis_dep::NCHANNELS;
@@ -171,6 +174,8 @@ int artis_amd_deposition_setup(artis_amd_engine *e, const artis_deposition_model
     return rc;
   }
   e->dep = st;
+  st->h_endecay_gamma.assign(m->nuc_endecay_gamma, m->nuc_endecay_gamma + nn);
+  st->h_endecay_particle.assign(m->nuc_endecay_particle, m->nuc_endecay_particle + (int64_t)nn * artis_dep::NQDOT);
   const hipMemcpyKind up = hipMemcpyHostToDevice;
   HIP_TRY(stage_copy(st->d_meanlife, dc->h_meanlife.data(), nn, up));
   HIP_TRY(stage_copy(st->d_energy, r.energy.data(), nv * nn, up));

@@ -77,6 +77,9 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_deposition_download.argtypes = [C.c_void_p, C.POINTER(abi.DepositionResult)]
     L.artis_amd_deposition_devptr.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
     L.artis_amd_grid_update_deposited.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
+    L.artis_amd_packet_init_setup.argtypes = [C.c_void_p, C.POINTER(abi.PacketInitModel)]
+    L.artis_amd_packet_init.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.artis_amd_packet_init_download.argtypes = [C.c_void_p, C.POINTER(abi.PacketInitResult)]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -106,6 +109,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_decay_setup", "artis_amd_decay_update", "artis_amd_decay_download", "artis_amd_grid_update_decayed",
     "artis_amd_deposition_setup", "artis_amd_deposition_update", "artis_amd_deposition_download", "artis_amd_deposition_devptr",
     "artis_amd_grid_update_deposited",
+    "artis_amd_packet_init_setup", "artis_amd_packet_init", "artis_amd_packet_init_download",
     "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
     "artis_amd_sizeof_plan", "artis_amd_engine_plan",
 ]
@@ -414,6 +418,46 @@ class Engine:
         self._ts = ts_next
         del keep
         return self.grid_update_download()
+
+    # pellet initialisation (include/artis_amd.h artis_amd_packet_init*)
+    def packet_init_setup(self, packet_init_model: dict):
+        """Validate and upload the gamma lines, the daughters' probability sums, the cells' initial energy and the switches: a dict over
+        artis_packet_init_model's fields (synth.packet_init_model). Needs decay_setup and deposition_setup; a second call replaces the
+        first, a new decay or deposition set-up invalidates it."""
+        m, keep = abi.packet_init_model(packet_init_model)
+        self._check(self.L.artis_amd_packet_init_setup(self.h, C.byref(m)))
+        del keep
+
+    def packet_init(self, npackets: int, seed_base: int, energy_vector=None, stream: int = 0) -> dict:
+        """Make npackets pellets by the reference's packet_init() on the device and install them as the resident population
+        (download_packets returns them in caller order); energy_vector: [npaths] energy_per_massoftopnuc_decaypath from the host (used as
+        it is), or None (the device forms it). Returns the download without the per-packet arrays."""
+        keep = None if energy_vector is None else np.ascontiguousarray(energy_vector, dtype=np.float64).reshape(-1)
+        self._check(self.L.artis_amd_packet_init(self.h, int(npackets), int(seed_base) & 0xFFFFFFFF, keep.ctypes.data_as(C.c_void_p) if keep is not None else None,
+                                                 C.c_void_p(stream)))
+        del keep
+        return self.packet_init_download(per_packet=False)
+
+    def packet_init_download(self, per_packet: bool = True, arrays: bool = True) -> dict:
+        """numpy arrays under the field names of artis_packet_init_result (channel and trials [npackets] only with per_packet), the
+        reported scalars, "kernel_ms" as a dict over abi.PINIT_KERNELS; arrays=False: only the reported fields"""
+        info = abi.PacketInitResult(struct_size=C.sizeof(abi.PacketInitResult))
+        self._check(self.L.artis_amd_packet_init_download(self.h, C.byref(info)))  # sizes first
+        out = abi.packet_init_arrays(info.ngrid, info.npts_nonempty, info.npaths, info.npackets if per_packet else 0) if arrays else {}
+        if not per_packet:
+            out.pop("channel", None), out.pop("trials", None)
+        types = dict(abi.PacketInitResult._fields_)
+        for k, v in out.items():
+            if v.size:
+                setattr(info, k, v.ctypes.data_as(types[k]))
+        if arrays:
+            self._check(self.L.artis_amd_packet_init_download(self.h, C.byref(info)))
+        for k in ("npackets", "ngrid", "npts_nonempty", "npaths", "ncheckpoints", "continuation_launches", "max_trials"):
+            out[k] = int(getattr(info, k))
+        for k in ("etot_simtime", "e_cmf_per_packet", "e_cmf_total", "e_ratio"):
+            out[k] = float(getattr(info, k))
+        out["kernel_ms"] = {k: float(info.kernel_ms[i]) for i, k in enumerate(abi.PINIT_KERNELS)}
+        return out
 
     def debug_cellcache(self, c: int) -> dict:
         d = self.model.d

@@ -1139,3 +1139,63 @@ def deposition_model(model: abi.Model, network: dict, seed: int = 31) -> dict:
     out = decay_energies(network, seed)
     out.update(assocvolume_tmin=assocvolume_tmin(model), radial_pos_tmin=radial_pos_tmin(model))
     return out
+
+
+# ---- pellet initialisation (include/artis_amd.h artis_amd_packet_init*)
+def gamma_lines(network: dict, energies: dict, seed: int = 41) -> dict:
+    """gamma_start [nnuclides + 1], gamma_energy, gamma_probability for a network of decay_network() and the energies of
+    decay_energies(): one to six lines for a nuclide with a gamma energy, probabilities scaled so that the sum of probability x energy is
+    the nuclide's endecay_gamma (up to rounding, as in the reference's line lists). Every fifth such nuclide has NO lines (its gamma
+    packets become k-packets, gammapkt.cc:870), every third one with lines begins with a line of zero probability. A nuclide without
+    gamma energy (stable, or every fourth radioactive one) has none."""
+    rng = np.random.default_rng(seed)
+    MEV = 1.602176634e-6
+    gamma = np.asarray(energies["nuc_endecay_gamma"], np.float64)
+    start, energy, prob = [0], [], []
+    k = 0
+    for n, eg in enumerate(gamma):
+        if eg > 0:
+            k += 1
+            if k % 5 != 2:
+                nl = int(rng.integers(1, 7))
+                e = rng.uniform(0.05, 3.5, nl) * MEV
+                p = rng.uniform(0.05, 1.0, nl)
+                if k % 3 == 0:
+                    p[0] = 0.0
+                    if nl == 1:
+                        e, p = np.append(e, 1.0 * MEV), np.append(p, 1.0)
+                p *= eg / float(np.sum(p * e))
+                energy += list(e)
+                prob += list(p)
+        start.append(len(energy))
+    return dict(gamma_start=np.array(start, np.int32), gamma_energy=np.array(energy, np.float64), gamma_probability=np.array(prob, np.float64))
+
+
+def decay_daughters_probsum(network: dict, seed: int = 43) -> np.ndarray:
+    """[nnuclides] Nuclide::decay_daughters_probsum: 1 for most decaying nuclides, 0.75 or 2 for every seventh (fission-like yields), 0 for a
+    stable one"""
+    life = np.asarray(network["nuc_meanlife"], np.float64)
+    out = np.where(life > 0, 1.0, 0.0)
+    rad = np.nonzero(life > 0)[0]
+    out[rad[3::7]] = 0.75
+    out[rad[5::7]] = 2.0
+    return out
+
+
+def initenergyq(model: abi.Model, seed: int = 47) -> np.ndarray:
+    """[npts_nonempty] grid::get_initenergyq [erg/g]: of the order of the decay energy per mass of a cell; every ninth cell has none"""
+    rng = np.random.default_rng(seed)
+    q = 10.0 ** rng.uniform(14.0, 16.0, int(model["npts_nonempty"]))
+    q[4::9] = 0.0
+    return q
+
+
+def packet_init_model(model: abi.Model, network: dict, energies: dict, tmax: float, initial_energy: bool = False, seed: int = 41,
+                      max_trials_per_launch: int = 0) -> dict:
+    """A dict over artis_packet_init_model's fields for a grid made by build(), a network of decay_network() and the energies of
+    decay_energies(). initial_energy: INITIAL_PACKETS_ON and USE_MODEL_INITIAL_ENERGY (the classic option set); else both off."""
+    out = gamma_lines(network, energies, seed)
+    out.update(nuc_decay_daughters_probsum=decay_daughters_probsum(network, seed + 2), tmax=float(tmax), initial_packets_on=int(initial_energy),
+               use_model_initial_energy=int(initial_energy), uniform_pellet_energies=1, max_trials_per_launch=int(max_trials_per_launch),
+               initenergyq=initenergyq(model, seed + 6) if initial_energy else None)
+    return out

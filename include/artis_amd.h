@@ -1015,6 +1015,61 @@ int artis_amd_deposition_devptr(artis_amd_engine *eng, const double **eps_ana, c
  * ARTIS_ERR_ARG unless a deposition update is valid, was made for nts_next == ts_next->nts and on the decay update of ts_next->mid. */
 int artis_amd_grid_update_deposited(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream);
 
+/* ---- pellet initialisation -----------------------------------------------------------------
+ * The reference's packet_init() (packet.cc:91) on the device: the energy every decay path releases per mass of its top nuclide between
+ * t0 (t_model with initial packets on, else tmin) and tmax (decay.cc:1067), per cell the decay energy per mass (decay.cc:1052), the
+ * cumulative energy over ALL propagation cells in index order (packet.cc:116-131), and per packet n -- generator seeded seed_base + n
+ * (input.cc:1912) -- the cell, the position (grid.cc:1603), the decay channel (decay.cc:1347), the decay time (decay.cc:482), the decaying
+ * nuclide with its particle / gamma choice and gamma line (gammapkt.cc:869), direction and rest-frame energy (packet.cc:83-85); then the
+ * normalisation of packet.cc:149-159. Every sum is the sequential sum of the reference, in its order; every packet draws from its own
+ * generator in the reference's order, and the state left in the packet is the one propagation continues from. With the host's energy
+ * vector handed in, every discrete field, the generator state, the energies and the 3D positions are the host's bit for bit; decay times,
+ * 1D / 2D positions, directions and e_rf differ by the device's log / cbrt / sin / cos against the host's. Works in every build. */
+#define ARTIS_PINIT_NKERNELS 7
+typedef struct artis_packet_init_model {
+  int64_t struct_size;                        /* sizeof(artis_packet_init_model) */
+  const double *nuc_decay_daughters_probsum;  /* [nnuclides] Nuclide::decay_daughters_probsum (decay.cc:238) */
+  const int32_t *gamma_start;                 /* [nnuclides + 1] nuclide n's lines are [gamma_start[n], gamma_start[n + 1]); none: it emits no gamma packets */
+  const double *gamma_energy;                 /* [gamma_start[nnuclides]] erg */
+  const double *gamma_probability;            /* ... per decay */
+  const double *initenergyq;                  /* [npts_nonempty] grid::get_initenergyq [erg/g]; NULL unless initial_packets_on && use_model_initial_energy */
+  double tmax;                                /* globals::tmax (tmin is the model's) */
+  int32_t initial_packets_on;                 /* INITIAL_PACKETS_ON */
+  int32_t use_model_initial_energy;           /* USE_MODEL_INITIAL_ENERGY */
+  int32_t uniform_pellet_energies;            /* UNIFORM_PELLET_ENERGIES: 0 is ARTIS_ERR_UNSUPPORTED */
+  int32_t max_trials_per_launch;              /* decay-time trials of one packet per launch before it is parked; 0: 4096 */
+} artis_packet_init_model;
+typedef struct artis_packet_init_result {
+  int64_t struct_size; /* sizeof(artis_packet_init_result) */
+  /* host arrays to fill; NULL: skip */
+  double *en_cumulative;      /* [ngrid] */
+  double *energy_vector;      /* [npaths] energy_per_massoftopnuc_decaypath as the device used it */
+  double *endecay_per_mass;   /* [npts_nonempty] */
+  int32_t *channel;           /* [npackets] the decay channel of every packet in caller order: its path, npaths for the initial-energy channel */
+  int32_t *trials;            /* [npackets] its decay-time trials */
+  /* reported */
+  int64_t npackets;
+  int32_t ngrid, npts_nonempty, npaths, ncheckpoints;
+  double etot_simtime, e_cmf_per_packet, e_cmf_total, e_ratio;
+  int32_t continuation_launches; /* launches that continued parked packets */
+  int32_t max_trials;            /* the largest trial count of one packet */
+  double kernel_ms[ARTIS_PINIT_NKERNELS]; /* HIP-event time: [0] k_pinit_energy, [1] k_pinit_checkpoints, [2] k_pinit_cumulative, [3] k_pinit_place,
+                                             [4] k_pinit_decay (all launches), [5] k_pinit_gather, k_pinit_total and k_pinit_scale, [6] the installation */
+} artis_packet_init_result;
+/* Needs artis_amd_decay_setup and artis_amd_deposition_setup (a new one of either invalidates this set-up). Validates (ARTIS_ERR_ARG with a
+ * text naming the nuclide: a non-finite or negative value, a probsum <= 0 for a decaying nuclide, gamma_start not monotone; tmax <= tmin,
+ * t_model > tmin, the initial-energy channel without initenergyq), refuses uniform_pellet_energies == 0 (ARTIS_ERR_UNSUPPORTED), uploads.
+ * A second call replaces the first. */
+int artis_amd_packet_init_setup(artis_amd_engine *eng, const artis_packet_init_model *model);
+/* Make npackets pellets on hip_stream (synchronous) and install them as the resident population, exactly as artis_amd_packets_upload
+ * would with the same structs: artis_amd_packets_download returns them in caller order. energy_vector_or_null: [npaths] the host's
+ * energy_per_massoftopnuc_decaypath, used as it is; NULL: the device forms it. A packet whose decay time is not accepted within
+ * max_trials_per_launch trials is parked with its generator state and continued by a further launch (the result does not depend on where
+ * it was cut); after 4096 such launches ARTIS_ERR_NOTCONVERGED names the path. On any error the previous population stays resident. */
+int artis_amd_packet_init(artis_amd_engine *eng, int64_t npackets, uint32_t seed_base, const double *energy_vector_or_null, void *hip_stream);
+/* Copy the results of the last artis_amd_packet_init to the host (sizes in the reported fields even when every pointer is NULL). */
+int artis_amd_packet_init_download(artis_amd_engine *eng, artis_packet_init_result *out);
+
 #ifdef __cplusplus
 }
 #endif
