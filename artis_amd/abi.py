@@ -751,3 +751,51 @@ def packet_init_arrays(ngrid: int, ncell: int, npaths: int, npackets: int) -> di
     """zeroed host arrays for the outputs of artis_packet_init_result (the keys are its field names)"""
     return dict(en_cumulative=np.zeros(ngrid), energy_vector=np.zeros(npaths), endecay_per_mass=np.zeros(ncell), channel=np.zeros(npackets, np.int32),
                 trials=np.zeros(npackets, np.int32))
+
+
+# thermal balance of the thin cells (include/artis_amd.h artis_amd_thermal_*)
+THERMAL_BRACKETED, THERMAL_PINNED_LOW, THERMAL_PINNED_HIGH, THERMAL_NONFINITE = 256, 512, 1024, 2048
+THERMAL_DAMPED_UP, THERMAL_DAMPED_DOWN, THERMAL_MAXIT, THERMAL_RENORM_ONE = 4096, 8192, 16384, 32768
+THERMAL_FLAGS = IONBAL_FLAGS + ["bracketed", "pinned_low", "pinned_high", "nonfinite_ends", "damped_up", "damped_down", "maxit", "renorm_one"]
+THERMAL_NRATES = 10
+THERMAL_NTIMES = 4
+THERMAL_RATES = ("cooling_ff", "cooling_collisional", "cooling_fb", "cooling_adiabatic", "heating_ff", "heating_bf", "heating_collisional",
+                 "heating_dep", "residual", "dep_frac_heating")
+THERMAL_KERNELS = ("renorm", "gamma_partfunct", "solve", "rates")
+
+
+class ThermalParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("rho", _F32P), ("elem_massfracs", _F32P), ("elem_meanweight", _F32P), ("bfheatingcoeffs", _F64P),
+                ("ntlepton_dep", _F64P), ("dep_alpha", _F64P), ("dep_spfission", _F64P), ("clumpfactor", _F32P)]
+
+
+class ThermalResult(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("Te", _F32P), ("Te_solved", _F64P), ("bracket", _F64P), ("evals", _I32P), ("flags", _I32P),
+                ("nne", _F32P), ("rates", _F64P), ("ion_groundlevelpops", _F32P), ("ion_partfuncts", _F32P), ("phi", _F64P), ("gamma", _F64P),
+                ("corrphotoionrenorm", _F64P), ("ncells_flagged", C.c_int64 * len(THERMAL_FLAGS)), ("total_evals", C.c_int64),
+                ("nfitted", C.c_int64), ("npts_nonempty", C.c_int32), ("nions", C.c_int32), ("nbfcontinua_ground", C.c_int32),
+                ("nlevels", C.c_int32), ("kernel_ms", C.c_double * THERMAL_NTIMES)]
+
+
+def thermal_params(bfheatingcoeffs, rho=None, elem_massfracs=None, elem_meanweight=None, ntlepton_dep=None, dep_alpha=None,
+                   dep_spfission=None, clumpfactor=None):
+    """(ThermalParams, the arrays it points into: keep them alive while it is used); None: a NULL pointer"""
+    keep = {}
+    p = ThermalParams(struct_size=C.sizeof(ThermalParams))
+    for k, v, dt, pt in (("rho", rho, np.float32, _F32P), ("elem_massfracs", elem_massfracs, np.float32, _F32P),
+                         ("elem_meanweight", elem_meanweight, np.float32, _F32P), ("bfheatingcoeffs", bfheatingcoeffs, np.float64, _F64P),
+                         ("ntlepton_dep", ntlepton_dep, np.float64, _F64P), ("dep_alpha", dep_alpha, np.float64, _F64P),
+                         ("dep_spfission", dep_spfission, np.float64, _F64P), ("clumpfactor", clumpfactor, np.float32, _F32P)):
+        if v is None:
+            continue
+        keep[k] = np.ascontiguousarray(v, dtype=dt).reshape(-1)
+        setattr(p, k, keep[k].ctypes.data_as(pt))
+    return p, keep
+
+
+def thermal_arrays(ncell: int, nions: int, nbfg: int) -> dict:
+    """zeroed host arrays for every output of artis_thermal_result (the keys are its field names)"""
+    return dict(Te=np.zeros(ncell, np.float32), Te_solved=np.zeros(ncell), bracket=np.zeros(2 * ncell), evals=np.zeros(ncell, np.int32),
+                flags=np.zeros(ncell, np.int32), nne=np.zeros(ncell, np.float32), rates=np.zeros(ncell * THERMAL_NRATES),
+                ion_groundlevelpops=np.zeros(ncell * nions, np.float32), ion_partfuncts=np.zeros(ncell * nions, np.float32),
+                phi=np.zeros(ncell * nions), gamma=np.zeros(max(ncell * nbfg, 1)), corrphotoionrenorm=np.zeros(max(ncell * nbfg, 1)))

@@ -33,6 +33,7 @@
 #include "decay_update.h"
 #include "deposition.h"
 #include "packet_init.h"
+#include "thermal_balance.h"
 #include "spectra.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -1978,6 +1979,8 @@ struct DepState;
 void dep_free(DepState *st);
 struct PinitState;
 void pinit_free(PinitState *st);
+struct TbState;
+void tb_free(TbState *st);
 
 }  // namespace
 
@@ -2050,6 +2053,8 @@ struct artis_amd_engine {
   DecayState *decay = nullptr;  // artis_amd_decay_*: nothing until artis_amd_decay_setup
   DepState *dep = nullptr;      // artis_amd_deposition_*: nothing until artis_amd_deposition_setup
   PinitState *pinit = nullptr;  // artis_amd_packet_init*: nothing until artis_amd_packet_init_setup
+  TbState *tb = nullptr;        // artis_amd_thermal_*: nothing until the first call
+  uint64_t cellstate_serial = 0;  // counts the changes of the resident cell state (artis_amd_set_cellstate, the hand-over of artis_amd_grid_update*)
   bool fit_since_step = false;  // an artis_amd_radfield_fit since the last propagation call (artis_amd_grid_update use_fit)
   ModelOwned own;
   std::vector<void *> model_allocs;
@@ -3130,6 +3135,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   decay_free(e->decay);
   dep_free(e->dep);
   pinit_free(e->pinit);
+  tb_free(e->tb);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->cc.d_krow, e->cc.d_fill_cells, e->cc.d_waiting,
                   e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts};
@@ -3246,6 +3252,7 @@ int artis_amd_set_cellstate(artis_amd_engine *e, const artis_cellstate *cells, c
   }
 #endif
   e->have_cells = true;
+  e->cellstate_serial++;
   return artis_amd_populate_cellcache(e, nullptr);
 }
 
@@ -3717,3 +3724,4 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 #include "stage_decay.h"
 #include "stage_deposition.h"
 #include "stage_packet_init.h"
+#include "stage_thermal.h"

@@ -85,6 +85,13 @@ __global__ void __launch_bounds__(BLOCK) k_ib_renorm(double *renorm, const int32
   if (flags[i / nbfg] & artis_ib::FORCED_SAHA) renorm[i] = 1.;
 }
 
+// dst[cell][ground continuum] = src[...] in the cells the fit has fitted (artis_amd_grid_update_thermal)
+__global__ void __launch_bounds__(BLOCK) k_ib_fitted_copy(double *dst, const double *src, const int32_t *fit_flags, int64_t ncell, int32_t nbfg) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= ncell * nbfg) return;
+  if (fit_flags[i / nbfg] & ARTIS_RADFIELD_FITTED) dst[i] = src[i];
+}
+
 // the scratch of artis_amd_grid_update*: one block, made at the first call
 struct IbState {
   StageBlock block;
@@ -137,6 +144,11 @@ int ib_init(artis_amd_engine *e) {
 struct IbMatter {
   const float *rho, *massfrac, *meanweight;
   const int32_t *thick = nullptr;
+  // artis_amd_grid_update_thermal (stage_thermal.h): in the cells the fit has fitted, T_e, the balance's gamma [cell][ground continuum]
+  // and the cell state's corrphotoionrenorm are the thermal solve's (device arrays)
+  const float *thermal_Te = nullptr;
+  const double *thermal_gamma = nullptr, *thermal_renorm = nullptr;
+  const float *thermal_clump = nullptr;  // ... and the clumping factors of every cell the solve's (they become the cell state's)
 };
 
 // artis_amd_grid_update (matter == nullptr: u's host arrays) and artis_amd_grid_update_decayed (matter: copied device to device into the same scratch)
@@ -193,6 +205,7 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
   a.fit_Te = u->use_fit ? e->rf->d_Te : st->d_hTe;
   a.fit_flags = u->use_fit ? e->rf->d_flags : nullptr;
   a.host_Te = (u->use_fit && u->Te) ? st->d_hTe : nullptr;
+  if (matter && matter->thermal_Te) a.host_Te = matter->thermal_Te;
   a.cur_ground = e->C.ion_groundlevelpops;
   a.cur_thick = e->C.thick;
   a.gamma_raw = e->E.gammaestimator;
@@ -204,6 +217,7 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
   }
   a.tmin = e->model_copy.tmin;
   a.clump = u->clumpfactor ? st->d_clump : e->C.clumpfactor;
+  if (matter && matter->thermal_clump) a.clump = matter->thermal_clump;
   a.cell.rho = st->d_rho;
   a.cell.massfrac = st->d_massfrac;
   a.cell.meanweight_cell = ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT ? st->d_meanweight : nullptr;
@@ -243,6 +257,10 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
     if ((rc = done("k_ib_cells")) != ARTIS_OK) return rc;
     if (st->nbfg > 0) hipLaunchKernelGGL(k_ib_gamma, dim3(nblocks(n * st->nbfg)), dim3(BLOCK), 0, s, a);
     if ((rc = done("k_ib_gamma")) != ARTIS_OK) return rc;
+    if (matter && matter->thermal_gamma && st->nbfg > 0) {
+      hipLaunchKernelGGL(k_ib_fitted_copy, dim3(nblocks(n * st->nbfg)), dim3(BLOCK), 0, s, st->d_gamma, matter->thermal_gamma, a.fit_flags, n, (int32_t)st->nbfg);
+      if ((rc = done("k_ib_fitted_copy")) != ARTIS_OK) return rc;
+    }
     if (ni > 0) hipLaunchKernelGGL(k_ib_partfunct, dim3(nblocks(n * ni)), dim3(BLOCK), 0, s, a);
     if ((rc = done("k_ib_partfunct")) != ARTIS_OK) return rc;
   }
@@ -295,15 +313,22 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
   if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT) HIP_TRY(stage_copy(e->C.elem_meanweight, st->d_meanweight, n * ne, hipMemcpyDeviceToDevice, &s));
   if (u->kappagrey) HIP_TRY(stage_copy(e->C.kappagrey, st->d_kappagrey, n, hipMemcpyDeviceToDevice, &s));
   if (u->clumpfactor) HIP_TRY(stage_copy(e->C.clumpfactor, st->d_clump, n, hipMemcpyDeviceToDevice, &s));
+  if (matter && matter->thermal_clump) HIP_TRY(stage_copy(e->C.clumpfactor, matter->thermal_clump, n, hipMemcpyDeviceToDevice, &s));
   if (u->ffegrp) HIP_TRY(stage_copy(e->C.ffegrp, st->d_ffegrp, n, hipMemcpyDeviceToDevice, &s));
   if (ARTIS_OPT_USE_LUT_PHOTOION && n > 0 && st->nbfg > 0) {
     hipLaunchKernelGGL(k_ib_renorm, dim3(nblocks(n * st->nbfg)), dim3(BLOCK), 0, s, const_cast<double *>(e->C.corrphotoionrenorm),
                        st->d_flags, n, (int32_t)st->nbfg);
     HIP_TRY(hipGetLastError());
+    if (matter && matter->thermal_renorm) {
+      hipLaunchKernelGGL(k_ib_fitted_copy, dim3(nblocks(n * st->nbfg)), dim3(BLOCK), 0, s, const_cast<double *>(e->C.corrphotoionrenorm),
+                         matter->thermal_renorm, a.fit_flags, n, (int32_t)st->nbfg);
+      HIP_TRY(hipGetLastError());
+    }
   }
   // (the thickness last: the balance and the renormalisation read the current one)
   HIP_TRY(stage_copy(e->C.thick, st->d_thick, n, hipMemcpyDeviceToDevice, &s));
   HIP_TRY(hipStreamSynchronize(s));
+  e->cellstate_serial++;
   e->S = make_step(*ts_next);
   const auto t0 = std::chrono::steady_clock::now();
   rc = artis_amd_populate_cellcache(e, hip_stream);

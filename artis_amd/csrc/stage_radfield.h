@@ -70,6 +70,7 @@ struct RfState {
   int32_t *d_flags = nullptr, *d_counts = nullptr;
   unsigned long long *d_totals = nullptr;
   bool valid = false;
+  uint64_t serial = 0;  // counts the fits (artis_amd_grid_update_thermal: was the thermal solve made on the last one)
   double prev_mid = 0., deltat = 0.;  // the normalisation of the last fit (artis_amd_grid_update reads it)
   int32_t nprocs = 1, lte = 0;
   unsigned long long totals[ARTIS_RADFIELD_NCOUNTS] = {};
@@ -176,6 +177,7 @@ int artis_amd_radfield_fit(artis_amd_engine *e, const artis_radfield_config *cfg
   st->nprocs = cfg->nprocs;
   st->lte = a.lte;
   st->valid = true;
+  st->serial++;
   e->fit_since_step = true;
   return ARTIS_OK;
 }

@@ -80,6 +80,10 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_packet_init_setup.argtypes = [C.c_void_p, C.POINTER(abi.PacketInitModel)]
     L.artis_amd_packet_init.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.artis_amd_packet_init_download.argtypes = [C.c_void_p, C.POINTER(abi.PacketInitResult)]
+    L.artis_amd_thermal_solve.argtypes = [C.c_void_p, C.POINTER(abi.ThermalParams), C.c_void_p]
+    L.artis_amd_thermal_rates.argtypes = [C.c_void_p, C.POINTER(abi.ThermalParams), C.c_void_p, C.c_int, C.c_void_p]
+    L.artis_amd_thermal_download.argtypes = [C.c_void_p, C.POINTER(abi.ThermalResult)]
+    L.artis_amd_grid_update_thermal.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -110,6 +114,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_deposition_setup", "artis_amd_deposition_update", "artis_amd_deposition_download", "artis_amd_deposition_devptr",
     "artis_amd_grid_update_deposited",
     "artis_amd_packet_init_setup", "artis_amd_packet_init", "artis_amd_packet_init_download",
+    "artis_amd_thermal_solve", "artis_amd_thermal_rates", "artis_amd_thermal_download", "artis_amd_grid_update_thermal",
     "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
     "artis_amd_sizeof_plan", "artis_amd_engine_plan",
 ]
@@ -458,6 +463,61 @@ class Engine:
             out[k] = float(getattr(info, k))
         out["kernel_ms"] = {k: float(info.kernel_ms[i]) for i, k in enumerate(abi.PINIT_KERNELS)}
         return out
+
+    # thermal balance of the thin cells (include/artis_amd.h artis_amd_thermal_*)
+    def thermal_solve(self, bfheatingcoeffs, rho=None, elem_massfracs=None, elem_meanweight=None, ntlepton_dep=None, dep_alpha=None,
+                      dep_spfission=None, clumpfactor=None, stream: int = 0) -> dict:
+        """Renormalisation, Gamma per ground population, partition functions and the T_e of the thermal balance of every cell the last
+        radiation-field fit has fitted, on the device. bfheatingcoeffs [ncell, nlevels] from the host; the matter None: the last
+        decay_update's; the deposition inputs None: the last deposition_update's. Returns the download."""
+        p, keep = abi.thermal_params(bfheatingcoeffs, rho, elem_massfracs, elem_meanweight, ntlepton_dep, dep_alpha, dep_spfission, clumpfactor)
+        self._check(self.L.artis_amd_thermal_solve(self.h, C.byref(p), C.c_void_p(stream)))
+        del keep
+        return self.thermal_download()
+
+    def thermal_rates(self, bfheatingcoeffs, Te=None, rebalance: bool = False, ntlepton_dep=None, dep_alpha=None, dep_spfission=None,
+                      stream: int = 0) -> dict:
+        """The rates of every non-empty cell at Te (None: the resident T_e); rebalance False: with the resident n_e, populations,
+        partition functions and matter; True: after the ion balance at Te with the last thermal_solve's Gamma. Returns the download."""
+        p, keep = abi.thermal_params(bfheatingcoeffs, None, None, None, ntlepton_dep, dep_alpha, dep_spfission, None)
+        te = None if Te is None else np.ascontiguousarray(Te, dtype=np.float32)
+        self._check(self.L.artis_amd_thermal_rates(self.h, C.byref(p), te.ctypes.data_as(C.c_void_p) if te is not None else None,
+                                                   int(bool(rebalance)), C.c_void_p(stream)))
+        del keep
+        return self.thermal_download()
+
+    def thermal_download(self, arrays: bool = True) -> dict:
+        """numpy arrays under the field names of artis_thermal_result (per-ion ones [ncell, nions], gamma and corrphotoionrenorm
+        [ncell, nbfcontinua_ground], bracket [ncell, 2], rates [ncell, 10] in abi.THERMAL_RATES order), "ncells_flagged" as a dict over
+        abi.THERMAL_FLAGS, "total_evals", "nfitted" and "kernel_ms" as a dict over abi.THERMAL_KERNELS; arrays=False: only those"""
+        info = abi.ThermalResult(struct_size=C.sizeof(abi.ThermalResult))
+        self._check(self.L.artis_amd_thermal_download(self.h, C.byref(info)))  # sizes first
+        n, ni, g = info.npts_nonempty, info.nions, info.nbfcontinua_ground
+        out = abi.thermal_arrays(n, ni, g) if arrays else {}
+        types = dict(abi.ThermalResult._fields_)
+        for k, v in out.items():
+            setattr(info, k, v.ctypes.data_as(types[k]))
+        if arrays:
+            self._check(self.L.artis_amd_thermal_download(self.h, C.byref(info)))
+            for k in ("ion_groundlevelpops", "ion_partfuncts", "phi"):
+                out[k] = out[k].reshape(n, ni)
+            for k in ("gamma", "corrphotoionrenorm"):
+                out[k] = out[k][: n * g].reshape(n, g)
+            out["bracket"] = out["bracket"].reshape(n, 2)
+            out["rates"] = out["rates"].reshape(n, abi.THERMAL_NRATES)
+        out["ncells_flagged"] = {k: int(info.ncells_flagged[i]) for i, k in enumerate(abi.THERMAL_FLAGS)}
+        out.update(total_evals=int(info.total_evals), nfitted=int(info.nfitted),
+                   kernel_ms={k: float(info.kernel_ms[i]) for i, k in enumerate(abi.THERMAL_KERNELS)})
+        return out
+
+    def grid_update_thermal(self, ts_next: abi.Timestep, thick=None, kappagrey=None, ffegrp=None, stream: int = 0) -> dict:
+        """grid_update with the matter, the clumping factors, and in fitted cells the T_e, Gamma and corrphotoionrenorm of the last
+        thermal_solve; thick None: the last deposition_update's flags. Returns the grid_update download."""
+        u, keep = abi.grid_update_config(True, None, None, thick, None, None, None, None, None, kappagrey, None, ffegrp)
+        self._check(self.L.artis_amd_grid_update_thermal(self.h, C.byref(u), C.cast(ts_next.ref(), C.c_void_p), C.c_void_p(stream)))
+        self._ts = ts_next
+        del keep
+        return self.grid_update_download()
 
     def debug_cellcache(self, c: int) -> dict:
         d = self.model.d

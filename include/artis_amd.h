@@ -1070,6 +1070,80 @@ int artis_amd_packet_init(artis_amd_engine *eng, int64_t npackets, uint32_t seed
 /* Copy the results of the last artis_amd_packet_init to the host (sizes in the reported fields even when every pointer is NULL). */
 int artis_amd_packet_init_download(artis_amd_engine *eng, artis_packet_init_result *out);
 
+/* ---- thermal balance of the thin cells -----------------------------------------------------
+ * What the reference's grid update does for a cell the radiation-field fit has fitted, outside an LTE iteration, on the device: the
+ * renormalisation of the photoionisation estimator (update_grid.cc:344-387), Gamma per ground population of every ion with a ground
+ * continuum (calculate_iongamma_per_gspop ratecoeff.cc:926), the partition functions at the fit's T_J and the T_e of the thermal
+ * balance (call_T_e_finder thermalbalance.cc:258: a TOMS 748 root of heating - cooling in [MINTEMP, MAXTEMP], every evaluation with
+ * its own ion balance; damped to [0.5, 2] x the resident T_e). The bound-free heating coefficients (calculate_bfheatingcoeffs, with
+ * their renormalisation applied) come from the host. Builds with LTEPOP_EXCITATION_USE_TJ, USE_LUT_PHOTOION, without NT_ON,
+ * DIRECT_COL_HEAT and NLTE populations (classic and its variants); every other build: ARTIS_ERR_UNSUPPORTED, the text names the option.
+ * A rate is summed by the 64 lanes of a wave in a fixed order (artis_amd/csrc/thermal_balance.h): bitwise reproducible. */
+#define ARTIS_THERMAL_BRACKETED 256     /* a sign change over [MINTEMP, MAXTEMP]: the root search ran */
+#define ARTIS_THERMAL_PINNED_LOW 512    /* cooling wins everywhere (or non-finite ends): MINTEMP */
+#define ARTIS_THERMAL_PINNED_HIGH 1024  /* heating wins everywhere: MAXTEMP */
+#define ARTIS_THERMAL_NONFINITE 2048    /* the residual at MINTEMP or MAXTEMP is not finite */
+#define ARTIS_THERMAL_DAMPED_UP 4096    /* the solution was above 2 x the resident T_e */
+#define ARTIS_THERMAL_DAMPED_DOWN 8192  /* ... below 0.5 x */
+#define ARTIS_THERMAL_MAXIT 16384       /* the root search stopped at 100 evaluations */
+#define ARTIS_THERMAL_RENORM_ONE 32768  /* a ground continuum of the cell could not be renormalised: corrphotoionrenorm = 1 there */
+#define ARTIS_THERMAL_NFLAGS 16         /* bits 0-7: ARTIS_IONBAL_* of the last evaluation's ion balance */
+#define ARTIS_THERMAL_NRATES 10
+#define ARTIS_THERMAL_NTIMES 4
+typedef struct artis_thermal_params {
+  int64_t struct_size; /* sizeof(artis_thermal_params) */
+  /* the new timestep's matter, as artis_grid_update's; all three NULL: the device arrays of the last artis_amd_decay_update */
+  const float *rho;             /* [npts_nonempty] */
+  const float *elem_massfracs;  /* [npts_nonempty*nelements] */
+  const float *elem_meanweight; /* [npts_nonempty*nelements]: USE_CALCULATED_MEANATOMICWEIGHT builds only */
+  const double *bfheatingcoeffs; /* [npts_nonempty*nlevels] calculate_bfheatingcoeffs' result (thermalbalance.cc:217) with its
+                                    renormalisation applied; required */
+  /* [npts_nonempty] each; all three NULL: the block of the last artis_amd_deposition_update */
+  const double *ntlepton_dep, *dep_alpha, *dep_spfission;
+  const float *clumpfactor; /* [npts_nonempty] or NULL: the resident one */
+} artis_thermal_params;
+typedef struct artis_thermal_result {
+  int64_t struct_size; /* sizeof(artis_thermal_result) */
+  /* host arrays to fill; NULL: skip */
+  float *Te;           /* [npts_nonempty] the T_e stored (an unfitted cell: the fit's, T_J) */
+  double *Te_solved;   /* [npts_nonempty] before the damping */
+  double *bracket;     /* [npts_nonempty][2] the final bracket (both Te_solved without a root search) */
+  int32_t *evals;      /* [npts_nonempty] evaluations of the residual */
+  int32_t *flags;      /* [npts_nonempty] ARTIS_THERMAL_* | ARTIS_IONBAL_* */
+  float *nne;          /* [npts_nonempty] */
+  double *rates;       /* [npts_nonempty][ARTIS_THERMAL_NRATES]: cooling_ff, cooling_collisional, cooling_fb, cooling_adiabatic,
+                          heating_ff, heating_bf, heating_collisional, heating_dep, heating - cooling, dep_frac_heating */
+  float *ion_groundlevelpops; /* [npts_nonempty*nions] */
+  float *ion_partfuncts;      /* [npts_nonempty*nions] at the fit's T_J */
+  double *phi;                /* [npts_nonempty*nions] of the last evaluation */
+  double *gamma;              /* [npts_nonempty*nbfcontinua_ground] Gamma per ground population */
+  double *corrphotoionrenorm; /* [npts_nonempty*nbfcontinua_ground] */
+  /* reported */
+  int64_t ncells_flagged[ARTIS_THERMAL_NFLAGS]; /* cells with bit k set */
+  int64_t total_evals, nfitted;
+  int32_t npts_nonempty, nions, nbfcontinua_ground, nlevels;
+  double kernel_ms[ARTIS_THERMAL_NTIMES]; /* HIP-event time: [0] k_tb_renorm, [1] k_tb_gamma and k_tb_partfunct, [2] k_tb_solve,
+                                             [3] k_tb_rates of the last artis_amd_thermal_rates */
+} artis_thermal_result;
+/* The solve on hip_stream (synchronous). Needs a cell state and an artis_amd_radfield_fit since the last propagation call. Leaves
+ * estimators, packets and the resident cell state untouched; keeps device copies of the matter it used. */
+int artis_amd_thermal_solve(artis_amd_engine *eng, const artis_thermal_params *params, void *hip_stream);
+/* The rates of every non-empty cell at Te[] (NULL: the resident T_e) into the same result block. Like the solve it needs
+ * params->bfheatingcoeffs, the deposition inputs (or a deposition update) and a fit since the last propagation call (the estimators'
+ * normalisation is the fit's), with either value of rebalance. rebalance = 0: with the resident n_e,
+ * ground populations, partition functions, T_J and matter (params' matter is not read); rebalance = 1: the ion balance of a solve's
+ * evaluation at Te[] first, with Gamma, partition functions and matter of the last artis_amd_thermal_solve (ARTIS_ERR_ARG without one). */
+int artis_amd_thermal_rates(artis_amd_engine *eng, const artis_thermal_params *params, const float *Te, int rebalance, void *hip_stream);
+/* Copy the results to the host (sizes in the reported fields even when every pointer is NULL). */
+int artis_amd_thermal_download(artis_amd_engine *eng, artis_thermal_result *out);
+/* artis_amd_grid_update with the matter the last artis_amd_thermal_solve used (u->rho, u->elem_massfracs and u->elem_meanweight must be
+ * NULL), u->use_fit = 1, and in the cells the fit fitted the solve's T_e, Gamma per ground population (the balance's gamma) and
+ * corrphotoionrenorm (written to the cell state). u->thick NULL: the flags of the last artis_amd_deposition_update. Unfitted cells go
+ * as in artis_amd_grid_update. u->clumpfactor must be NULL: the balance uses the clumping factors the solve used, and they become the
+ * cell state's. ARTIS_ERR_ARG unless a thermal solve is valid, was made on the last fit and on the cell state that is still resident
+ * (an artis_amd_set_cellstate or a hand-over since the solve makes it stale; so it does for artis_amd_thermal_rates with rebalance = 1). */
+int artis_amd_grid_update_thermal(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -305,6 +305,17 @@
 #ifndef ARTIS_OPT_DIRECT_COL_HEAT
 #define ARTIS_OPT_DIRECT_COL_HEAT 0 /* artisoptions_classic.h:35 */
 #endif
+/* TEMPERATURE_SOLVER_ACCURACY (artisoptions_classic.h:116): the relative width of the T_e bracket at which the thermal-balance root
+ * search stops (thermalbalance.cc:287). 1e-2 in artisoptions_classic.h and artisoptions_nltewithoutnonthermal.h:119, 1e-3 in the other
+ * four options files (kilonova_lte.h:116, nltenebular.h:123, christinenonthermal.h:121, nltephotospheric_dynamic_ion_range.h:124);
+ * tests/golden/thermal_options_reference.json pins every preset */
+#ifndef ARTIS_OPT_TEMPERATURE_SOLVER_ACCURACY
+#if defined(ARTIS_PRESET_KILONOVA_LTE) || (defined(ARTIS_PRESET_NLTENEBULAR) && !defined(ARTIS_PRESET_NLTEWITHOUTNONTHERMAL))
+#define ARTIS_OPT_TEMPERATURE_SOLVER_ACCURACY 1e-3
+#else
+#define ARTIS_OPT_TEMPERATURE_SOLVER_ACCURACY 1e-2
+#endif
+#endif
 #ifndef ARTIS_OPT_BFCOOLING_USELEVELPOPNOTIONPOP
 #define ARTIS_OPT_BFCOOLING_USELEVELPOPNOTIONPOP 0 /* artisoptions_classic.h:135 */
 #endif
