@@ -433,93 +433,14 @@ inline int sort_lds_grid(int64_t n) {
 #ifndef ARTIS_THERMAL_WAVES
 #define ARTIS_THERMAL_WAVES 4
 #endif
-constexpr int MAX_CHUNKS = 8192;  // >= 256 CUs x 4 waves/SIMD x 4 SIMDs, a multiple of 8
-// before a launch of the kernel of one kind: its own list's counter, the alternate counter and the chunk cursors start at zero
+#include "work_pull.h"  // MAX_CHUNKS, Puller, puller_init(), chunk_at(), pull(): handing the list's indices to the waves
+// before a launch of the kernel of one kind: its own list's counter, the alternate counter and the chunk cursors (and the flag) start at zero
 __global__ void __launch_bounds__(BLOCK) k_launch_reset(int32_t *count, int kind, int32_t *cursors) {
-  for (int i = threadIdx.x; i < MAX_CHUNKS + 1; i += BLOCK) cursors[i] = 0;
+  for (int i = threadIdx.x; i < PULL_SLOTS; i += BLOCK) cursors[i] = 0;
   if (threadIdx.x == 0) {
     count[kind] = 0;
     count[NEXT_NKINDS] = 0;
   }
-}
-
-
-struct Puller {
-  int chunk;           // current chunk
-  int32_t cbeg, cend;  // ... and its range of the list (kept: the bounds cost two 64-bit divisions)
-  int home, cx;        // first position of the search order: (XCD, local index); chunks per XCD
-  int nchunks;
-  bool exhausted;
-};
-__device__ inline int64_t chunk_begin(int32_t n, int c, int nchunks) { return ((int64_t)n * c) / nchunks; }
-// chunk_mode: 0 = one chunk per wave (or fewer, shared in order), 1 = per workgroup, 2 = per COMPUTE UNIT (nchunks == 256):
-// the workgroups that the hardware placed on one CU walk one run of cells together, so the CU's L1 sees a handful of
-// cells. The CU is read from HW_REG_HW_ID (MI355X: 8 XCDs x 4 shader engines x 8 CUs, CU_ID 0..7 or 1..8).
-__device__ inline void puller_init(Puller &q, int32_t n, int nchunks, int chunk_mode = 0) {
-  int xcd = blockIdx.x & 7;
-  // wave / workgroup / CU index within its XCD
-  int local = (chunk_mode == 1) ? (int)(blockIdx.x >> 3) : (int)(blockIdx.x >> 3) * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6);
-  if (chunk_mode == 2) {
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcd = (int)(xcc & 7u);
-    local = (int)(((hwid >> 13) & 3u) * 8u + ((hwid >> 8) & 7u));
-  }
-  q.nchunks = nchunks;
-  q.cx = nchunks >> 3;
-  q.home = xcd * q.cx + (local % q.cx);
-  q.chunk = q.home;
-  q.cbeg = (int32_t)chunk_begin(n, q.chunk, nchunks);
-  q.cend = (int32_t)chunk_begin(n, q.chunk + 1, nchunks);
-  q.exhausted = false;
-}
-// position v of a wave's search order -> chunk: its own XCD's chunks first (from its home chunk, wrapping), then the rest
-__device__ inline int chunk_at(const Puller &q, int v) {
-  const int x0 = (q.home / q.cx) * q.cx;
-  if (v < q.cx) return x0 + ((q.home - x0 + v) % q.cx);
-  return (x0 + v) % q.nchunks;
-}
-// Hands list indices to the lanes with need==true. Returns the index for this lane or -1. Wave-uniform control flow.
-__device__ inline int32_t pull(Puller &q, bool need, int32_t n, int32_t *cursors) {
-  int32_t idx = -1;
-  need = need && !q.exhausted;
-  const unsigned long long mask = __ballot(need);
-  if (mask == 0) return -1;
-  const int lane = threadIdx.x & 63;
-  const int cnt = __popcll(mask);
-  const int prefix = __popcll(mask & ((1ull << lane) - 1ull));
-  const int leader = __ffsll((long long)mask) - 1;
-  const int64_t cbeg = q.cbeg, cend = q.cend;
-  int base = 0;
-  if (lane == leader) base = atomicAdd(&cursors[q.chunk], cnt);
-  base = __shfl(base, leader);
-  const int64_t mine = cbeg + base + prefix;
-  if (need && mine < cend) idx = (int32_t)mine;
-  if (cbeg + base + cnt > cend) {
-    // this chunk is used up: look for one that still has entries, 64 candidates at a time (the unserved lanes ask again).
-    // A cursor only grows, so a stale read can only make a chunk look fuller than it is: the next pull finds out.
-    bool found = false;
-    for (int v0 = 1; v0 < q.nchunks && !found; v0 += 64) {
-      const int v = v0 + lane;
-      bool has = false;
-      int c = 0;
-      if (v < q.nchunks) {
-        c = chunk_at(q, v);
-        const int32_t used = __hip_atomic_load(&cursors[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        has = chunk_begin(n, c, q.nchunks) + used < chunk_begin(n, c + 1, q.nchunks);
-      }
-      const unsigned long long hm = __ballot(has);
-      if (hm != 0) {
-        q.chunk = __shfl(c, __ffsll((long long)hm) - 1);
-        q.cbeg = (int32_t)chunk_begin(n, q.chunk, q.nchunks);
-        q.cend = (int32_t)chunk_begin(n, q.chunk + 1, q.nchunks);
-        found = true;
-      }
-    }
-    if (!found) q.exhausted = true;
-  }
-  return idx;
 }
 // chunks for a list of n entries consumed by `nwaves` waves: one per wave, fewer when the list is short
 inline int chunks_for(int64_t n, int nwaves) {
@@ -640,7 +561,7 @@ __global__ void __launch_bounds__(TB, ARTIS_RPKT_WGS) k_rpkt(Env env, const int3
   long long tprev = clock64();
 #endif
   while (true) {
-    const int32_t idx = pull(q, !have, n, cursors);
+    const int32_t idx = pull(q, !have, cursors);
     if (idx >= 0) {
       pi = list[idx];
       pkt_load(env.P, pi, p);
@@ -787,7 +708,7 @@ __global__ void __launch_bounds__(BLOCK, ARTIS_GAMMA_WAVES) k_gamma(Env env, con
   int steps = 0;
   Pkt p;
   while (true) {
-    const int32_t idx = pull(q, !have, n, cursors);
+    const int32_t idx = pull(q, !have, cursors);
     if (idx >= 0) {
       pi = list[idx];
       pkt_load(env.P, pi, p);
@@ -922,7 +843,7 @@ __global__ void __launch_bounds__(TB, (TABLES_LDS ? 1 : ARTIS_THERMAL_EU)) k_the
   long long tprev = clock64();
 #endif
   while (true) {
-    const int32_t idx = pull(q, !have, n, cursors);
+    const int32_t idx = pull(q, !have, cursors);
     if (idx >= 0) {
       pi = list[idx];
       pkt_load_thermal(env.P, pi, p);  // the hot line only
@@ -938,6 +859,9 @@ __global__ void __launch_bounds__(TB, (TABLES_LDS ? 1 : ARTIS_THERMAL_EU)) k_the
     // units each) while the rest of the GPU idles. In a launch whose successor is large anyway (drain_budget set by the
     // host), a packet then leaves after drain_budget units for that next launch, where its work runs beside a full list.
     // (Where a packet is handed from launch to launch never changes it: budgets are placement, tested.)
+    // BEFORE the list is used up such a launch has no unit budget (the host passes budget = INT_MAX, launch_thermal(); ARTIS_AMD_BUDGET_T_BULK
+    // gives it one): holding the lane costs nothing while the wave's other lanes keep pulling, and the hand-over ends the launch anyway. A budget
+    // there only stored, listed, sorted and loaded a long history again every round, and left it to run alone at the step's end.
 #define ROUND_BEFORE_LEAVE \
     if (!drained && q.exhausted) { \
       drained = true; \
@@ -1065,7 +989,7 @@ __global__ void __launch_bounds__(TB, 1) k_thermal_q(Env env, const int32_t *lis
       const uint32_t actw = has ? Q.act[s] : (uint32_t)(TQ_EMPTY + 3);
       const int act = (int)(actw & 127u) - 3;
       const bool isdone = has && act != TQ_EMPTY;
-      const int32_t idx = pull(q, has && !isdone, n, cursors);
+      const int32_t idx = pull(q, has && !isdone, cursors);
       if (!drained && q.exhausted) {
         drained = true;
         if (lane == 0) __hip_atomic_store(&cursors[MAX_CHUNKS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1945,7 +1869,7 @@ __global__ void __launch_bounds__(TB, (CONT_LDS ? 1 : ARTIS_VPKT_WGS)) k_vpkt(En
     bool have = false;
     VRay ray;
     while (true) {
-      const int32_t idx = pull(q, !have, n, cursors);
+      const int32_t idx = pull(q, !have, cursors);
       if (idx >= 0) have = vray_begin_seed(env, queue[idx / nobs], idx % nobs, ray);
       if (!__any(have)) {
         if (q.exhausted) break;
@@ -2112,7 +2036,7 @@ struct artis_amd_engine {
   SortScratch sort_scratch;                   // the many-keys sort's buffers, allocated with the lists
   bool sort_attr_set = false;                 // k_sort_segments may use its 128 KB of LDS on this engine's device
   int32_t *d_count = nullptr;                 // [NEXT_NKINDS] current-list counts, [NEXT_NKINDS] alternate-list count
-  int32_t *d_cursors = nullptr;               // [MAX_CHUNKS] chunk cursors of the running pull kernel
+  int32_t *d_cursors = nullptr;               // [PULL_SLOTS] chunk cursors of the running pull kernel (work_pull.h)
   int ncu = 256;
   double *d_gamma_ws = nullptr;   // per-packet groundcont_gamma_contr lists (physics.h Env)
   int32_t *d_gamma_gi = nullptr;
@@ -2163,6 +2087,10 @@ struct artis_amd_engine {
   int small_list = 300000;
   int budget_t_small = 0;
   int budget_r_small = 0;
+  // k_thermal's unit budget while its list still has entries, in launches with the hand-over at list exhaustion below (EngineConfig::budget_t_bulk,
+  // ARTIS_AMD_BUDGET_T_BULK; 0 = none). None: the wave's other lanes keep pulling beside a long history and the hand-over ends the launch anyway, so
+  // budget_t there only stored, listed, sorted and loaded such a packet again every round. Launches without hand-over keep budget_t.
+  int budget_t_bulk = 0;
   // ... and after the launch's list is used up (ARTIS_AMD_DRAIN_T; 0 = off), in launches of at least drain_min_list packets
   int drain_t = 48;
   int drain_r = 1;       // ... do_rpkt_step() calls after the r-packet list is used up (ARTIS_AMD_DRAIN_R; 0 = off)
@@ -2216,6 +2144,7 @@ static void apply_config(artis_amd_engine *e, const artis_amd_config &checked) {
   if (e->cfg.tail_given) e->tail_max = e->cfg.tail_threshold;
   if (ARTIS_OPT_VPKT_ON) e->tail_max = 0;  // (see the estimator block: the event queue is sized per split launch)
   if (e->cfg.park_given) e->park_at = e->cfg.tile_park_at;
+  if (e->cfg.bulk_given) e->budget_t_bulk = e->cfg.budget_t_bulk;
 }
 static void trace_config(const artis_amd_engine *e) {
   const EngineConfig &c = e->cfg;
@@ -3075,7 +3004,7 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
   e->d_err = e->d_count + (2 * NEXT_NKINDS);
   e->d_late_bail = e->d_err + 1;  // (k_late's count of waves that gave up waiting: travels with the counters)
   HIP_TRY(hipHostMalloc((void **)&e->h_counts, sizeof(int32_t) * (2 * NEXT_NKINDS + 2), hipHostMallocDefault));
-  HIP_TRY(hipMalloc((void **)&e->d_cursors, sizeof(int32_t) * (MAX_CHUNKS + 1)));  // + the launch's "list used up" flag
+  HIP_TRY(hipMalloc((void **)&e->d_cursors, sizeof(int32_t) * PULL_SLOTS));  // (work_pull.h: the chunk cursors + the launch's "list used up" flag)
   HIP_TRY(hipMalloc((void **)&e->cc.d_fill_cells, sizeof(int32_t) * (size_t)(ncell_all > 0 ? ncell_all : 1)));
   if (e->cc.ntiles > 1) {  // rows for a set of cells at a time: the table of rows, no cell resident yet
     HIP_TRY(hipMalloc((void **)&e->cc.d_krow, sizeof(int32_t) * (size_t)ncell_all));

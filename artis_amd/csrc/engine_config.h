@@ -113,7 +113,12 @@ struct EngineConfig {
   int64_t tile_park_at = 0;
   int keep_line_dpop = -1;         // -1: dropped when that saves tiles; 0: dropped; 1: kept
   bool dpop_strict = false;        // ... kept or the creation fails (asked for through the struct)
-  uint8_t src_budget = 0, src_headroom = 0, src_scratch = 0, src_hot = 0, src_pool = 0, src_tail = 0, src_park = 0, src_dpop = 0;
+  // k_thermal's unit budget BEFORE its list is used up, in launches that hand over at list exhaustion (stage_propagate.h launch_thermal): 0 = none,
+  // a packet keeps its lane while the list lasts (the default); > 0: that many units (the launch's own budget, 2048 or 1024, gives the rule of
+  // before). No struct field: a placement switch like the other budgets (ARTIS_AMD_BUDGET_T_BULK), resolved here with the rest.
+  bool bulk_given = false;
+  int budget_t_bulk = 0;
+  uint8_t src_budget = 0, src_headroom = 0, src_scratch = 0, src_hot = 0, src_pool = 0, src_tail = 0, src_park = 0, src_dpop = 0, src_bulk = 0;
 };
 
 // THE resolution point: a field set in the (checked) struct wins; a field left at "automatic / default" takes its ARTIS_AMD_* variable if that is
@@ -159,6 +164,9 @@ inline EngineConfig resolve_config(const artis_amd_config &c) {
     r.keep_line_dpop = c.keep_line_dpop, r.dpop_strict = c.keep_line_dpop == 1, r.src_dpop = CONFIG_STRUCT;
   } else if (const char *b = std::getenv("ARTIS_AMD_DPOP")) {
     r.keep_line_dpop = std::atoi(b) == 0 ? 0 : 1, r.src_dpop = CONFIG_ENV;
+  }
+  if (const char *b = std::getenv("ARTIS_AMD_BUDGET_T_BULK")) {
+    r.bulk_given = true, r.budget_t_bulk = std::max(0, std::atoi(b)), r.src_bulk = CONFIG_ENV;
   }
   return r;
 }

@@ -226,13 +226,16 @@ struct PropRun {
   int launch_thermal(const int32_t *lst, int32_t nk, const Lists &next) {
     const int bud_t = budget_for(e->budget_t, e->budget_t_small, nk);
     const int drain = drain_for(e->drain_t, bud_t, nk);
+    // k_thermal in a launch with the hand-over (drain < bud_t): no unit budget while the list lasts (budget_t_bulk = 0), a packet leaves for budget
+    // reasons only once the list is used up, after `drain` units. Launches without hand-over, and k_thermal_q, keep bud_t.
+    const int bud_k = (drain < bud_t) ? (e->budget_t_bulk > 0 ? e->budget_t_bulk : INT_MAX) : bud_t;
     const size_t tq_bytes = tq_lds_bytes(TQ_TB, e->Mh.nlevels, e->Mh.nalltrans);
     const bool cold = e->Mh.ncold > 0;  // (kernels built with the on-demand records' look-ups only where the model has cold levels)
     if (cold) e->last.thermal_variants |= ARTIS_AMD_THERMAL_COLD;
     auto launch = [&](auto tb, auto tables_lds, int grid, int nchunks, int chunk_mode) {
       with_flag(cold, [&](auto is_cold) {
         hipLaunchKernelGGL((k_thermal<decltype(tb)::value, decltype(tables_lds)::value, decltype(is_cold)::value>), dim3(grid), dim3(decltype(tb)::value), 0,
-                           s, env, lst, nk, next, e->d_stats, bud_t, e->d_cursors, nchunks, chunk_mode, drain);
+                           s, env, lst, nk, next, e->d_stats, bud_k, e->d_cursors, nchunks, chunk_mode, drain);
       });
     };
     const int grid1024 = (int)std::min<int64_t>(((int64_t)nk + 1023) / 1024, (int64_t)e->ncu);
@@ -277,7 +280,7 @@ struct PropRun {
   int launch_vpkt_followup([[maybe_unused]] int kind) {
 #if ARTIS_OPT_VPKT_ON
     if (kind != NEXT_GAMMA && kind != NEXT_BB) {
-      HIP_TRY(hipMemsetAsync(e->d_cursors, 0, sizeof(int32_t) * (MAX_CHUNKS + 1), s));
+      HIP_TRY(hipMemsetAsync(e->d_cursors, 0, sizeof(int32_t) * PULL_SLOTS, s));
       if (e->vpkt_cont_lds && e->Mh.nbfcontinua <= CONT_LDS_MAX && e->Mh.nbfcontinua > 0)
         hipLaunchKernelGGL((k_vpkt<true, ARTIS_VPKT_TB>), dim3(e->ncu), dim3(ARTIS_VPKT_TB), 0, s, env, e->d_stats, e->d_cursors);
       else
