@@ -799,3 +799,41 @@ def thermal_arrays(ncell: int, nions: int, nbfg: int) -> dict:
                 flags=np.zeros(ncell, np.int32), nne=np.zeros(ncell, np.float32), rates=np.zeros(ncell * THERMAL_NRATES),
                 ion_groundlevelpops=np.zeros(ncell * nions, np.float32), ion_partfuncts=np.zeros(ncell * nions, np.float32),
                 phi=np.zeros(ncell * nions), gamma=np.zeros(max(ncell * nbfg, 1)), corrphotoionrenorm=np.zeros(max(ncell * nbfg, 1)))
+
+
+# bound-free heating coefficients of the thin cells (include/artis_amd.h artis_amd_bfheating_*)
+BFHEAT_RENORM_ONE, BFHEAT_NONFINITE = 1, 2
+BFHEAT_NTOTALS = 3
+BFHEAT_NTIMES = 2
+BFHEAT_TOTALS = ("nodes", "subdivided", "at_depth_cap")
+BFHEAT_KERNELS = ("ground", "levels")
+
+
+class BfheatingParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("TR", _F32P), ("W", _F32P)]
+
+
+class BfheatingResult(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("coeffs", _F64P), ("renorm", _F64P), ("flags", _I32P), ("totals", C.c_int64 * BFHEAT_NTOTALS),
+                ("nfitted", C.c_int64), ("nintegrals", C.c_int64), ("npts_nonempty", C.c_int32), ("nlevels", C.c_int32),
+                ("nbfcontinua_ground", C.c_int32), ("nlevels_with_targets", C.c_int32), ("kernel_ms", C.c_double * BFHEAT_NTIMES)]
+
+
+class Gk61Case(C.Structure):
+    _fields_ = [("which", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double), ("a", C.c_double), ("b", C.c_double), ("tol", C.c_double)]
+
+
+class Gk61Result(C.Structure):
+    _fields_ = [("result", C.c_double), ("error", C.c_double), ("evals", C.c_int64), ("nodes", C.c_int32), ("maxdepth", C.c_int32)]
+
+
+def bfheating_params(TR=None, W=None):
+    """(BfheatingParams, the arrays it points into: keep them alive while it is used); None: a NULL pointer (the last fit's)"""
+    keep = {}
+    p = BfheatingParams(struct_size=C.sizeof(BfheatingParams))
+    for k, v in (("TR", TR), ("W", W)):
+        if v is None:
+            continue
+        keep[k] = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+        setattr(p, k, keep[k].ctypes.data_as(_F32P))
+    return p, keep

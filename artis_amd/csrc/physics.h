@@ -586,9 +586,8 @@ AHD double phixs_threshold(const DevModel &M, int element, int ion, int level, i
 }
 AHD int emtype_continuum(const DevModel &M, int ul, int t) { return -1 - M.level_bflist_start[ul] - t; }  // atomic.h:508
 // photoionisation_crosssection_fromtable atomic.h:201
-AHD float phixs_fromtable(const DevModel &M, const float *xs, double nu_edge, double nu) {
-  const int NP = M.NPHIXSPOINTS;
-  const double INC = M.NPHIXSNUINCREMENT;
+// (the table's grid as three values: a caller that keeps them in registers need not hold the model's address, bf_heating.h)
+AHD float phixs_fromtable_grid(const int NP, const double INC, const double last_phixs_nuovernuedge, const float *xs, double nu_edge, double nu) {
 #if ARTIS_OPT_PHIXS_CLASSIC_NO_INTERPOLATION
   if (nu < nu_edge) return 0.f;
   if (nu == nu_edge) return xs[0];
@@ -608,9 +607,12 @@ AHD float phixs_fromtable(const DevModel &M, const float *xs, double nu_edge, do
     const double fb = ireal - i;
     return (float)(((1. - fb) * a) + (fb * b));
   }
-  const double nu_max_phixs = nu_edge * M.last_phixs_nuovernuedge;
+  const double nu_max_phixs = nu_edge * last_phixs_nuovernuedge;
   return (float)(xs[NP - 1] * pow3(nu_max_phixs / nu));
 #endif
+}
+AHD float phixs_fromtable(const DevModel &M, const float *xs, double nu_edge, double nu) {
+  return phixs_fromtable_grid(M.NPHIXSPOINTS, M.NPHIXSNUINCREMENT, M.last_phixs_nuovernuedge, xs, nu_edge, nu);
 }
 // Partition point of a[0..n) for a predicate that is true on a prefix and false on the rest: the index of the first
 // element for which it is false (n if none), i.e. what std::ranges::upper_bound / lower_bound / partition_point return.

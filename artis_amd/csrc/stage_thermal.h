@@ -285,12 +285,14 @@ TbArgs tb_args(artis_amd_engine *e) {
 }
 
 // what both calls check first, and the heating inputs into the block
-int tb_begin(artis_amd_engine *e, const artis_thermal_params *p, hipStream_t s, const char *call) {
+// dev_bfheat: the coefficients are on the device already (artis_amd_thermal_solve_bfheated), p->bfheatingcoeffs must be NULL then
+int tb_begin(artis_amd_engine *e, const artis_thermal_params *p, hipStream_t s, const char *call, const double *dev_bfheat = nullptr) {
   const std::string who = std::string(call) + ": ";
   if (!e->have_cells) return stage_error(ARTIS_ERR_ARG, who + "no cell state (artis_amd_set_cellstate)");
   if (!e->rf || !e->rf->valid || !e->fit_since_step)
     return stage_error(ARTIS_ERR_ARG, who + "needs an artis_amd_radfield_fit since the last propagation call");
-  if (!p->bfheatingcoeffs) return stage_error(ARTIS_ERR_ARG, who + "bfheatingcoeffs is required");
+  if (dev_bfheat && p->bfheatingcoeffs) return stage_error(ARTIS_ERR_ARG, who + "bfheatingcoeffs must be NULL (the coefficients are the bound-free heating stage's)");
+  if (!dev_bfheat && !p->bfheatingcoeffs) return stage_error(ARTIS_ERR_ARG, who + "bfheatingcoeffs is required");
   const bool dep_host = p->ntlepton_dep || p->dep_alpha || p->dep_spfission;
   if (dep_host && !(p->ntlepton_dep && p->dep_alpha && p->dep_spfission))
     return stage_error(ARTIS_ERR_ARG, who + "ntlepton_dep, dep_alpha and dep_spfission come together or not at all");
@@ -304,7 +306,7 @@ int tb_begin(artis_amd_engine *e, const artis_thermal_params *p, hipStream_t s, 
   TbState *st = e->tb;
   if (tb_slice_bytes(e->Mh) * (BLOCK / 64) > 64 * 1024) return stage_error(ARTIS_ERR_UNSUPPORTED, who + "the per-ion arrays of four cells do not fit 64 KiB of LDS");
   const int64_t n = st->ncell;
-  HIP_TRY(stage_copy(st->d_bfheat, p->bfheatingcoeffs, n * st->nlevels, hipMemcpyHostToDevice, &s));
+  if (!dev_bfheat) HIP_TRY(stage_copy(st->d_bfheat, p->bfheatingcoeffs, n * st->nlevels, hipMemcpyHostToDevice, &s));
   if (dep_host) {
     HIP_TRY(stage_copy(st->d_dep, p->ntlepton_dep, n, hipMemcpyHostToDevice, &s));
     HIP_TRY(stage_copy(st->d_dep ? st->d_dep + n : nullptr, p->dep_alpha, n, hipMemcpyHostToDevice, &s));
@@ -340,15 +342,9 @@ int tb_unsupported(const char *call) {
                                                 ": the thermal balance of the thin cells is the host's");
 }
 
-}  // namespace
-
-extern "C" {
-
-int artis_amd_thermal_solve(artis_amd_engine *e, const artis_thermal_params *p, void *hip_stream) {
-  if (!e || !p) return stage_error(ARTIS_ERR_ARG, "thermal_solve: null engine or parameters");
-#if !ARTIS_TB_SUPPORTED
-  return tb_unsupported("thermal_solve");
-#else
+#if ARTIS_TB_SUPPORTED
+// artis_amd_thermal_solve; dev_bfheat: artis_amd_thermal_solve_bfheated (stage_bfheat.h), the coefficients read where they lie
+int tb_solve(artis_amd_engine *e, const artis_thermal_params *p, void *hip_stream, const double *dev_bfheat) {
   STAGE_STRUCT_SIZE(p, artis_thermal_params, "thermal_solve");
   const bool host_matter = p->rho || p->elem_massfracs || p->elem_meanweight;
   if (host_matter && (!p->rho || !p->elem_massfracs)) return stage_error(ARTIS_ERR_ARG, "thermal_solve: rho and elem_massfracs come together");
@@ -356,7 +352,7 @@ int artis_amd_thermal_solve(artis_amd_engine *e, const artis_thermal_params *p, 
     return stage_error(ARTIS_ERR_ARG, "thermal_solve: this build has USE_CALCULATED_MEANATOMICWEIGHT: elem_meanweight is required");
   if (!host_matter && (!e->decay || !e->decay->valid)) return stage_error(ARTIS_ERR_ARG, "thermal_solve: no matter and no decay update (artis_amd_decay_update)");
   hipStream_t s = (hipStream_t)hip_stream;
-  int rc = tb_begin(e, p, s, "thermal_solve");
+  int rc = tb_begin(e, p, s, "thermal_solve", dev_bfheat);
   if (rc != ARTIS_OK) return rc;
   TbState *st = e->tb;
   st->valid = st->solved = false;
@@ -379,6 +375,7 @@ int artis_amd_thermal_solve(artis_amd_engine *e, const artis_thermal_params *p, 
   st->nfitted = (int64_t)list.size();
   HIP_TRY(stage_copy(st->d_list, list.data(), st->nfitted, hipMemcpyHostToDevice, &s));
   TbArgs a = tb_args(e);
+  if (dev_bfheat) a.A.bfheatingcoeffs = dev_bfheat;
   a.A.rho = st->d_rho;
   a.A.massfrac = st->d_massfrac;
   a.A.meanweight_cell = ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT ? st->d_meanweight : nullptr;
@@ -432,6 +429,19 @@ int artis_amd_thermal_solve(artis_amd_engine *e, const artis_thermal_params *p, 
   st->cellstate_serial = e->cellstate_serial;
   st->valid = st->solved = true;
   return ARTIS_OK;
+}
+#endif
+
+}  // namespace
+
+extern "C" {
+
+int artis_amd_thermal_solve(artis_amd_engine *e, const artis_thermal_params *p, void *hip_stream) {
+  if (!e || !p) return stage_error(ARTIS_ERR_ARG, "thermal_solve: null engine or parameters");
+#if !ARTIS_TB_SUPPORTED
+  return tb_unsupported("thermal_solve");
+#else
+  return tb_solve(e, p, hip_stream, nullptr);
 #endif
 }
 

@@ -161,6 +161,75 @@ AHD double tb_log(double x) {
   const double dk = k;
   return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
 }
+// exp(x) - 1 for the bound-free heating integrand (bf_heating.h): the rational form and coefficients of fdlibm's s_expm1.c (same
+// notice as above; Copyright (C) 1993 by Sun Microsystems, Inc.), the ranges chosen by comparing values, below 1 ulp
+AHD double tb_expm1(double x) {
+  if (x != x) return x;
+  if (x > 709.782712893383973096) return (double)INFINITY;
+  if (x < -38.816242111356935) return -1.;  // 56 ln2: exp(x) is below half an ulp of 1
+  const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10, invln2 = 1.44269504088896338700e+00;
+  const double Q1 = -3.33333333333331316428e-02, Q2 = 1.58730158725481460165e-03, Q3 = -7.93650757867487942473e-05,
+               Q4 = 4.00821782732936239552e-06, Q5 = -2.01099218183624371326e-07;
+  const double ax = (x < 0) ? -x : x;
+  int k = 0;
+  double c = 0.;
+  if (ax > 0.34657359027997264) {  // 0.5 ln2
+    double hi, lo;
+    if (ax < 1.0397207708399179) {  // 1.5 ln2
+      if (x > 0) {
+        hi = x - ln2_hi;
+        lo = ln2_lo;
+        k = 1;
+      } else {
+        hi = x + ln2_hi;
+        lo = -ln2_lo;
+        k = -1;
+      }
+    } else {
+      k = (int)(invln2 * x + ((x < 0) ? -0.5 : 0.5));
+      const double t = k;
+      hi = x - t * ln2_hi;
+      lo = t * ln2_lo;
+    }
+    x = hi - lo;
+    c = (hi - x) - lo;
+  } else if (ax < 5.551115123125783e-17) {  // 2^-54
+    return x;
+  }
+  const double hfx = 0.5 * x;
+  const double hxs = x * hfx;
+  const double r1 = 1. + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
+  double t = 3. - r1 * hfx;
+  double e = hxs * ((r1 - t) / (6. - x * t));
+  if (k == 0) return x - (x * e - hxs);
+  e = (x * (e - c) - c);
+  e = e - hxs;
+  if (k == -1) return 0.5 * (x - e) - 0.5;
+  if (k == 1) {
+    if (x < -0.25) return -2. * (e - (x + 0.5));
+    return 1. + 2. * (x - e);
+  }
+  if (k <= -2 || k > 56) {  // exp(x) - 1
+    double y = 1. - (e - x);
+    if (k == 1024)
+      y = y * 2. * pow2i(1023);
+    else
+      y = y * pow2i(k);
+    return y - 1.;
+  }
+  double y;
+  if (k < 20) {
+    t = 1. - pow2i(-k);
+    y = t - (e - x);
+    y = y * pow2i(k);
+  } else {
+    t = pow2i(-k);
+    y = x - (e + t);
+    y = y + 1.;
+    y = y * pow2i(k);
+  }
+  return y;
+}
 // col_excitation_ratecoeff macroatom.cc:750 (physics.h col_exc) with the stage's exp and log
 AHD double tb_col_exc(const DevModel &M, const float T_e, const float cnne, const double epsilon_trans, const double gu, const double gl, const int ati) {
   const float cs = M.alltrans_coll_str[ati];

@@ -84,6 +84,10 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_thermal_rates.argtypes = [C.c_void_p, C.POINTER(abi.ThermalParams), C.c_void_p, C.c_int, C.c_void_p]
     L.artis_amd_thermal_download.argtypes = [C.c_void_p, C.POINTER(abi.ThermalResult)]
     L.artis_amd_grid_update_thermal.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
+    L.artis_amd_bfheating_update.argtypes = [C.c_void_p, C.POINTER(abi.BfheatingParams), C.c_void_p]
+    L.artis_amd_bfheating_download.argtypes = [C.c_void_p, C.POINTER(abi.BfheatingResult)]
+    L.artis_amd_thermal_solve_bfheated.argtypes = [C.c_void_p, C.POINTER(abi.ThermalParams), C.c_void_p]
+    L.artis_amd_debug_gk61.argtypes = [C.c_int32, C.POINTER(abi.Gk61Case), C.POINTER(abi.Gk61Result)]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -115,6 +119,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_grid_update_deposited",
     "artis_amd_packet_init_setup", "artis_amd_packet_init", "artis_amd_packet_init_download",
     "artis_amd_thermal_solve", "artis_amd_thermal_rates", "artis_amd_thermal_download", "artis_amd_grid_update_thermal",
+    "artis_amd_bfheating_update", "artis_amd_bfheating_download", "artis_amd_thermal_solve_bfheated", "artis_amd_debug_gk61",
     "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
     "artis_amd_sizeof_plan", "artis_amd_engine_plan",
 ]
@@ -135,6 +140,19 @@ def plan(model: abi.Model, config=None, device: int = 0, preset: str = "classic"
     if rc != 0:
         raise EngineError(f"artis_amd error {rc}: {L.artis_amd_last_error().decode()}")
     return abi.struct_dict(out)
+
+
+def debug_gk61(cases, preset: str = "classic") -> list:
+    """artis_amd_debug_gk61: the adaptive 61-point Gauss-Kronrod integrator on the analytic integrands of tests/golden/gk61_reference.json,
+    on the current device, one lane per case. cases: (which, p, a, b, tol); returns a dict per case (result, error, evals, nodes, maxdepth)."""
+    L = load_library(preset=preset)
+    n = len(cases)
+    arr = (abi.Gk61Case * max(n, 1))(*[abi.Gk61Case(which=int(w), p=float(p), a=float(a), b=float(b), tol=float(tol)) for w, p, a, b, tol in cases])
+    out = (abi.Gk61Result * max(n, 1))()
+    rc = L.artis_amd_debug_gk61(n, arr, out)
+    if rc != 0:
+        raise EngineError(f"artis_amd error {rc}: {L.artis_amd_last_error().decode()}")
+    return [{k: getattr(out[i], k) for k, _ in abi.Gk61Result._fields_} for i in range(n)]
 
 
 class Engine:
@@ -472,6 +490,45 @@ class Engine:
         decay_update's; the deposition inputs None: the last deposition_update's. Returns the download."""
         p, keep = abi.thermal_params(bfheatingcoeffs, rho, elem_massfracs, elem_meanweight, ntlepton_dep, dep_alpha, dep_spfission, clumpfactor)
         self._check(self.L.artis_amd_thermal_solve(self.h, C.byref(p), C.c_void_p(stream)))
+        del keep
+        return self.thermal_download()
+
+    # bound-free heating coefficients of the thin cells (include/artis_amd.h artis_amd_bfheating_*)
+    def bfheating_update(self, TR=None, W=None, stream: int = 0) -> dict:
+        """The bound-free heating coefficients [ncell, nlevels] of every cell the last radiation-field fit has fitted, renormalised, on
+        the device. TR, W [ncell] None: the fit's; given: those instead in the levels' integrals. Returns the download."""
+        p, keep = abi.bfheating_params(TR, W)
+        self._check(self.L.artis_amd_bfheating_update(self.h, C.byref(p), C.c_void_p(stream)))
+        del keep
+        return self.bfheating_download()
+
+    def bfheating_download(self, arrays: bool = True) -> dict:
+        """"coeffs" [ncell, nlevels], "renorm" [ncell, nbfcontinua_ground], "flags" [ncell] (abi.BFHEAT_*), "totals" as a dict over
+        abi.BFHEAT_TOTALS, "nfitted", "nintegrals", "nlevels_with_targets" and "kernel_ms" as a dict over abi.BFHEAT_KERNELS;
+        arrays=False: only those"""
+        info = abi.BfheatingResult(struct_size=C.sizeof(abi.BfheatingResult))
+        self._check(self.L.artis_amd_bfheating_download(self.h, C.byref(info)))  # sizes first
+        n, nl, g = info.npts_nonempty, info.nlevels, info.nbfcontinua_ground
+        out = {}
+        if arrays:
+            out = dict(coeffs=np.zeros(max(n * nl, 1)), renorm=np.zeros(max(n * g, 1)), flags=np.zeros(max(n, 1), np.int32))
+            types = dict(abi.BfheatingResult._fields_)
+            for k, v in out.items():
+                setattr(info, k, v.ctypes.data_as(types[k]))
+            self._check(self.L.artis_amd_bfheating_download(self.h, C.byref(info)))
+            out["coeffs"] = out["coeffs"][: n * nl].reshape(n, nl)
+            out["renorm"] = out["renorm"][: n * g].reshape(n, g)
+            out["flags"] = out["flags"][:n]
+        out.update(totals={k: int(info.totals[i]) for i, k in enumerate(abi.BFHEAT_TOTALS)}, nfitted=int(info.nfitted),
+                   nintegrals=int(info.nintegrals), nlevels_with_targets=int(info.nlevels_with_targets),
+                   kernel_ms={k: float(info.kernel_ms[i]) for i, k in enumerate(abi.BFHEAT_KERNELS)})
+        return out
+
+    def thermal_solve_bfheated(self, rho=None, elem_massfracs=None, elem_meanweight=None, ntlepton_dep=None, dep_alpha=None,
+                               dep_spfission=None, clumpfactor=None, stream: int = 0) -> dict:
+        """thermal_solve with the coefficients of the last bfheating_update, read where they lie on the device. Returns the download."""
+        p, keep = abi.thermal_params(None, rho, elem_massfracs, elem_meanweight, ntlepton_dep, dep_alpha, dep_spfission, clumpfactor)
+        self._check(self.L.artis_amd_thermal_solve_bfheated(self.h, C.byref(p), C.c_void_p(stream)))
         del keep
         return self.thermal_download()
 

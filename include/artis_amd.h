@@ -1076,7 +1076,8 @@ int artis_amd_packet_init_download(artis_amd_engine *eng, artis_packet_init_resu
  * continuum (calculate_iongamma_per_gspop ratecoeff.cc:926), the partition functions at the fit's T_J and the T_e of the thermal
  * balance (call_T_e_finder thermalbalance.cc:258: a TOMS 748 root of heating - cooling in [MINTEMP, MAXTEMP], every evaluation with
  * its own ion balance; damped to [0.5, 2] x the resident T_e). The bound-free heating coefficients (calculate_bfheatingcoeffs, with
- * their renormalisation applied) come from the host. Builds with LTEPOP_EXCITATION_USE_TJ, USE_LUT_PHOTOION, without NT_ON,
+ * their renormalisation applied) come from the host, or from artis_amd_bfheating_update below without leaving the device
+ * (artis_amd_thermal_solve_bfheated). Builds with LTEPOP_EXCITATION_USE_TJ, USE_LUT_PHOTOION, without NT_ON,
  * DIRECT_COL_HEAT and NLTE populations (classic and its variants); every other build: ARTIS_ERR_UNSUPPORTED, the text names the option.
  * A rate is summed by the 64 lanes of a wave in a fixed order (artis_amd/csrc/thermal_balance.h): bitwise reproducible. */
 #define ARTIS_THERMAL_BRACKETED 256     /* a sign change over [MINTEMP, MAXTEMP]: the root search ran */
@@ -1143,6 +1144,57 @@ int artis_amd_thermal_download(artis_amd_engine *eng, artis_thermal_result *out)
  * cell state's. ARTIS_ERR_ARG unless a thermal solve is valid, was made on the last fit and on the cell state that is still resident
  * (an artis_amd_set_cellstate or a hand-over since the solve makes it stale; so it does for artis_amd_thermal_rates with rebalance = 1). */
 int artis_amd_grid_update_thermal(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream);
+
+/* ---- bound-free heating coefficients of the thin cells ---------------------------------------
+ * calculate_bfheatingcoeffs (thermalbalance.cc:217) with the bfheatingestimator renormalisation in front of it (update_grid.cc:412-443)
+ * on the device, for the cells the last radiation-field fit has fitted: one adaptive 61-point Gauss-Kronrod integral
+ * (gauss_kronrod_integrate<61>, depth 15, 1e-3) per (cell, photoionisation target) and one per (cell, ground continuum). The ground
+ * integrals read the RESIDENT T_R and W (the reference renormalises before fit_parameters), the levels' integrals the fit's. Rules:
+ * artis_amd/csrc/bf_heating.h; the same builds as the thermal balance, every other: ARTIS_ERR_UNSUPPORTED. Bitwise reproducible. */
+#define ARTIS_BFHEAT_RENORM_ONE 1 /* a ground continuum of the cell could not be renormalised (integral not > 0, ratio not finite): 1 */
+#define ARTIS_BFHEAT_NONFINITE 2  /* a coefficient of the cell is not finite (the call refuses the block) */
+#define ARTIS_BFHEAT_NTOTALS 3
+#define ARTIS_BFHEAT_NTIMES 2
+typedef struct artis_bfheating_params {
+  int64_t struct_size; /* sizeof(artis_bfheating_params) */
+  /* [npts_nonempty] each, together or not at all. NULL: the last fit's T_R and W. Given: those instead, in the levels' integrals
+   * (a host with its own fit) */
+  const float *TR, *W;
+} artis_bfheating_params;
+typedef struct artis_bfheating_result {
+  int64_t struct_size; /* sizeof(artis_bfheating_result) */
+  /* host arrays to fill; NULL: skip */
+  double *coeffs;  /* [npts_nonempty*nlevels] bfheatingcoeffs, renormalised; +0 in unfitted cells and for levels without targets */
+  double *renorm;  /* [npts_nonempty*nbfcontinua_ground] the renormalisation factors; +0 in unfitted cells and places no ion has */
+  int32_t *flags;  /* [npts_nonempty] ARTIS_BFHEAT_* */
+  /* reported */
+  int64_t totals[ARTIS_BFHEAT_NTOTALS]; /* 61-point nodes evaluated, integrals that subdivided, integrals that reached depth 15 */
+  int64_t nfitted, nintegrals;
+  int32_t npts_nonempty, nlevels, nbfcontinua_ground, nlevels_with_targets;
+  double kernel_ms[ARTIS_BFHEAT_NTIMES]; /* HIP-event time: [0] k_bfh_ground, [1] k_bfh_levels (all its launches) */
+} artis_bfheating_result;
+/* The update on hip_stream (synchronous). Needs a cell state and an artis_amd_radfield_fit since the last propagation call (its flags,
+ * and the estimators' normalisation). Leaves estimators, packets, counters and the resident cell state untouched; remembers the fit and
+ * the cell state it was made on. A coefficient that is not finite: ARTIS_ERR_NOTCONVERGED with the count in the text, nothing valid. */
+int artis_amd_bfheating_update(artis_amd_engine *eng, const artis_bfheating_params *params, void *hip_stream);
+/* Copy the results to the host (sizes in the reported fields even when every pointer is NULL). */
+int artis_amd_bfheating_download(artis_amd_engine *eng, artis_bfheating_result *out);
+/* artis_amd_thermal_solve with the coefficients of the last artis_amd_bfheating_update, read where they lie on the device:
+ * params->bfheatingcoeffs must be NULL. ARTIS_ERR_ARG unless that update was made on the last fit and on the cell state that is still
+ * resident (as artis_amd_grid_update_thermal asks of the solve). */
+int artis_amd_thermal_solve_bfheated(artis_amd_engine *eng, const artis_thermal_params *params, void *hip_stream);
+/* Test hook: gauss_kronrod_integrate<61>(f, a, b, 15, tol, &error) of the analytic integrands of tests/golden/gk61_reference.json
+ * (artis_amd/csrc/bf_heating.h Gk61TestFn) on the current device, one lane per case, so that the subdividing walk runs there. */
+typedef struct artis_gk61_case {
+  int32_t which, reserved;
+  double p, a, b, tol;
+} artis_gk61_case;
+typedef struct artis_gk61_result {
+  double result, error;
+  int64_t evals;
+  int32_t nodes, maxdepth;
+} artis_gk61_result;
+int artis_amd_debug_gk61(int32_t ncases, const artis_gk61_case *cases, artis_gk61_result *out);
 
 #ifdef __cplusplus
 }
