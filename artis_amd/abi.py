@@ -837,3 +837,17 @@ def bfheating_params(TR=None, W=None):
         keep[k] = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
         setattr(p, k, keep[k].ctypes.data_as(_F32P))
     return p, keep
+
+
+# rate-coefficient tables (include/artis_amd.h artis_amd_ratecoeff_*)
+RATECOEFF_BAD_ALPHA_SP, RATECOEFF_BAD_GAMMACORR, RATECOEFF_BAD_BFCOOLING, RATECOEFF_BAD_SAHAFACT = 1, 2, 4, 8
+
+
+class RatecoeffRequest(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("install", C.c_int32), ("reserved", C.c_int32), ("items_per_launch", C.c_int64)]
+
+
+class RatecoeffStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("integrals", C.c_int64), ("nodes", C.c_int64), ("at_depth_cap", C.c_int64), ("flagged", C.c_int64),
+                ("first_flagged", C.c_int64), ("nbfcontinua", C.c_int64), ("ncovered", C.c_int64), ("tablesize", C.c_int32), ("ntables", C.c_int32),
+                ("kernel_ms", C.c_double)]

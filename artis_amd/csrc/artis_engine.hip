@@ -35,6 +35,7 @@
 #include "packet_init.h"
 #include "thermal_balance.h"
 #include "bf_heating.h"
+#include "ratecoeff_tables.h"
 #include "spectra.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -1908,6 +1909,8 @@ struct TbState;
 void tb_free(TbState *st);
 struct BfhState;
 void bfh_free(BfhState *st);
+struct RcState;
+void rc_free(RcState *st);
 
 }  // namespace
 
@@ -1982,6 +1985,7 @@ struct artis_amd_engine {
   PinitState *pinit = nullptr;  // artis_amd_packet_init*: nothing until artis_amd_packet_init_setup
   TbState *tb = nullptr;        // artis_amd_thermal_*: nothing until the first call
   BfhState *bfh = nullptr;      // artis_amd_bfheating_*: nothing until the first call
+  RcState *rc = nullptr;        // artis_amd_ratecoeff_*: nothing until the first call
   uint64_t cellstate_serial = 0;  // counts the changes of the resident cell state (artis_amd_set_cellstate, the hand-over of artis_amd_grid_update*)
   bool fit_since_step = false;  // an artis_amd_radfield_fit since the last propagation call (artis_amd_grid_update use_fit)
   ModelOwned own;
@@ -3070,6 +3074,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   pinit_free(e->pinit);
   tb_free(e->tb);
   bfh_free(e->bfh);
+  rc_free(e->rc);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->cc.d_krow, e->cc.d_fill_cells, e->cc.d_waiting,
                   e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts};
@@ -3660,3 +3665,4 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 #include "stage_packet_init.h"
 #include "stage_thermal.h"
 #include "stage_bfheat.h"
+#include "stage_ratecoeff.h"

@@ -88,6 +88,8 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_bfheating_download.argtypes = [C.c_void_p, C.POINTER(abi.BfheatingResult)]
     L.artis_amd_thermal_solve_bfheated.argtypes = [C.c_void_p, C.POINTER(abi.ThermalParams), C.c_void_p]
     L.artis_amd_debug_gk61.argtypes = [C.c_int32, C.POINTER(abi.Gk61Case), C.POINTER(abi.Gk61Result)]
+    L.artis_amd_ratecoeff_compute.argtypes = [C.c_void_p, C.POINTER(abi.RatecoeffRequest)]
+    L.artis_amd_ratecoeff_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.RatecoeffStats)]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -120,6 +122,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_packet_init_setup", "artis_amd_packet_init", "artis_amd_packet_init_download",
     "artis_amd_thermal_solve", "artis_amd_thermal_rates", "artis_amd_thermal_download", "artis_amd_grid_update_thermal",
     "artis_amd_bfheating_update", "artis_amd_bfheating_download", "artis_amd_thermal_solve_bfheated", "artis_amd_debug_gk61",
+    "artis_amd_ratecoeff_compute", "artis_amd_ratecoeff_download",
     "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
     "artis_amd_sizeof_plan", "artis_amd_engine_plan",
 ]
@@ -531,6 +534,30 @@ class Engine:
         self._check(self.L.artis_amd_thermal_solve_bfheated(self.h, C.byref(p), C.c_void_p(stream)))
         del keep
         return self.thermal_download()
+
+    # rate-coefficient tables from the cross-sections (include/artis_amd.h artis_amd_ratecoeff_*)
+    def ratecoeff_tables(self, install: bool = False, items_per_launch: int = 0) -> dict:
+        """artis_amd_ratecoeff_compute and the download: "spontrecombcoeffs", "bfcooling_coeffs" and (builds with USE_LUT_PHOTOION; else
+        None) "corrphotoioncoeffs" as [nbfcontinua, TABLESIZE], "flags" alike (abi.RATECOEFF_*), and the counts of artis_ratecoeff_stats.
+        install: copy the tables over the model's on the device (set-up phase only). A flagged entry raises; ratecoeff_download() still
+        shows the tables and flags."""
+        req = abi.RatecoeffRequest(struct_size=C.sizeof(abi.RatecoeffRequest), install=int(bool(install)), items_per_launch=int(items_per_launch))
+        self._check(self.L.artis_amd_ratecoeff_compute(self.h, C.byref(req)))
+        return self.ratecoeff_download()
+
+    def ratecoeff_download(self) -> dict:
+        stats = abi.RatecoeffStats(struct_size=C.sizeof(abi.RatecoeffStats))
+        self._check(self.L.artis_amd_ratecoeff_download(self.h, None, None, None, None, C.byref(stats)))  # sizes first
+        shape = (int(stats.nbfcontinua), int(stats.tablesize))
+        n = max(shape[0] * shape[1], 1)
+        spont, cool, flags = np.zeros(n), np.zeros(n), np.zeros(n, np.int32)
+        gamma = np.zeros(n) if stats.ntables == 3 else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self.L.artis_amd_ratecoeff_download(self.h, ptr(spont), ptr(gamma), ptr(cool), ptr(flags), C.byref(stats)))
+        cut = lambda a: None if a is None else a[: shape[0] * shape[1]].reshape(shape)
+        out = dict(spontrecombcoeffs=cut(spont), corrphotoioncoeffs=cut(gamma), bfcooling_coeffs=cut(cool), flags=cut(flags))
+        out.update({k: v for k, v in abi.struct_dict(stats).items() if k != "struct_size"})
+        return out
 
     def thermal_rates(self, bfheatingcoeffs, Te=None, rebalance: bool = False, ntlepton_dep=None, dep_alpha=None, dep_spfission=None,
                       stream: int = 0) -> dict:

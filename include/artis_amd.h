@@ -1196,6 +1196,43 @@ typedef struct artis_gk61_result {
 } artis_gk61_result;
 int artis_amd_debug_gk61(int32_t ncases, const artis_gk61_case *cases, artis_gk61_result *out);
 
+/* ---- rate-coefficient tables -----------------------------------------------------------------
+ * precalculate_rate_coefficient_integrals (ratecoeff.cc:143-233) on the device: spontrecombcoeffs, bfcooling_coeffs and, in builds with
+ * USE_LUT_PHOTOION, corrphotoioncoeffs, [nbfcontinua][TABLESIZE] each, from the model's cross-section tables; one adaptive 61-point
+ * Gauss-Kronrod integral (depth 15, 1e-3) per table and entry. Covered: ions 0 .. nions-2 of every element, levels below
+ * nlevels_ionising, every target, at (level_bflist_start[level] + target) * TABLESIZE + temperature index; every other element is +0.
+ * Rules: artis_amd/csrc/ratecoeff_tables.h; every build. Bitwise reproducible. Not built: the calibration to a recombination-rate file
+ * (read_recombrate_file / scale_level_phixs multiply the finished tables): a host that calibrates keeps handing its tables in. */
+#define ARTIS_RATECOEFF_BAD_ALPHA_SP 1  /* the entry's alpha_sp is negative or not finite (the reference asserts) */
+#define ARTIS_RATECOEFF_BAD_GAMMACORR 2 /* ... its gammacorr is not >= 0 */
+#define ARTIS_RATECOEFF_BAD_BFCOOLING 4 /* ... its bfcooling coefficient is negative or not finite */
+#define ARTIS_RATECOEFF_BAD_SAHAFACT 8  /* ... its modified_sahafact is negative or not finite */
+typedef struct artis_ratecoeff_request {
+  int64_t struct_size; /* sizeof(artis_ratecoeff_request) */
+  int32_t install;     /* 1: copy the tables over the model's on the device (set-up phase only, see below); 0: compute only */
+  int32_t reserved;
+  int64_t items_per_launch; /* entries (continuum x temperature) per kernel launch; 0: the default */
+} artis_ratecoeff_request;
+typedef struct artis_ratecoeff_stats {
+  int64_t struct_size; /* sizeof(artis_ratecoeff_stats) */
+  int64_t integrals, nodes, at_depth_cap; /* integrals taken, 61-point nodes evaluated, integrals that reached depth 15 */
+  int64_t flagged, first_flagged;         /* entries with a flag; the first one's index (-1: none) */
+  int64_t nbfcontinua, ncovered;          /* rows of a table; rows the reference's loops write */
+  int32_t tablesize, ntables;             /* TABLESIZE; 3 with USE_LUT_PHOTOION, else 2 */
+  double kernel_ms;                       /* HIP-event time of all launches of k_rc_tables */
+} artis_ratecoeff_stats;
+/* Compute the tables (synchronous, on the null stream); the block is allocated at the first call. An entry the reference would
+ * assert on is flagged: with any, ARTIS_ERR_NOTCONVERGED naming the first and the count, and nothing is installed (the download still
+ * shows tables and flags). install = 1 is allowed only while the engine is being set up -- no artis_amd_set_cellstate or hand-over yet,
+ * and the ion balance's ion_alpha_sp table not made: the pairs' coefficients of the cell cache, the cooling lists and ion_alpha_sp are
+ * all derived from the tables after that; otherwise ARTIS_ERR_ARG saying which. Creation reads only the tables' addresses, so a host
+ * that installs may hand in placeholders (zeros). Without install the engine's model, cell state, packets and estimators are untouched. */
+int artis_amd_ratecoeff_compute(artis_amd_engine *eng, const artis_ratecoeff_request *request);
+/* Copy the last computed tables ([nbfcontinua*TABLESIZE] doubles each), the per-entry flags ([nbfcontinua*TABLESIZE], ARTIS_RATECOEFF_*)
+ * and the counts to the host; any pointer may be NULL. A non-NULL corrphotoion in a build without USE_LUT_PHOTOION: ARTIS_ERR_ARG. */
+int artis_amd_ratecoeff_download(artis_amd_engine *eng, double *spont, double *corrphotoion, double *bfcooling, int32_t *flags,
+                                 artis_ratecoeff_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
