@@ -851,3 +851,20 @@ class RatecoeffStats(C.Structure):
     _fields_ = [("struct_size", C.c_int64), ("integrals", C.c_int64), ("nodes", C.c_int64), ("at_depth_cap", C.c_int64), ("flagged", C.c_int64),
                 ("first_flagged", C.c_int64), ("nbfcontinua", C.c_int64), ("ncovered", C.c_int64), ("tablesize", C.c_int32), ("ntables", C.c_int32),
                 ("kernel_ms", C.c_double)]
+
+
+# photoionisation coefficients of builds without USE_LUT_PHOTOION (include/artis_amd.h artis_amd_set_cellstate_photoion)
+PHOTOION_NONFINITE = 1
+PHOTOION_SRC_ESTIMATOR, PHOTOION_SRC_INTEGRAL = 1, 2
+PHOTOION_NTOTALS = 5
+PHOTOION_TOTALS = ("from_estimators", "integrals", "nodes", "at_depth_cap", "nonfinite")
+
+
+class PhotoionParams(C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("use_bf_estimators", C.c_int32), ("bfrate_normed", _F32P), ("cells_per_launch", C.c_int32)]
+
+
+class PhotoionResult(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("coeff", _F64P), ("source", C.POINTER(C.c_uint8)), ("flags", _I32P),
+                ("totals", C.c_int64 * PHOTOION_NTOTALS), ("npts_nonempty", C.c_int32), ("nphixstargets_total", C.c_int32),
+                ("nbfcontinua", C.c_int32), ("nbfestim", C.c_int32), ("kernel_ms", C.c_double)]

@@ -9,8 +9,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libartis_amd.so")
-SOURCES = ["artis_engine.hip", "physics.h", "tables.h", "model_build.h", "engine_config.h", "cache_residency.h", "cellcache_kernels.h", "spectra.h", "radfield_fit.h", "ion_balance.h", "decay_update.h", "deposition.h", "packet_init.h", "thermal_balance.h", "bf_heating.h", "ratecoeff_tables.h",
-           "stage_cellcache.h", "stage_propagate.h", "stage_common.h", "stage_spectra.h", "stage_radfield.h", "stage_ionbal.h", "stage_decay.h", "stage_deposition.h", "stage_packet_init.h", "stage_thermal.h", "stage_bfheat.h", "stage_ratecoeff.h", "rpkt_round.inc", "thermal_round.inc", "work_pull.h"]
+SOURCES = ["artis_engine.hip", "physics.h", "tables.h", "model_build.h", "engine_config.h", "cache_residency.h", "cellcache_kernels.h", "spectra.h", "radfield_fit.h", "ion_balance.h", "decay_update.h", "deposition.h", "packet_init.h", "thermal_balance.h", "bf_heating.h", "ratecoeff_tables.h", "photoion.h",
+           "stage_cellcache.h", "stage_propagate.h", "stage_common.h", "stage_spectra.h", "stage_radfield.h", "stage_ionbal.h", "stage_decay.h", "stage_deposition.h", "stage_packet_init.h", "stage_thermal.h", "stage_bfheat.h", "stage_ratecoeff.h", "stage_photoion.h", "rpkt_round.inc", "thermal_round.inc", "work_pull.h"]
 # -ffp-contract=off: the operation order of physics.h is part of the parity contract (no FMA contraction).
 # -munsafe-fp-atomics: estimator adds become global_atomic_add_f64, not compare-and-swap loops.
 # -fno-slp-vectorize: with SLP vectorisation on, hipcc 7.2 packs the four int32 of a packet's hot line that follow each other

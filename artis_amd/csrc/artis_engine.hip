@@ -36,6 +36,7 @@
 #include "thermal_balance.h"
 #include "bf_heating.h"
 #include "ratecoeff_tables.h"
+#include "photoion.h"
 #include "spectra.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -1911,6 +1912,8 @@ struct BfhState;
 void bfh_free(BfhState *st);
 struct RcState;
 void rc_free(RcState *st);
+struct PiState;
+void pi_free(PiState *st);
 
 }  // namespace
 
@@ -1986,6 +1989,8 @@ struct artis_amd_engine {
   TbState *tb = nullptr;        // artis_amd_thermal_*: nothing until the first call
   BfhState *bfh = nullptr;      // artis_amd_bfheating_*: nothing until the first call
   RcState *rc = nullptr;        // artis_amd_ratecoeff_*: nothing until the first call
+  PiState *pi = nullptr;        // artis_amd_set_cellstate_photoion: nothing until the first call
+  double *pi_coeff = nullptr;   // ... its coefficients [cell][nphixstargets_total] among cell_allocs (null: the cell state is not of that call)
   uint64_t cellstate_serial = 0;  // counts the changes of the resident cell state (artis_amd_set_cellstate, the hand-over of artis_amd_grid_update*)
   bool fit_since_step = false;  // an artis_amd_radfield_fit since the last propagation call (artis_amd_grid_update use_fit)
   ModelOwned own;
@@ -3075,6 +3080,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   tb_free(e->tb);
   bfh_free(e->bfh);
   rc_free(e->rc);
+  pi_free(e->pi);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->cc.d_krow, e->cc.d_fill_cells, e->cc.d_waiting,
                   e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts};
@@ -3085,14 +3091,18 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   delete e;
 }
 
-int artis_amd_set_cellstate(artis_amd_engine *e, const artis_cellstate *cells, const artis_timestep *ts) {
-  if (!e || !cells || !ts) {
-    g_last_error = "null argument";
-    return ARTIS_ERR_ARG;
-  }
+}  // extern "C"
+
+namespace {
+
+// artis_amd_set_cellstate in two halves, shared with artis_amd_set_cellstate_photoion (stage_photoion.h), which computes
+// corrphotoioncoeff between them. The first: the uploads and what the build's options need from the host; corrphotoioncoeff_follows:
+// the caller makes that array on the device before cellstate_finish.
+int cellstate_upload(artis_amd_engine *e, const artis_cellstate *cells, const artis_timestep *ts, const bool corrphotoioncoeff_follows) {
   HIP_TRY(hipSetDevice(e->device));
   e->have_cells = false;  // until every array of the new state is resident
   free_all(e->cell_allocs);
+  e->pi_coeff = nullptr;
   const DevModel &h = e->Mh;
   DevCells hc = make_host_cells_view(*cells);
   std::vector<float> zero_ffegrp;
@@ -3122,7 +3132,7 @@ int artis_amd_set_cellstate(artis_amd_engine *e, const artis_cellstate *cells, c
   e->C.nt_ionratecoeff = nullptr;
   e->C.nt_ionenrate_cum = nullptr;
   // what the options this library was built with need from the host
-  if (!ARTIS_OPT_USE_LUT_PHOTOION && h.nphixstargets_total > 0 && !e->C.corrphotoioncoeff) {
+  if (!ARTIS_OPT_USE_LUT_PHOTOION && h.nphixstargets_total > 0 && !e->C.corrphotoioncoeff && !corrphotoioncoeff_follows) {
     g_last_error = "this build has USE_LUT_PHOTOION off: artis_cellstate.corrphotoioncoeff is required";
     return ARTIS_ERR_ARG;
   }
@@ -3162,7 +3172,14 @@ int artis_amd_set_cellstate(artis_amd_engine *e, const artis_cellstate *cells, c
     }
   }
   e->S = make_step(*ts);
+  return ARTIS_OK;
+}
+
+// the second half: what is derived once per cell state, then the cell cache
+int cellstate_finish(artis_amd_engine *e) {
+  const DevModel &h = e->Mh;
 #if ARTIS_OPT_NT_ON
+  const int64_t nt_stored = e->C.nt_excitations_stored;
   if (!e->C.nt_frac_ionisation || !e->C.nt_frac_excitation || !e->C.nt_deposition_rate_density || !e->C.nt_eff_ionpot ||
       !e->C.nt_prob_num_auger || !e->C.nt_ionenfrac_num_auger || !e->C.nt_exc_count ||
       (nt_stored > 0 && (!e->C.nt_exc_frac_deposition || !e->C.nt_exc_ratecoeffperdeposition || !e->C.nt_exc_alltransindex))) {
@@ -3193,6 +3210,20 @@ int artis_amd_set_cellstate(artis_amd_engine *e, const artis_cellstate *cells, c
   e->have_cells = true;
   e->cellstate_serial++;
   return artis_amd_populate_cellcache(e, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int artis_amd_set_cellstate(artis_amd_engine *e, const artis_cellstate *cells, const artis_timestep *ts) {
+  if (!e || !cells || !ts) {
+    g_last_error = "null argument";
+    return ARTIS_ERR_ARG;
+  }
+  const int rc = cellstate_upload(e, cells, ts, false);
+  if (rc != ARTIS_OK) return rc;
+  return cellstate_finish(e);
 }
 
 }  // extern "C"
@@ -3666,3 +3697,4 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 #include "stage_thermal.h"
 #include "stage_bfheat.h"
 #include "stage_ratecoeff.h"
+#include "stage_photoion.h"

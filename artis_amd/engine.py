@@ -90,6 +90,8 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_debug_gk61.argtypes = [C.c_int32, C.POINTER(abi.Gk61Case), C.POINTER(abi.Gk61Result)]
     L.artis_amd_ratecoeff_compute.argtypes = [C.c_void_p, C.POINTER(abi.RatecoeffRequest)]
     L.artis_amd_ratecoeff_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.RatecoeffStats)]
+    L.artis_amd_set_cellstate_photoion.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(abi.PhotoionParams), C.c_void_p]
+    L.artis_amd_photoion_download.argtypes = [C.c_void_p, C.POINTER(abi.PhotoionResult)]
     if L.artis_amd_abi_version() != abi.ABI_VERSION:  # a stale or foreign build would read these ctypes structs with another layout
         raise EngineError(f"{so}: ABI version {L.artis_amd_abi_version()}, this package describes version {abi.ABI_VERSION}")
     assert L.artis_amd_sizeof_packet() == abi.PACKET_DTYPE.itemsize
@@ -123,6 +125,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_thermal_solve", "artis_amd_thermal_rates", "artis_amd_thermal_download", "artis_amd_grid_update_thermal",
     "artis_amd_bfheating_update", "artis_amd_bfheating_download", "artis_amd_thermal_solve_bfheated", "artis_amd_debug_gk61",
     "artis_amd_ratecoeff_compute", "artis_amd_ratecoeff_download",
+    "artis_amd_set_cellstate_photoion", "artis_amd_photoion_download",
     "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
     "artis_amd_sizeof_plan", "artis_amd_engine_plan",
 ]
@@ -557,6 +560,39 @@ class Engine:
         cut = lambda a: None if a is None else a[: shape[0] * shape[1]].reshape(shape)
         out = dict(spontrecombcoeffs=cut(spont), corrphotoioncoeffs=cut(gamma), bfcooling_coeffs=cut(cool), flags=cut(flags))
         out.update({k: v for k, v in abi.struct_dict(stats).items() if k != "struct_size"})
+        return out
+
+    # photoionisation coefficients of builds without USE_LUT_PHOTOION (include/artis_amd.h artis_amd_set_cellstate_photoion)
+    def set_cellstate_photoion(self, cells: abi.CellState, ts: abi.Timestep, use_bf_estimators: bool = False, bfrate_normed=None,
+                               cells_per_launch: int = 0, stream: int = 0):
+        """set_cellstate for a cell state without "corrphotoioncoeff": the engine computes it on the device from the state it uploads.
+        use_bf_estimators: the host's timestep >= DETAILED_BF_ESTIMATORS_USEFROMTIMESTEP; bfrate_normed [ncell, nbfestim] float32, or
+        None: the last radfield_fit's block, device to device. photoion() downloads what was computed."""
+        bf = None if bfrate_normed is None else np.ascontiguousarray(bfrate_normed, dtype=np.float32).reshape(-1)
+        p = abi.PhotoionParams(struct_size=C.sizeof(abi.PhotoionParams), use_bf_estimators=int(bool(use_bf_estimators)),
+                               cells_per_launch=int(cells_per_launch))
+        if bf is not None:
+            p.bfrate_normed = bf.ctypes.data_as(C.POINTER(C.c_float))
+        self._cells, self._ts = cells, ts
+        self._check(self.L.artis_amd_set_cellstate_photoion(self.h, C.cast(cells.ref(), C.c_void_p), C.cast(ts.ref(), C.c_void_p), C.byref(p),
+                                                            C.c_void_p(stream)))
+
+    def photoion(self) -> dict:
+        """artis_amd_photoion_download: "coeff" [ncell, nphixstargets_total], "source" alike (uint8, abi.PHOTOION_SRC_*), "flags" [ncell]
+        (abi.PHOTOION_NONFINITE), "totals" as a dict over abi.PHOTOION_TOTALS, the sizes and "kernel_ms" """
+        info = abi.PhotoionResult(struct_size=C.sizeof(abi.PhotoionResult))
+        self._check(self.L.artis_amd_photoion_download(self.h, C.byref(info)))  # sizes first
+        n, ne = info.npts_nonempty, info.nphixstargets_total
+        out = dict(coeff=np.zeros(max(n * ne, 1)), source=np.zeros(max(n * ne, 1), np.uint8), flags=np.zeros(max(n, 1), np.int32))
+        types = dict(abi.PhotoionResult._fields_)
+        for k, v in out.items():
+            setattr(info, k, v.ctypes.data_as(types[k]))
+        self._check(self.L.artis_amd_photoion_download(self.h, C.byref(info)))
+        out["coeff"] = out["coeff"][: n * ne].reshape(n, ne)
+        out["source"] = out["source"][: n * ne].reshape(n, ne)
+        out["flags"] = out["flags"][:n]
+        out.update(totals={k: int(info.totals[i]) for i, k in enumerate(abi.PHOTOION_TOTALS)}, npts_nonempty=n, nphixstargets_total=ne,
+                   nbfcontinua=int(info.nbfcontinua), nbfestim=int(info.nbfestim), kernel_ms=float(info.kernel_ms))
         return out
 
     def thermal_rates(self, bfheatingcoeffs, Te=None, rebalance: bool = False, ntlepton_dep=None, dep_alpha=None, dep_spfission=None,

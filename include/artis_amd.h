@@ -479,7 +479,9 @@ typedef struct artis_amd_engine artis_amd_engine;
 #define ARTIS_ERR_RCCL (-6)
 
 const char *artis_amd_last_error(void);
-/* 6 -- and it stays 6 with the deposition rates and thickness flags (artis_deposition_model, artis_deposition_params, artis_deposition_result and
+/* 6 -- and it stays 6 with the photoionisation coefficients (artis_photoion_params, artis_photoion_result, artis_amd_set_cellstate_photoion and
+ * artis_amd_photoion_download): additive; artis_amd_set_cellstate is unchanged.
+ * It stayed 6 with the deposition rates and thickness flags (artis_deposition_model, artis_deposition_params, artis_deposition_result and
  * the five functions artis_amd_deposition_setup / _update / _download / _devptr and artis_amd_grid_update_deposited): additive again.
  * It stayed 6 with the decay and abundance update (artis_decay_model, artis_decay_coeffs, artis_decay_result and the four functions
  * artis_amd_decay_setup / _update / _download and artis_amd_grid_update_decayed): new functions and new structs only, no existing one changed.
@@ -1232,6 +1234,51 @@ int artis_amd_ratecoeff_compute(artis_amd_engine *eng, const artis_ratecoeff_req
  * and the counts to the host; any pointer may be NULL. A non-NULL corrphotoion in a build without USE_LUT_PHOTOION: ARTIS_ERR_ARG. */
 int artis_amd_ratecoeff_download(artis_amd_engine *eng, double *spont, double *corrphotoion, double *bfcooling, int32_t *flags,
                                  artis_ratecoeff_stats *stats);
+
+/* ---- photoionisation coefficients of builds without USE_LUT_PHOTOION -------------------------
+ * get_corrphotoioncoeff (ratecoeff.cc:840) for every bound-free pair of every cell on the device, in place of the host array
+ * artis_cellstate.corrphotoioncoeff: the normalised bound-free estimator of the last timestep where the build keeps one and it is >= 0
+ * (DETAILED_BF_ESTIMATORS_ON, from DETAILED_BF_ESTIMATORS_USEFROMTIMESTEP on), else one adaptive 61-point Gauss-Kronrod integral
+ * (depth 15, 1e-3) over the cell's radiation field (calculate_corrphotoioncoeff_integral, ratecoeff.cc:480-521), read from the state that
+ * is being set: level populations, T_e, n_e, W, T_R and the multibin W, T_R. Continuum i of the model's allcont_* arrays writes entry
+ * level_phixstargetstart[level] + target of the cell's row; an entry no continuum writes is +0. Rules: artis_amd/csrc/photoion.h.
+ * Bitwise reproducible. Builds with USE_LUT_PHOTOION: ARTIS_ERR_UNSUPPORTED. */
+#define ARTIS_PHOTOION_NONFINITE 1 /* per-cell flag: a coefficient of the cell is not finite (the reference asserts) */
+#define ARTIS_PHOTOION_SRC_ESTIMATOR 1 /* per-entry source: the bound-free estimator */
+#define ARTIS_PHOTOION_SRC_INTEGRAL 2  /* ... the integral (0: no continuum writes the entry) */
+#define ARTIS_PHOTOION_NTOTALS 5
+typedef struct artis_photoion_params {
+  size_t struct_size;          /* sizeof(artis_photoion_params) */
+  int32_t use_bf_estimators;   /* globals::timestep >= DETAILED_BF_ESTIMATORS_USEFROMTIMESTEP (artisoptions.h; 13 in every shipped file);
+                                * must be 0 in a build without DETAILED_BF_ESTIMATORS_ON */
+  const float *bfrate_normed;  /* [npts_nonempty][nbfestim] prev_bfrate_normed, or NULL: the last artis_amd_radfield_fit's block, device
+                                * to device */
+  int32_t cells_per_launch;    /* 0 = default; for tests */
+} artis_photoion_params;
+typedef struct artis_photoion_result {
+  int64_t struct_size; /* sizeof(artis_photoion_result) */
+  /* host arrays to fill; NULL: skip */
+  double *coeff;   /* [npts_nonempty*nphixstargets_total] */
+  uint8_t *source; /* [npts_nonempty*nphixstargets_total] ARTIS_PHOTOION_SRC_* */
+  int32_t *flags;  /* [npts_nonempty] ARTIS_PHOTOION_* */
+  /* reported */
+  int64_t totals[ARTIS_PHOTOION_NTOTALS]; /* entries from estimators, integrals, 61-point nodes, integrals that reached depth 15,
+                                           * non-finite coefficients */
+  int32_t npts_nonempty, nphixstargets_total, nbfcontinua, nbfestim;
+  double kernel_ms; /* HIP-event time of all launches of k_photoion */
+} artis_photoion_result;
+/* artis_amd_set_cellstate for a host that does not make corrphotoioncoeff: cells->corrphotoioncoeff must be NULL (else ARTIS_ERR_ARG).
+ * Uploads the state, computes the coefficients on hip_stream from the state just uploaded (the radiation-field timestep test uses
+ * ts->nts), makes them the cell state's and populates the cell cache as artis_amd_set_cellstate does (synchronous). ARTIS_ERR_ARG:
+ * cells->levelpops missing; a multibin build without the bins; use_bf_estimators in a build without DETAILED_BF_ESTIMATORS_ON, or with
+ * bfrate_normed NULL and no valid artis_amd_radfield_fit; every refusal of artis_amd_set_cellstate. Any coefficient that is not finite:
+ * ARTIS_ERR_NOTCONVERGED with the count in the text, and no cell state is resident (as after any refused artis_amd_set_cellstate);
+ * artis_amd_photoion_download still shows the block until the next cell state is set. */
+int artis_amd_set_cellstate_photoion(artis_amd_engine *eng, const artis_cellstate *cells, const artis_timestep *ts,
+                                     const artis_photoion_params *params, void *hip_stream);
+/* Copy the coefficients of the last artis_amd_set_cellstate_photoion, the per-entry sources, the per-cell flags and the counts to the
+ * host (sizes in the reported fields even when every pointer is NULL). ARTIS_ERR_ARG once another cell state has been set. */
+int artis_amd_photoion_download(artis_amd_engine *eng, artis_photoion_result *out);
 
 #ifdef __cplusplus
 }
