@@ -1333,10 +1333,15 @@ struct LateSink {
   int32_t *stamp;
 #endif
   // left: this lane gave up packet pi, whose next kind is `kind`. Wave-uniform control flow.
-  __device__ void put(bool left, int kind, int32_t pi, const Pkt &p, const Lists &next) const {
+  // to_list: a slow-path packet that leaves the kernel for the ordinary slow-path list (it waits for a record k_slow has to fill)
+  __device__ void put(bool left, int kind, int32_t pi, const Pkt &p, const Lists &next, bool to_list = false) const {
     const bool to_r = left && kind == NEXT_RPKT;
     const bool to_t = left && (kind == NEXT_MA || kind == NEXT_KPKT);
-    const bool to_s = left && kind == NEXT_SLOW;
+    // (a packet that waits for a static record the population left out -- tables.h "ABSENT IONS"; this kernel runs where no level is cold --
+    // leaves for the ordinary slow-path list like the kinds the kernel cannot run: k_slow fills such records, between launches)
+    // (from the r-packet and thermal roles that is PEND_MA_FILL alone: an action's record was populated when it was drawn from a moment ago; the
+    // slow role passes to_list for every packet physics.h ma_waits_for_static_fill() flags)
+    const bool to_s = left && kind == NEXT_SLOW && p.pend != PEND_MA_FILL && !to_list;
 #ifdef ARTIS_PROFILE_LATE
     if (to_s) stamp[pi] = (int32_t)(clock64() >> 4);
 #endif
@@ -1386,11 +1391,14 @@ void late_slow_round(const Env &env, const LateSink &sink, const Lists &next, in
   }
   fbsel_wave(env, sel);
   int kind = NEXT_DONE;
-  if (mine) {
+  const bool waits = mine && ma_waits_for_static_fill(env, p);
+  if (waits) {
+    kind = NEXT_SLOW;  // (put() sends it on to k_slow, untouched)
+  } else if (mine) {
     kind = advance_slow(env, p, pi, sel.valid ? &sel : nullptr);
     pkt_store(env.P, pi, p);
   }
-  sink.put(mine, kind, pi, p, next);
+  sink.put(mine, kind, pi, p, next, waits);
 #ifdef ARTIS_PROFILE_LATE
   if ((threadIdx.x & 63) == 0) {
     atomicAdd(&env.stats[46], (stat_t)1);
@@ -1612,6 +1620,12 @@ __global__ void __launch_bounds__(BLOCK, ARTIS_TAIL_WAVES) k_tail(Env env, TailL
     if (owner) kind = classify(env, p, ts_end);
     const int kind_w = __builtin_amdgcn_readfirstlane(__shfl(kind, 0));
     if (kind_w == NEXT_SLOW) {
+      if (env.ion_absent != nullptr) {
+        // the packet waits for a static record the population left out (tables.h "ABSENT IONS"): it leaves for the slow-path list, whose kernel
+        // fills such records -- between launches, where no wave reads a record while another writes it (the host runs that list next)
+        const bool hand = owner && ma_waits_for_static_fill(env, p);
+        if (__builtin_amdgcn_readfirstlane(__shfl((int)hand, 0)) != 0) break;  // (kind is NEXT_SLOW)
+      }
 #ifdef ARTIS_PROFILE_TAIL
       const long long tps0 = clock64();
 #endif
@@ -1788,6 +1802,12 @@ __global__ void __launch_bounds__(BLOCK, ARTIS_SLOW_EU) k_slow(Env env, const in
     }
   }
 #endif
+  if (env.ion_absent != nullptr) {  // a static record the population left out (tables.h "ABSENT IONS"): claimed by the lane, filled by the wave
+    int sc = 0, sul = 0;
+    // (... or that an action of the packet's macro-atom needs again after a refill of its row: physics.h ma_waits_for_static_fill)
+    const bool sfill = mine && ma_waits_for_static_fill(env, p) && ma_static_fill_claim(env, p, &sc, &sul);
+    ma_fill_wave<true>(env, sfill, sc, sul);
+  }
   {  // a cold level's record (PEND_MA_FILL): claimed by the lane, filled by the wave, published by the lane
     int fc = 0, ful = 0;
     int32_t funit = 0;
@@ -2147,6 +2167,12 @@ struct artis_amd_engine {
   bool ma_tables_lds = true;  // k_thermal<1024, true>: the static target tables in LDS when they fit (ARTIS_AMD_MATABLES_LDS=0: in HBM)
   bool trace = false;
   uint32_t *d_visit_counts = nullptr;  // -DARTIS_VISIT_COUNTS builds: [cell][level] transitions drawn per record in the last call
+  // ABSENT IONS (tables.h; EngineConfig::ma_absent_eps >= 0): [resident row][nions] the ions whose static records the last population of the row left
+  // out, and the two counters behind artis_amd_last_absent_records(): records left out by the last population | filled on demand in the last call
+  uint8_t *d_ion_absent = nullptr;
+  double *d_ion_popsum = nullptr;  // k_ion_absent's scratch, [resident row][nions]
+  unsigned long long *d_absent_counts = nullptr;
+  int64_t last_absent_skipped = 0, last_absent_filled = 0;
   ncclComm_t comm = nullptr;  // created by artis_amd_comm_init(), owned by the engine
 };
 
@@ -2158,6 +2184,10 @@ static void apply_config(artis_amd_engine *e, const artis_amd_config &checked) {
   if (ARTIS_OPT_VPKT_ON) e->tail_max = 0;  // (see the estimator block: the event queue is sized per split launch)
   if (e->cfg.park_given) e->park_at = e->cfg.tile_park_at;
   if (e->cfg.bulk_given) e->budget_t_bulk = e->cfg.budget_t_bulk;
+  // ABSENT IONS: off by default in the builds with non-thermal ionisation (the nebular family) -- their macro-atoms reach sparsely populated ions
+  // through the non-thermal channels, 3.1e5 fills per headline step at eps = 1e-12, and the step is 27 ms longer (profiles/r12/absent_ions.md);
+  // ARTIS_AMD_MA_ABSENT_EPS turns it on
+  if (ARTIS_OPT_NT_ON && e->cfg.src_absent == CONFIG_DEFAULT) e->cfg.ma_absent_eps = -1.;
 }
 static void trace_config(const artis_amd_engine *e) {
   const EngineConfig &c = e->cfg;
@@ -2168,6 +2198,8 @@ static void trace_config(const artis_amd_engine *e) {
           c.pop_scratch, config_source_name(c.src_scratch), e->ma_hotfrac, c.hot_given ? config_source_name(c.src_hot) : "default: automatic", c.ma_pool,
           config_source_name(c.src_pool), e->tail_max, config_source_name(c.src_tail), (long long)e->park_at, config_source_name(c.src_park),
           e->Mh.ndpop > 0 ? 1 : 0, c.keep_line_dpop >= 0 ? config_source_name(c.src_dpop) : "default: automatic");
+  fprintf(stderr, "[artis_amd] absent ions: ARTIS_AMD_MA_ABSENT_EPS %g (%s)%s\n", c.ma_absent_eps, config_source_name(c.src_absent),
+          e->d_ion_absent != nullptr ? "" : ": every static record is populated");
 }
 
 // The experiment switches (ARTIS_AMD_*: kernel forms, sorts, chunking) of the fields above (engine_fill). Order: BUDGET before _R / _T, SORT_CELLSHIFT after SORT_NUMAJOR.
@@ -2295,6 +2327,10 @@ Env make_env(const artis_amd_engine *e) {
 #ifdef ARTIS_VISIT_COUNTS
   env.visit_counts = e->d_visit_counts;
 #endif
+  env.ion_absent = e->d_ion_absent;
+  env.ion_popsum = e->d_ion_popsum;
+  env.ma_absent_counts = e->d_absent_counts;
+  env.ma_absent_eps = e->cfg.ma_absent_eps;
   return env;
 }
 
@@ -3053,6 +3089,18 @@ int engine_fill(artis_amd_engine *e, const artis_model *model) {
     e->cc.pop_batch = pop_batch_cells(e->Mh, e->cc.res.tile_cells, e->cfg);
     HIP_TRY(hipMalloc((void **)&e->cc.d_collexc_terms, pop_scratch_alloc_bytes(e->Mh, e->cc.pop_batch)));
   }
+  // (a build whose slow path fills records by the lane has no fill into a static slot: everything is populated)
+  // (... and a model with cold levels keeps the full population of its static records unless ARTIS_AMD_MA_ABSENT_EPS asks: its step was measured
+  // slower with the skip, profiles/r12/absent_ions.md)
+  if (e->Mh.ncold > 0 && e->cfg.src_absent == CONFIG_DEFAULT) e->cfg.ma_absent_eps = -1.;
+  if (e->cfg.ma_absent_eps >= 0. && ARTIS_MA_WAVE_FILL && e->Mh.nions > 0 && e->Mh.nalltrans > 0) {
+    const size_t nb = (size_t)e->cc.res.tile_cells * (size_t)e->Mh.nions;
+    HIP_TRY(hipMalloc((void **)&e->d_ion_absent, nb));
+    HIP_TRY(hipMemset(e->d_ion_absent, 0, nb));
+    HIP_TRY(hipMalloc((void **)&e->d_ion_popsum, nb * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&e->d_absent_counts, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(e->d_absent_counts, 0, 2 * sizeof(unsigned long long)));
+  }
   if (e->trace) trace_config(e);
   if (e->trace)
     fprintf(stderr, "[artis_amd] record tiers: static records for %.2f of every ion's levels, %d cold levels, pool of %d slots per resident cell; %d tile(s) of %lld cells, %zu B per cell\n",
@@ -3083,7 +3131,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   pi_free(e->pi);
   if (e->h_counts) (void)hipHostFree(e->h_counts);
   void *ptrs[] = {e->d_est, e->d_stats, e->d_aos, e->d_hist, e->d_tiles, e->d_count, e->d_cursors, e->cc.d_krow, e->cc.d_fill_cells, e->cc.d_waiting,
-                  e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts};
+                  e->d_bfrate_kept, e->cc.d_collexc_terms, e->d_visit_counts, e->d_ion_absent, e->d_ion_popsum, e->d_absent_counts};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : {e->ev0, e->ev1, e->ev2, e->ev3})
@@ -3559,6 +3607,12 @@ int artis_amd_last_pool_usage(artis_amd_engine *e, int64_t *units_used, int64_t 
   if (!e) return ARTIS_ERR_ARG;
   if (units_used) *units_used = e->last_pool_used;
   if (units_cap) *units_cap = e->last_pool_cap;
+  return ARTIS_OK;
+}
+int artis_amd_last_absent_records(artis_amd_engine *e, int64_t *skipped, int64_t *filled) {
+  if (!e) return ARTIS_ERR_ARG;
+  if (skipped) *skipped = e->last_absent_skipped;
+  if (filled) *filled = e->last_absent_filled;
   return ARTIS_OK;
 }
 int artis_amd_last_thermal_variants(artis_amd_engine *e, int32_t *mask) {

@@ -19,6 +19,52 @@ __global__ void __launch_bounds__(BLOCK) k_levelpops(Env env) {
   if (i >= total) return;
   populate_levelpop(env, fill_cell(env, i / env.M.nlevels), (int)(i % env.M.nlevels));
 }
+// ABSENT IONS (tables.h): which ions the population of the macro-atom records leaves out in each cell of the fill. After k_levelpops, from the
+// populations the kernels below read (whoever formed them). One WAVE per cell, a LANE per ion: the lane adds its ion's populations up (the wave's
+// lanes read one row: its lines are fetched once) and leaves the sum in the row's own scratch (Env::ion_popsum), then -- the wave's lanes together
+// again, their stores done -- compares it with its element's sum. `<=` with the product: an element without abundance is wholly absent, eps = 0 means "exactly zero",
+// eps = 1 every ion. counts[0] += the static records left out (an ion's static records are those of its lowest levels: model_build.h).
+__global__ void __launch_bounds__(BLOCK) k_ion_absent(Env env) {
+  const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wave >= fill_count(env)) return;
+  const DevModel &M = env.M;
+  const int c = fill_cell(env, wave);
+  const double *pops = env.K.levelpops + (krow(env, c) * M.nlevels);
+  double *ionsum = env.ion_popsum + (krow(env, c) * M.nions);
+  uint8_t *absent = env.ion_absent + (krow(env, c) * M.nions);
+  for (int ui = lane; ui < M.nions; ui += 64) {
+    const int start = M.ion_uniquelevelindexstart[ui], n = M.ion_nlevels[ui];
+    double s = 0.;
+    for (int l = 0; l < n; l++) s += pops[start + l];
+    ionsum[ui] = s;
+  }
+  // the lanes read each other's sums below: every lane of the wave has left the loop above (the barrier) and its stores are visible (the fence)
+  __builtin_amdgcn_wave_barrier();
+  __threadfence();
+  __builtin_amdgcn_wave_barrier();
+  unsigned int nskip = 0;
+  for (int ui = lane; ui < M.nions; ui += 64) {
+    const int element = M.ion_element[ui];
+    const int i0 = M.elem_uniqueionindexstart[element], ni = M.elem_nions[element];
+    double total = 0.;
+    for (int i = 0; i < ni; i++) total += ionsum[i0 + i];
+    const bool a = ionsum[ui] <= env.ma_absent_eps * total;
+    absent[ui] = a ? 1 : 0;
+    if (a) {  // the ion's levels with a static record: the first lo of them (bisection for the first cold level)
+      const int start = M.ion_uniquelevelindexstart[ui];
+      int lo = 0, hi = M.ion_nlevels[ui];
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) / 2);
+        if (M.level_pack[start + mid].rec_off >= 0) lo = mid + 1; else hi = mid;
+      }
+      nskip += (unsigned int)lo;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) nskip += __shfl_xor(nskip, o);
+  if (lane == 0 && nskip != 0) atomicAdd(env.ma_absent_counts, (unsigned long long)nskip);
+}
 __global__ void __launch_bounds__(BLOCK) k_line_dpop(Env env) {
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   const int64_t total = fill_count(env) * env.M.nlines;
@@ -178,6 +224,18 @@ __global__ void __launch_bounds__(BLOCK, 4) k_matrans(Env env) {
   U4 *row = env.K.macache + (krow(env, c) * M.nmacache);
   double *upterms = env.collexc_terms + (kf * M.nupcum);
   double(*v)[MATRANS_BLOCK] = lds_v[w];
+  // ABSENT IONS (tables.h): a block that lies inside one ion (levels are in the order of their ions) which is absent in this cell leaves as a wave
+  // with the collisional-excitation cooling terms of its upward entries alone -- the cooling list needs them, bit for bit; nothing of the records is
+  // written (k_macroatom leaves the marker in them). A block that straddles ions skips its absent levels' writes below.
+  const int ion_first = M.level_ion[sfirst.ul], ion_last = M.level_ion[slast.ul];
+  if (ion_first == ion_last && ma_ion_absent(env, c, ion_first)) {
+    for (int k = lane; k < nent; k += 64) {
+      const int e = (nent > MATRANS_BLOCK) ? k : M.scanperm[a0 + k];
+      const MaTransTerms t = matrans_terms<true>(env, c, a0 + e);
+      if (!t.isdown) upterms[M.level_upcum_start[t.ul] + t.i] = t.kterm;
+    }
+    return;
+  }
   if (nent > MATRANS_BLOCK) {
     // one long segment: its rates, 64 terms at a time (lane k adds its term to the finished sum of lane k - 1; lane 0 takes the carry)
     const LevelPack lpk = M.level_pack[sfirst.ul];
@@ -241,7 +299,7 @@ __global__ void __launch_bounds__(BLOCK, 4) k_matrans(Env env) {
       v[2][o + i] = s2;
     }
     const LevelPack lpk = M.level_pack[sg.ul];
-    if (lpk.rec_off < 0) continue;
+    if (lpk.rec_off < 0 || ma_ion_absent(env, c, M.level_ion[sg.ul])) continue;
     double *rates = ma_rates_of(row + lpk.rec_off, lpk.ndown, lpk.nup);
     if (sg.dir == 0) {
       rates[ARTIS_MA_ACTION_RADDEEXC] = s0;
@@ -274,7 +332,7 @@ __global__ void __launch_bounds__(BLOCK, 4) k_matrans(Env env) {
   // 3b. ... into the records: the entries of a line that is not usable are 0, its mark too
   for (int e = lane; e < nent; e += 64) {
     const MaEntryPos ps = ma_entry_pos(M, a0, e);
-    if (ps.lpk.rec_off < 0) continue;
+    if (ps.lpk.rec_off < 0 || ma_ion_absent(env, c, M.level_ion[M.alltrans_owner[a0 + e]])) continue;
     const int e_line = e - (ps.ti % MAREC_PER);
     U4 *rec = row + ps.lpk.rec_off;
     const bool lok_int = lds_ok[w][0][e_line] != 0;
@@ -302,10 +360,11 @@ __global__ void __launch_bounds__(BLOCK) k_macroatom_recomb(Env env) {
   const int r = threadIdx.x & 15;
   const DevModel &M = env.M;
   const int64_t nrows = fill_count(env) * M.nrecomblevels;
-  const bool valid = row_id < nrows;
-  const int c = fill_cell(env, (valid ? row_id : 0) / M.nrecomblevels);
-  const int ul = M.recomb_levels[(valid ? row_id : 0) % M.nrecomblevels];
+  const bool inrange = row_id < nrows;
+  const int c = fill_cell(env, (inrange ? row_id : 0) / M.nrecomblevels);
+  const int ul = M.recomb_levels[(inrange ? row_id : 0) % M.nrecomblevels];
   const int ui = M.level_ion[ul];
+  const bool valid = inrange && !ma_ion_absent(env, c, ui);  // (an absent ion's records are not populated: tables.h "ABSENT IONS")
   const int ls = M.ion_uniquelevelindexstart[ui > 0 ? ui - 1 : 0];
   const int64_t cb = krow(env, c) * M.nphixstargets_total;
   const double e_cur = eps(M, ul);
@@ -354,8 +413,15 @@ __global__ void __launch_bounds__(BLOCK) k_macroatom(Env env) {
   const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   const int64_t total = fill_count(env) * env.M.nlevels;
   if (i >= total) return;
-  if (env.M.level_pack[i % env.M.nlevels].rec_off < 0) return;  // (a cold level: filled when a packet reaches it, physics.h ma_slow_fill)
-  populate_macroatom<true>(env, fill_cell(env, i / env.M.nlevels), (int)(i % env.M.nlevels));
+  const LevelPack lpk = env.M.level_pack[i % env.M.nlevels];
+  if (lpk.rec_off < 0) return;  // (a cold level: filled when a packet reaches it, physics.h ma_slow_fill)
+  const int c = fill_cell(env, i / env.M.nlevels);
+  if (ma_ion_absent(env, c, env.M.level_ion[i % env.M.nlevels])) {
+    // not populated (tables.h "ABSENT IONS"): the marker, at every population of the row; the first visit fills the record (k_slow)
+    *ma_rec_of(env, c, lpk) = U4{{MA_MARK_ABSENT, 0u, 0u, 0u}};
+    return;
+  }
+  populate_macroatom<true>(env, c, (int)(i % env.M.nlevels));
 }
 // The filters of the directions with more transitions than a block of k_matrans holds (DevModel::malongsegs: > MATRANS_BLOCK):
 // a wave per (cell, segment) re-forms the running sums 63 transitions (nine filter lines) at a time -- the same terms
@@ -369,6 +435,7 @@ __global__ void __launch_bounds__(BLOCK) k_mafilter_long(Env env) {
   const int c = fill_cell(env, wave / nseg);
   const MaLongSeg seg = env.M.malongsegs[wave % nseg];
   const LevelPack lpk = env.M.level_pack[seg.ul];
+  if (ma_ion_absent(env, c, env.M.level_ion[seg.ul])) return;  // (the wave: the record is not populated, tables.h "ABSENT IONS")
   U4 *rec = env.K.macache + (krow(env, c) * env.M.nmacache) + lpk.rec_off;
   const double *rates = ma_rates_of(rec, lpk.ndown, lpk.nup);
   const bool down = seg.dir == 0;
@@ -492,6 +559,10 @@ __device__ inline void wave_put_dirfilters(U4 *rec, const LevelPack &lpk, bool d
     }
   }
 }
+// STATIC_SLOT (tables.h "ABSENT IONS"): the record is a static one the population left out. Its action filter (slot 0) holds the marker until
+// lane 0 stores the filter as the record's LAST write, and its cooling filter -- which the population wrote like every level's (k_collexc_filter),
+// and which k-packets read without asking for the record -- is left as it stands.
+template <bool STATIC_SLOT = false>
 __device__ inline void ma_fill_record_wave(const Env &env, int c, int ul) {
   const DevModel &M = env.M;
   const int lane = (int)(threadIdx.x & 63);
@@ -501,9 +572,12 @@ __device__ inline void ma_fill_record_wave(const Env &env, int c, int ul) {
   {  // populate_mainit_at(): every filter entry "never counted", the rates zero
     const int nfilt = marec_rates_slot(nd, nu), nfine0 = marec_fine_slot0(nd, nu), nrec = marec_slots(nd, nu);
     const int ntot = ((nrec + MAREC_ALIGN - 1) / MAREC_ALIGN) * MAREC_ALIGN;
+    const int ncool0 = marec_slot(MADIR_COOL, 0, nd, nu);
     const uint32_t none2 = MAFILT_NONE | (MAFILT_NONE << 16);
-    for (int i = lane; i < ntot; i += 64)
+    for (int i = lane; i < ntot; i += 64) {
+      if (STATIC_SLOT && (i == 0 || (i >= ncool0 && i < nfilt))) continue;
       rec[i] = (i < nfilt) ? U4{{none2, none2, none2, none2}} : ((i >= nfine0 && i < nrec) ? U4{{~0u, ~0u, ~0u, ~0u}} : U4{{0u, 0u, 0u, 0u}});
+    }
   }
   __threadfence_block();  // (other lanes write into these slots below)
   // ---- downward: rates (radiative, collisional de-excitation, internal down), then the internal-down and radiative filters
@@ -585,7 +659,7 @@ __device__ inline void ma_fill_record_wave(const Env &env, int c, int ul) {
       const double s0 = (nu <= 63) ? b0_up : ss[0];
       wave_put_dirfilters(rec, lpk, false, nu, ti, valid, s0, 0., w_up, 0., lane);
       c_up = wave_bcast(s0, nb - 1);
-      if (hi_i >= 0) {
+      if (!STATIC_SLOT && hi_i >= 0) {
         const double sk = ss[1];
         bool ok = (span > 0.) && (span <= DBLMAX);
         uint32_t q = MAFILT_NONE;
@@ -611,23 +685,43 @@ __device__ inline void ma_fill_record_wave(const Env &env, int c, int ul) {
     rates[ARTIS_MA_ACTION_COLDEEXC] = w_col;
     rates[ARTIS_MA_ACTION_INTERNALDOWNSAME] = w_down;
     rates[ARTIS_MA_ACTION_INTERNALUPSAME] = w_up;
-    populate_macroatom<false>(env, c, ul);  // the bound-free channels and the action filter
+    populate_macroatom<false, STATIC_SLOT>(env, c, ul);  // the bound-free channels and the action filter (a static slot's: after a release)
   }
 }
 // every lane of the wave whose packet waits for a record it has claimed (physics.h ma_slow_fill_claim) gets it filled, lane by lane
+template <bool STATIC_SLOT = false>
 __device__ inline void ma_fill_wave(const Env &env, bool mine, int c, int ul) {
   unsigned long long m = __ballot(mine);
   while (m != 0) {
     const int src = __ffsll((long long)m) - 1;
-    ma_fill_record_wave(env, __builtin_amdgcn_readlane(c, src), __builtin_amdgcn_readlane(ul, src));
+    ma_fill_record_wave<STATIC_SLOT>(env, __builtin_amdgcn_readlane(c, src), __builtin_amdgcn_readlane(ul, src));
     m &= m - 1;
   }
+}
+// ABSENT IONS (tables.h): the packet waits (PEND_MA_FILL) in a level with a STATIC record that the population left out. The lane claims the record
+// with a compare-and-swap on the marker word (absent -> being filled); true: the wave is to fill it (ma_fill_wave<true>). A lane that loses the
+// claim -- another lane won it, in this launch or an earlier one -- goes back to its list: the record is complete when this launch ends.
+__device__ inline bool ma_static_fill_claim(const Env &env, const Pkt &p, int *c_out, int *ul_out) {
+  const DevModel &M = env.M;
+  const int c = M.propcell_nonemptymgi[p.cellindex];
+  const int ul = M.ion_uniquelevelindexstart[uion(M, p.ma_element, p.ma_ion)] + p.ma_level;
+  const LevelPack lpk = M.level_pack[ul];
+  if (lpk.rec_off < 0) return false;
+  uint32_t *w0 = (uint32_t *)(env.K.macache + (krow(env, c) * M.nmacache) + lpk.rec_off);
+  if (__hip_atomic_load(w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != MA_MARK_ABSENT) return false;
+  if (atomicCAS(w0, MA_MARK_ABSENT, MA_MARK_FILLING) != MA_MARK_ABSENT) return false;
+  atomicAdd(env.ma_absent_counts + 1, 1ull);
+  *c_out = c;
+  *ul_out = ul;
+  return true;
 }
 // test / debug view of one cell's records (artis_amd_debug_cellcache): a thread per level
 __global__ void __launch_bounds__(BLOCK) k_debug_macache(Env env, int c, double *maprocessrates, double *matrans, int32_t *bad) {
   const int ul = blockIdx.x * BLOCK + threadIdx.x;
   if (ul >= env.M.nlevels) return;
   if (ma_resolve(env, c, env.M.level_pack[ul].rec_off) == MA_REC_NONE) return;  // (a cold level no packet has reached in this cell: no record)
+  // a static record the population left out (tables.h "ABSENT IONS") is filled before it is read: the sequential forms, as for a cold level
+  if (env.M.level_pack[ul].rec_off >= 0 && ma_mark_unpopulated(ma_rec_of(env, c, env.M.level_pack[ul])->w[0])) ma_fill_record(env, c, ul);
   const int b = debug_level_record(env, c, ul, maprocessrates, matrans);
   if (b != 0) atomicAdd(bad, b);
 }

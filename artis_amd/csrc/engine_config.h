@@ -97,6 +97,7 @@ inline int config_copy_checked(const artis_amd_config *in, artis_amd_config *out
 enum ConfigSource : uint8_t { CONFIG_DEFAULT = 0, CONFIG_ENV = 1, CONFIG_STRUCT = 2 };
 inline const char *config_source_name(uint8_t s) { return s == CONFIG_STRUCT ? "struct" : (s == CONFIG_ENV ? "environment" : "default"); }
 
+constexpr double MA_ABSENT_EPS_DEFAULT = 1e-12;  // (the shortest headline step of the values measured: profiles/r12/absent_ions.md)
 // The resolved configuration: what cache_budget_bytes(), the record-tier choice, the population scratch and the driver read. Bytes are kept as
 // doubles, the form the sizing rule computes in (a variable in MB times 2^20 is exact).
 struct EngineConfig {
@@ -118,7 +119,11 @@ struct EngineConfig {
   // before). No struct field: a placement switch like the other budgets (ARTIS_AMD_BUDGET_T_BULK), resolved here with the rest.
   bool bulk_given = false;
   int budget_t_bulk = 0;
-  uint8_t src_budget = 0, src_headroom = 0, src_scratch = 0, src_hot = 0, src_pool = 0, src_tail = 0, src_park = 0, src_dpop = 0, src_bulk = 0;
+  // ABSENT IONS (tables.h): the population leaves out the static macro-atom records of an ion whose population in the cell is <= eps * its element's;
+  // the first visit fills such a record (results do not depend on it). < 0: everything is populated; 0: ions without any population only; 1: every
+  // ion, every record filled at its first visit (tests). No struct field: a placement switch (ARTIS_AMD_MA_ABSENT_EPS).
+  double ma_absent_eps = MA_ABSENT_EPS_DEFAULT;
+  uint8_t src_budget = 0, src_headroom = 0, src_scratch = 0, src_hot = 0, src_pool = 0, src_tail = 0, src_park = 0, src_dpop = 0, src_bulk = 0, src_absent = 0;
 };
 
 // THE resolution point: a field set in the (checked) struct wins; a field left at "automatic / default" takes its ARTIS_AMD_* variable if that is
@@ -167,6 +172,10 @@ inline EngineConfig resolve_config(const artis_amd_config &c) {
   }
   if (const char *b = std::getenv("ARTIS_AMD_BUDGET_T_BULK")) {
     r.bulk_given = true, r.budget_t_bulk = std::max(0, std::atoi(b)), r.src_bulk = CONFIG_ENV;
+  }
+  if (const char *b = std::getenv("ARTIS_AMD_MA_ABSENT_EPS")) {
+    const double v = std::atof(b);
+    r.ma_absent_eps = (v >= 0.) ? std::min(1., v) : -1., r.src_absent = CONFIG_ENV;  // (a NaN: populate everything)
   }
   return r;
 }

@@ -293,6 +293,14 @@ struct Env {
   // set by a kernel whose waves FILL pool records while others read them (k_tail, k_slow): a cold level's published place is then read with
   // acquire semantics (ma_rowtab_acquire), pairing with the filler's release store. The thermal kernels read records of earlier launches only.
   int32_t ma_concurrent_fill;
+  // ABSENT IONS (tables.h "ABSENT IONS"): [row][M.nions] 1 = the population left the static records of this ion's levels unpopulated in this cell
+  // (k_ion_absent; the records hold the marker MA_MARK_ABSENT and are filled at their first visit); null: every record is populated
+  // (ARTIS_AMD_MA_ABSENT_EPS < 0, and the host emulation). ma_absent_eps: an ion is absent iff its population <= eps * its element's.
+  // ma_absent_counts: [0] records the last population skipped, [1] records filled on demand in the last propagation call.
+  uint8_t *ion_absent;
+  double *ion_popsum;  // [row][M.nions] k_ion_absent's own scratch: the sums of the ions' level populations
+  unsigned long long *ma_absent_counts;
+  double ma_absent_eps;
 #ifdef ARTIS_VISIT_COUNTS
   // (measurement build, tools/visit_sparsity.py) [cell][level] macro-atom transitions drawn in that level's record this call
   uint32_t *visit_counts;
@@ -362,6 +370,20 @@ AHD uint32_t rng_next(Pkt &p) {
   p.s2 ^= t;
   p.s3 = rotl32(p.s3, 11U);
   return result;
+}
+// the generator as it was before its last rng_next(): the state's step is a bijection (xor, shift and rotate of words), inverted here. For the one
+// place that has drawn before it learns that nothing was to be drawn (ma_jump_internal: a record that is not populated yet).
+// s1' ^ s2' = s1 ^ (s1 << 9) gives s1 back 9 bits at a time; the other words follow.
+AHD void rng_unstep(Pkt &p) {
+  const uint32_t s3a = rotl32(p.s3, 21U);  // (rotated back by 11: s3 ^ s1)
+  const uint32_t y = p.s1 ^ p.s2;
+  const uint32_t s1 = y ^ (y << 9U) ^ (y << 18U) ^ (y << 27U);
+  const uint32_t s2a = p.s1 ^ s1;  // s2 ^ s0
+  const uint32_t s0 = p.s0 ^ s3a;
+  p.s0 = s0;
+  p.s1 = s1;
+  p.s2 = s2a ^ s0;
+  p.s3 = s3a ^ s1;
 }
 // random.h:49 rng_uniform() redraws while the value is 1. It never is: the 24-bit integer is at most 2^24 - 1, exact as a
 // float, and the product with 2^-24 is exact, so the largest value is 1 - 2^-24. Without the (dead) loop a draw is
@@ -1360,6 +1382,16 @@ AHD double nt_excitation_ratecoeff(const DevCells &C, int c, int lowerlevel, int
 // coefficient once instead of twice. The later stages form the same products and add them in the same order: same bits.
 // the terms one entry of alltrans adds to the running sums of its level: for a downward transition {R e_trans, C e_trans,
 // (R + C) e_target}, for an upward one {(R + C + NT) e_cur, -, -} plus its k-packet cooling term n C e_trans
+// ABSENT IONS (tables.h): a static record the population left out holds MA_MARK_ABSENT in the first word of its action filter (rec[0]; the other
+// three words 0), MA_MARK_FILLING while the slow-path kernel fills it. Both read as "first entry above the last" -- the test the transition loop
+// makes anyway (ma_jump_internal `unusable`) -- and neither is a filter populate_mafilter_level() can write: its entries are at most 0x7FFF, and its
+// own "no usable filter" marker has 0 in the second entry.
+constexpr uint32_t MA_MARK_ABSENT = MAFILT_NONE | (0x8001u << 16);
+constexpr uint32_t MA_MARK_FILLING = MAFILT_NONE | (0x8002u << 16);
+AHD bool ma_mark_unpopulated(uint32_t w0) { return (w0 & 0x8000FFFFu) == (0x80000000u | MAFILT_NONE); }
+AHD bool ma_ion_absent(const Env &env, int c, int ui) {
+  return env.ion_absent != nullptr && env.ion_absent[(krow(env, c) * env.M.nions) + ui] != 0;
+}
 struct MaTransTerms {
   int ul, i;        // owner level; index within its down (isdown) or up block
   bool isdown;
@@ -1376,7 +1408,8 @@ AHD MaTransTerms matrans_terms(const Env &env, int c, int ati) {
   r.ul = M.alltrans_owner[ati];
   r.lpk = M.level_pack[r.ul];
   const int ul = r.ul;
-  if (COOLING_ONLY_IF_COLD && r.lpk.rec_off < 0) {
+  // (... and of a level whose ion is absent in this cell: its static record is not populated either, tables.h "ABSENT IONS")
+  if (COOLING_ONLY_IF_COLD && (r.lpk.rec_off < 0 || ma_ion_absent(env, c, M.level_ion[ul]))) {
     const int i = ati - r.lpk.alltrans_startdown;
     r.isdown = i < r.lpk.ndown;
     r.i = r.isdown ? i : i - r.lpk.ndown;
@@ -1616,7 +1649,7 @@ AHD void populate_mafilter_level(const Env &env, int c, int ul);  // (below, wit
 // bound-bound rates are already in the record: populate_level_bb() / k_matrans), then the record's action filter
 // RECOMB_DONE: the three sums over the level's recombination list are in the record already (k_macroatom_recomb formed them with a
 // row of lanes, the additions in this loop's order)
-template <bool RECOMB_DONE = false>
+template <bool RECOMB_DONE = false, bool RELEASE_BEFORE_FILTER = false>
 AHD void populate_macroatom(const Env &env, int c, int ul) {
   const DevModel &M = env.M;
   const int ui = M.level_ion[ul];
@@ -1682,6 +1715,10 @@ AHD void populate_macroatom(const Env &env, int c, int ul) {
 #endif
   rates[ARTIS_MA_ACTION_INTERNALUPHIGHERNT] = s_up_highernt;
   rates[ARTIS_MA_ACTION_INTERNALUPHIGHER] = s_up_higher;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // (a static record filled on demand, tables.h "ABSENT IONS": the action filter -- where its marker stands -- is the last write, after a release)
+  if (RELEASE_BEFORE_FILTER) __threadfence();
+#endif
   populate_mafilter_level(env, c, ul);  // every rate of the record is final now: the action filter of its line 0
 }
 // one (cell, ion): calculate_cooling_rates_ion<true> kpkt.cc:57 in three parts, so that the GPU can form the long middle
@@ -4135,6 +4172,15 @@ AHD int ma_jump_internal(const Env &env, Pkt &p, MACtx &k, const U4 *rec) {
     // ("cum[8] = total <= zrand * total" never holds: zrand <= 1 - 2^-24, and the product of that with total is below total)
     const bool unusable = (f.w[0] & 0xFFFFu) > (f.w[3] >> 16);
     if (__builtin_expect((int)amb | (int)unusable | (int)(env.ma_filters_off != 0), 0)) {
+      // a static record the population left out (its ion is absent in this cell, tables.h "ABSENT IONS"): nothing is drawn -- the generator goes
+      // back to where it stood -- and the caller hands the packet to the slow path, which fills the record (PEND_MA_FILL)
+      if (ma_mark_unpopulated(f.w[0])) {
+#if defined(ARTIS_VISIT_COUNTS) && defined(__HIP_DEVICE_COMPILE__)
+        if (env.visit_counts != nullptr) atomicSub(&env.visit_counts[((int64_t)k.c * env.M.nlevels) + k.start + p.ma_level], 1u);  // (nothing is drawn: counted after the fill)
+#endif
+        rng_unstep(p);
+        return MA_EXIT_FILL;
+      }
       double r[MA_N], cum[MA_N];
       ma_load_rates(ma_rates_of(rec, k.nd, k.nu), r, cum);
       if (unusable && !(cum[MA_N - 1] > 0.)) {
@@ -4312,6 +4358,29 @@ AHD bool ma_record_absent(const Env &env, const Pkt &p) {
   if (lpk.rec_off >= 0) return false;
   return ma_rowtab_load(env.K.ma_rowtab + (krow(env, M.propcell_nonemptymgi[p.cellindex]) * M.ncold) + (-lpk.rec_off - 1)) == -1;
 }
+// the level the packet's macro-atom stands in has a static record (PEND_MA_FILL then means: one the population left out, tables.h "ABSENT IONS")
+AHD bool ma_level_static(const Env &env, const Pkt &p) {
+  const DevModel &M = env.M;
+  if (p.ma_level < 0) return false;
+  return M.level_pack[M.ion_uniquelevelindexstart[uion(M, p.ma_element, p.ma_ion)] + p.ma_level].rec_off >= 0;
+}
+// The packet cannot go on before the slow-path kernel has filled a static record the population left out (tables.h "ABSENT IONS"): its walk met
+// the marker (PEND_MA_FILL), or an action / search of its macro-atom is pending whose record a refill of the row has left unpopulated again.
+// The kernels that must not fill records while others read them (k_late, k_tail) hand such a packet to the slow-path list.
+AHD bool ma_waits_for_static_fill(const Env &env, const Pkt &p) {
+  if (env.ion_absent == nullptr || !ma_level_static(env, p)) return false;
+  if (p.pend == PEND_MA_FILL) return true;
+  if (!ma_ion_absent(env, env.M.propcell_nonemptymgi[p.cellindex], uion(env.M, p.ma_element, p.ma_ion))) return false;  // (never left out: never filled)
+  if (p.pend != PEND_MA_ACTION && p.pend != PEND_MA_SEARCH && p.pend != PEND_MA_RADSEARCH) return false;
+  const DevModel &M = env.M;
+  const LevelPack lpk = M.level_pack[M.ion_uniquelevelindexstart[uion(M, p.ma_element, p.ma_ion)] + p.ma_level];
+  const uint32_t *w0 = (const uint32_t *)(env.K.macache + (krow(env, M.propcell_nonemptymgi[p.cellindex]) * M.nmacache) + lpk.rec_off);
+#if defined(__HIP_DEVICE_COMPILE__)
+  return ma_mark_unpopulated(__hip_atomic_load(w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+#else
+  return ma_mark_unpopulated(*w0);
+#endif
+}
 AHD bool ma_ensure_record(const Env &env, int c, int ul, bool *failed, bool *full = nullptr) {
   const DevModel &M = env.M;
   const LevelPack lpk = M.level_pack[ul];
@@ -4377,6 +4446,22 @@ AHD void ma_slow_fill(const Env &env, Pkt &p) {
 // a tile (and empties the pool) while packets wait for it. true: it is there (again).
 AHD bool ma_slow_record_ready(const Env &env, Pkt &p) {
   const DevModel &M = env.M;
+  // (tables.h "ABSENT IONS") ... or it was a static record filled on demand, and the row's refill has put the marker back: the slow-path kernel
+  // fills it again (the action's lane claims it first, artis_engine.hip k_slow); while another wave is at it, ask again. A record that is
+  // there may have been completed by another wave of this very launch: its loads come after an acquire (the filler's release: populate_macroatom).
+  // (Only the records of an ion that is absent in the cell are ever filled on demand: every other action pays one byte's read.)
+  if (env.ion_absent != nullptr && ma_level_static(env, p) && ma_ion_absent(env, M.propcell_nonemptymgi[p.cellindex], uion(M, p.ma_element, p.ma_ion))) {
+    const LevelPack lpk = M.level_pack[M.ion_uniquelevelindexstart[uion(M, p.ma_element, p.ma_ion)] + p.ma_level];
+    const uint32_t *w0 = (const uint32_t *)(env.K.macache + (krow(env, M.propcell_nonemptymgi[p.cellindex]) * M.nmacache) + lpk.rec_off);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t v = __hip_atomic_load(w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (ma_mark_unpopulated(v)) return false;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+#else
+    if (ma_mark_unpopulated(*w0)) return false;
+#endif
+    return true;
+  }
   if (M.ncold == 0) return true;
   bool failed = false;
   const bool ready = ma_ensure_record(env, M.propcell_nonemptymgi[p.cellindex], M.ion_uniquelevelindexstart[uion(M, p.ma_element, p.ma_ion)] + p.ma_level, &failed);

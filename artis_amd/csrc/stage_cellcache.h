@@ -22,6 +22,7 @@ void launch_fill_batch(artis_amd_engine *e, hipStream_t s, const Env &env, int64
   const DevModel &h = e->Mh;
   if (h.ncold > 0) hipLaunchKernelGGL(k_ma_reset, dim3(nblocks(ncell * h.ncold)), dim3(BLOCK), 0, s, env);
   hipLaunchKernelGGL(k_levelpops, dim3(nblocks(ncell * h.nlevels)), dim3(BLOCK), 0, s, env);
+  if (env.ion_absent != nullptr) hipLaunchKernelGGL(k_ion_absent, dim3(nblocks(ncell * 64)), dim3(BLOCK), 0, s, env);  // (tables.h "ABSENT IONS")
   if (h.ndpop > 0) hipLaunchKernelGGL(k_line_dpop, dim3(nblocks(ncell * h.nlines)), dim3(BLOCK), 0, s, env);
   hipLaunchKernelGGL(k_cell_scalars, dim3(nblocks(ncell)), dim3(BLOCK), 0, s, env);
   if (h.nbfcontinua > 0) hipLaunchKernelGGL(k_allcont, dim3(nblocks(ncell * h.nkeepwords * 64)), dim3(BLOCK), 0, s, env);
@@ -54,6 +55,12 @@ int finish_fill(artis_amd_engine *e, hipStream_t s, int64_t ncell, bool listed_c
   HIP_TRY(hipMemcpy(&cur, e->d_stats + ARTIS_STAT_UPDATECELL, sizeof(cur), hipMemcpyDeviceToHost));
   cur += add;
   HIP_TRY(hipMemcpy(e->d_stats + ARTIS_STAT_UPDATECELL, &cur, sizeof(cur), hipMemcpyHostToDevice));
+  if (e->d_absent_counts != nullptr) {
+    unsigned long long skipped = 0;
+    HIP_TRY(hipMemcpy(&skipped, e->d_absent_counts, sizeof(skipped), hipMemcpyDeviceToHost));
+    e->last_absent_skipped = (int64_t)skipped;
+    if (e->trace) fprintf(stderr, "[artis_amd] population of %lld cells: %lld static records of absent ions left out\n", (long long)ncell, (long long)skipped);
+  }
   int32_t err = 0;
   HIP_TRY(hipMemcpy(&err, e->d_err, sizeof(err), hipMemcpyDeviceToHost));
   if (err != 0) {
@@ -77,6 +84,7 @@ int populate_tile(artis_amd_engine *e, hipStream_t s, int64_t nfill = -1) {
   const int64_t ncell_fill = listed_cells ? nfill : hi - lo;
   if (ncell_fill <= 0) return ARTIS_OK;
   if (const int rc = empty_pool_for_fill(e, s, listed_cells)) return rc;
+  if (e->d_absent_counts != nullptr) HIP_TRY(hipMemsetAsync(e->d_absent_counts, 0, sizeof(unsigned long long), s));  // (the records this population leaves out)
   // in batches of pop_batch cells (the scratch of cooling terms holds that many rows); the kernels of a batch see it as
   // their whole fill: a sub-range of the tile, or a stretch of the list of a sparse fill
   for (int64_t b0 = 0; b0 < ncell_fill; b0 += e->cc.pop_batch) {

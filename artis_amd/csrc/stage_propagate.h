@@ -382,11 +382,20 @@ struct PropRun {
     }
     for (int i = 0; i < LATE_NQ; i++) HIP_TRY(hipMemsetAsync(e->d_count + kinds[i], 0, sizeof(int32_t), s));
     HIP_TRY(hipMemsetAsync(e->d_late_bail, 0, sizeof(int32_t), s));
+    // ABSENT IONS (tables.h): the kernel ejects the packets that wait for a record the population left out to the slow-path list -- the ALTERNATE one
+    // (its workgroups still read their shares of the current one), which becomes the current list as after a launch of that kind; run_visit() runs it next
+    const bool absent_on = env.ion_absent != nullptr;
+    if (absent_on) HIP_TRY(hipMemsetAsync(e->d_count + NEXT_NKINDS, 0, sizeof(int32_t), s));
     HIP_TRY(hipEventRecord(e->ev0, s));
     e->last.thermal_variants |= ARTIS_AMD_THERMAL_LATE;
-    hipLaunchKernelGGL(k_late, dim3(e->ncu), dim3(LATE_TB), lds, s, env, a, lists_for(0), e->d_stats);
+    hipLaunchKernelGGL(k_late, dim3(e->ncu), dim3(LATE_TB), lds, s, env, a, lists_for(absent_on ? NEXT_SLOW : 0), e->d_stats);
     HIP_TRY(hipEventRecord(e->ev1, s));
     STEP(read_counts());
+    if (absent_on) {
+      cur[NEXT_SLOW] = 1 - cur[NEXT_SLOW];
+      cnt[NEXT_SLOW] = cnt[NEXT_NKINDS];
+      HIP_TRY(hipMemcpyAsync(e->d_count + NEXT_SLOW, e->d_count + NEXT_NKINDS, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    }
     const int32_t bail = e->h_counts[(2 * NEXT_NKINDS) + 1];  // (the slot after the error flag: one pinned copy brings all)
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
@@ -478,6 +487,8 @@ struct PropRun {
       // there, about to become r-packets, beside a short thermal list)
       if (late_ok && cnt[NEXT_KPKT] == 0 && (int64_t)cnt[NEXT_RPKT] + cnt[NEXT_MA] <= e->late_max && cnt[NEXT_BB] <= e->late_max) {
         if (cnt[NEXT_RPKT] + cnt[NEXT_MA] + cnt[NEXT_SLOW] > 0) STEP(run_late());
+        // (what k_late left on the slow-path list waits for records the population left out: k_slow fills them, tables.h "ABSENT IONS")
+        if (env.ion_absent != nullptr && cnt[NEXT_SLOW] > 0) STEP(run_kind(NEXT_SLOW));
         for (int kind : order)
           if (kind == NEXT_GAMMA || kind == NEXT_BB)
             if (cnt[kind] > 0) STEP(run_kind(kind));
@@ -488,6 +499,7 @@ struct PropRun {
       if (should_park(sweep, tile, tail_n, tail_now)) break;
       if (tail_now) {
         STEP(run_tail(tail_n));
+        if (env.ion_absent != nullptr && cnt[NEXT_SLOW] > 0) STEP(run_kind(NEXT_SLOW));  // (as after k_late above)
         continue;
       }
       for (int kind : order)
@@ -512,6 +524,7 @@ extern "C" int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_st
   if (e->d_visit_counts == nullptr) HIP_TRY(hipMalloc((void **)&e->d_visit_counts, vb));
   HIP_TRY(hipMemsetAsync(e->d_visit_counts, 0, vb, s));
 #endif
+  if (e->d_absent_counts != nullptr) HIP_TRY(hipMemsetAsync(e->d_absent_counts + 1, 0, sizeof(unsigned long long), s));  // (the records this call fills on demand)
   PropRun run{e, s};
   if (e->d_bfrate_kept != nullptr) {
     if (e->bfrate_kept_dirty)
@@ -555,6 +568,12 @@ extern "C" int artis_amd_update_packets_device(artis_amd_engine *e, void *hip_st
     HIP_TRY(hipMemcpy(&used, e->K.ma_pool_used, sizeof(used), hipMemcpyDeviceToHost));
     e->last_pool_used = std::min<int64_t>(used, run.env.ma_pool_cap);
     e->last_pool_cap = run.env.ma_pool_cap;
+  }
+  if (e->d_absent_counts != nullptr) {  // artis_amd_last_absent_records()
+    unsigned long long filled = 0;
+    HIP_TRY(hipMemcpy(&filled, e->d_absent_counts + 1, sizeof(filled), hipMemcpyDeviceToHost));
+    e->last_absent_filled = (int64_t)filled;
+    if (e->trace) fprintf(stderr, "[artis_amd] absent ions: %lld records filled on demand (the last population left %lld out)\n", (long long)filled, (long long)e->last_absent_skipped);
   }
   int32_t err = 0;
   HIP_TRY(hipMemcpy(&err, e->d_err, sizeof(err), hipMemcpyDeviceToHost));

@@ -157,6 +157,15 @@ struct DevModel {
   // says where it is. A pool that is used up is emptied by the host before the slow-path list's next launch (Env::ma_pool_full; every cold level
   // is then without a record again and is filled when next needed, as after a tile's refill): it costs fills, never an answer.
   // ncold == 0: every level has a static record (the default whenever the whole cache fits one tile).
+  // ABSENT IONS (round 12). On top of the static records, per cell and per population: an ion whose population in the cell is at most eps times its
+  // element's (Env::ion_absent, k_ion_absent; eps = ARTIS_AMD_MA_ABSENT_EPS) has its static records LEFT OUT by the population -- nothing of their
+  // transitions is evaluated but the collisional-excitation cooling terms the cell's cooling list needs (matrans_terms<true>), and the first word of
+  // the record's action filter holds MA_MARK_ABSENT (physics.h), written at every population of the row. A walker that meets the marker draws
+  // nothing and leaves for the slow-path list (PEND_MA_FILL, as from a cold level without a record); k_slow claims the record (compare-and-swap,
+  // absent -> MA_MARK_FILLING) and its wave fills it with the fill of a cold level's record -- the same terms added in the same order: the bits
+  // the population would have written -- storing the action filter last. Records are filled BETWEEN the launches that read them: k_late and
+  // k_tail hand a packet that meets the marker to the ordinary slow-path list. The record's cooling filter is the population's
+  // (k_collexc_filter: k-packets read it without asking for the record) and is left alone by the fill.
   int32_t ncold, ma_pool_slots;
   // [nlevels] the entry of the cooling list that holds the running sum after the level's collisional excitations (-1: no upward transitions)
   const int32_t *level_coolhi;

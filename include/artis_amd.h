@@ -653,6 +653,12 @@ int artis_amd_record_tiers(artis_amd_engine *eng, double *hot_fraction, int32_t 
  * bytes, beside the pool's size: a pool that runs near its size thrashes (artis_amd_last_pool_resets), one far below it could give its memory
  * to static records (a larger hot fraction). (ABI 6) */
 int artis_amd_last_pool_usage(artis_amd_engine *eng, int64_t *units_used, int64_t *units_cap);
+/* Absent ions: the population of the cell cache leaves out the static macro-atom records of the ions whose population in
+ * the cell is at most ARTIS_AMD_MA_ABSENT_EPS times their element's (negative: none are left out), and a packet that reaches such a record has it
+ * filled by the slow-path kernel -- the same bits the population would have written. *skipped: the records the last population (of the whole cache,
+ * or of the cells a tiled run made resident last) left out; *filled: the records the last artis_amd_update_packets_device call filled on demand.
+ * Either pointer may be NULL. (ABI 6: an added entry point; nothing that existed changes) */
+int artis_amd_last_absent_records(artis_amd_engine *eng, int64_t *skipped, int64_t *filled);
 /* Which forms of the thermal kernel (macro-atom walks + k-packet steps) the last artis_amd_update_packets_device call
  * launched, as a mask: the form is chosen per launch from the atomic data's size and the list's length, and a parity test has to know that the
  * form it means to check is the one that ran. (ABI 6) */

@@ -27,7 +27,7 @@ KERNELS = {  # substring of the mangled name -> label
 }
 # the hot loops, found in the source by their tags: (kernel substring, name, reference lines, file, tag, largest body in assembly lines)
 HOT = [
-    ("9k_thermalILi1024ELi1ELb0E", "transition loop", "macroatom.cc:385-577", "artis_engine.hip", "[census: transition loop]", 520),
+    ("9k_thermalILi1024ELi1ELb0E", "transition loop", "macroatom.cc:385-577", "thermal_round.inc", "[census: transition loop]", 520),
     ("6k_rpktILb1ELi768ELb0E", "opacity sum", "rpkt.cc:721-830", "physics.h", "[census: opacity sum]", 1100),
     ("6k_rpktILb1ELi768ELb0E", "line walk", "rpkt.cc:106-207", "physics.h", "[census: line walk]", 1500),
 ]
