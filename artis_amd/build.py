@@ -9,8 +9,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libartis_amd.so")
-SOURCES = ["artis_engine.hip", "physics.h", "tables.h", "model_build.h", "engine_config.h", "cache_residency.h", "cellcache_kernels.h", "spectra.h", "radfield_fit.h", "ion_balance.h", "decay_update.h", "deposition.h", "packet_init.h", "thermal_balance.h", "bf_heating.h", "ratecoeff_tables.h", "photoion.h",
-           "stage_cellcache.h", "stage_propagate.h", "stage_common.h", "stage_spectra.h", "stage_radfield.h", "stage_ionbal.h", "stage_decay.h", "stage_deposition.h", "stage_packet_init.h", "stage_thermal.h", "stage_bfheat.h", "stage_ratecoeff.h", "stage_photoion.h", "rpkt_round.inc", "thermal_round.inc", "work_pull.h"]
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc")))  # every source of csrc/: a new file cannot be forgotten
 # -ffp-contract=off: the operation order of physics.h is part of the parity contract (no FMA contraction).
 # -munsafe-fp-atomics: estimator adds become global_atomic_add_f64, not compare-and-swap loops.
 # -fno-slp-vectorize: with SLP vectorisation on, hipcc 7.2 packs the four int32 of a packet's hot line that follow each other
@@ -42,6 +41,10 @@ def so_path(preset: str = "classic") -> str:
     return SO if preset == "classic" else os.path.join(HERE, f"libartis_amd_{preset}.so")
 
 
+def preset_flags(preset: str) -> list:
+    return [] if preset == "classic" else [f"-DARTIS_PRESET_{preset.upper()}", f'-DARTIS_PRESET_NAME="{preset}"']
+
+
 def needs_build(preset: str = "classic") -> bool:
     so = so_path(preset)
     if not os.path.exists(so):
@@ -58,14 +61,13 @@ def build(force: bool = False, extra_flags=(), preset: str = "classic") -> str:
     if not force and not needs_build(preset):
         return so
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    pflags = [] if preset == "classic" else [f"-DARTIS_PRESET_{preset.upper()}", f'-DARTIS_PRESET_NAME="{preset}"']
     # one compiler run per library at a time (pytest-xdist workers, ranks of one node): the others wait, find it fresh and return;
     # the library appears under its name only when it is complete
     with open(so + ".lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         if force or needs_build(preset):
             tmp = f"{so}.{os.getpid()}.tmp"
-            cmd = [hipcc, *FLAGS, *pflags, *extra_flags, "-o", tmp, os.path.join(CSRC, "artis_engine.hip")]
+            cmd = [hipcc, *FLAGS, *preset_flags(preset), *extra_flags, "-o", tmp, os.path.join(CSRC, "artis_engine.hip")]
             subprocess.check_call(cmd)
             os.replace(tmp, so)
     return so

@@ -58,1858 +58,17 @@ thread_local std::string g_last_error;
 
 constexpr int BLOCK = 256;
 
-#include "cellcache_kernels.h"  // ------------------------------------------------ populate kernels
-
-// ------------------------------------------------------------------ packet layout kernels
-// The slot of a packet is not its index in the caller's array: slots are handed out in the order of the packets'
-// propagation cells at upload (perm[slot] = index in the caller's array), so that the lanes of a wave -- whose work list
-// is sorted by cell -- read and write neighbouring records. Thermal packets never leave their cell, r-packets drift away
-// from this order only gradually. perm == nullptr: identity.
-__global__ void __launch_bounds__(BLOCK) k_aos_to_rec(const artis_packet *aos, PktStore P, const int32_t *perm) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i < P.n) aos_to_rec(aos[perm ? perm[i] : i], P, i);
-}
-__global__ void __launch_bounds__(BLOCK) k_rec_to_aos(PktStore P, artis_packet *aos, const int32_t *perm) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i < P.n) rec_to_aos(P, i, aos[perm ? perm[i] : i]);
-}
-__global__ void __launch_bounds__(BLOCK) k_aos_cellkeys(const artis_packet *aos, int64_t n, int32_t ngrid, int32_t *ident, int32_t *keys) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= n) return;
-  ident[i] = (int32_t)i;
-  const int32_t c = aos[i].cellindex;
-  keys[i] = (c >= 0 && c < ngrid) ? c : 0;  // a packet of a type this path does not own may carry any cell index
-}
-
-// append (pi, key) of every lane with flag set to list[] / keys[], one atomic per wave (wave-ballot compaction)
-// (the sort counts the keys itself, in LDS, a tile of the list at a time: k_sort_tilehist)
-__device__ inline void wave_append(bool flag, int32_t pi, int32_t key, int32_t *list, int32_t *keys, int32_t *count) {
-  const unsigned long long mask = __ballot(flag);
-  if (mask == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int prefix = __popcll(mask & ((1ull << lane) - 1ull));
-  int base = 0;
-  const int leader = __ffsll((long long)mask) - 1;
-  if (lane == leader) base = atomicAdd(count, __popcll(mask));
-  base = __shfl(base, leader);
-  if (flag) {
-    list[base + prefix] = pi;
-    keys[base + prefix] = key;
-  }
-}
-
-// Blocks are dealt round-robin over the 8 XCDs (each with its own L2). The work lists are sorted by cell, so give
-// every XCD one contiguous eighth of the list: the per-cell tables its waves read then stay in that XCD's L2.
-// (Bijective remap of blockIdx -> list chunk; placement only changes speed, never results.)
-__device__ inline int64_t xcd_chunk(int64_t b, int64_t nb) {
-  const int64_t q = nb / 8, r = nb % 8, xcd = b % 8;
-  return ((xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
-}
-
-// Work lists, one per kind of pending work (physics.h NEXT_*). A kernel consumes the whole current list of ITS kind and
-// appends packets to the current lists of the other kinds; packets that stay with the kernel's own kind (launch budget
-// used up) go to that kind's alternate list, which becomes its current list afterwards. Every entry carries its sort
-// key (physics.h list_sort_key), written by the lane that still has the packet in registers, so that sorting a list
-// never touches the packet records.
-struct Lists {
-  int32_t *lst[NEXT_NKINDS];  // current list of each kind
-  int32_t *key[NEXT_NKINDS];  // ... and the sort keys of its entries
-  int32_t *counts;            // [NEXT_NKINDS] fill counts of the current lists
-  int32_t self_kind;          // kind of the running kernel
-  int32_t *self_list;         // its alternate list
-  int32_t *self_key;
-  int32_t *self_count;
-  int32_t kpkt_slot;          // list that takes k-packets: NEXT_KPKT, or NEXT_MA when k-packets and macro-atoms share the
-                              // fused thermal kernel
-  int32_t nubins;             // frequency bins of the r-packet list's keys (1 = sort by cell only)
-  int32_t mabins;             // sub-keys of the thermal list's keys (1 = sort by cell only)
-  int32_t numajor;            // > 0 = the cell groups of the grid: r-packet keys with the frequency bin as the MAJOR part (ARTIS_AMD_SORT_NUMAJOR=0: cell-major)
-  int32_t cellshift;          // ... groups of 2^cellshift cells with neighbouring indices share a key (ARTIS_AMD_SORT_CELLSHIFT)
-};
-// ma_sub: (tuning, ARTIS_AMD_MABINS=16) a sub-key 0..15 of a thermal-list entry below its cell, -1: none
-__device__ inline void append_by_kind(int kind, int32_t pi, int32_t cellindex, double nu_cmf, const Lists &L, int ma_sub = -1) {
-  const int slot = (kind == NEXT_KPKT) ? L.kpkt_slot : kind;
-  int32_t key = list_sort_key(cellindex, nu_cmf, (slot == NEXT_RPKT) ? L.nubins : 1);
-  if (slot == NEXT_RPKT && L.numajor > 0 && L.nubins > 1) key = ((key % SORT_NUBINS) * L.numajor) + ((key / SORT_NUBINS) >> L.cellshift);
-  if (slot == NEXT_MA && L.mabins > 1)
-    key = (cellindex * SORT_MABINS) + ((kind == NEXT_KPKT || ma_sub < 0) ? SORT_MABINS - 1 : (ma_sub & (SORT_MABINS - 1)));
-#pragma unroll
-  for (int k = 1; k < NEXT_NKINDS; k++) {
-    int32_t *dst = (k == L.self_kind) ? L.self_list : L.lst[k];
-    int32_t *dkey = (k == L.self_kind) ? L.self_key : L.key[k];
-    int32_t *cnt = (k == L.self_kind) ? L.self_count : (L.counts + k);
-    wave_append(slot == k, pi, key, dst, dkey, cnt);
-  }
-}
-// start of update_packets(): every resident packet is put on the list of its kind. A ContinuumOpacity never survives
-// into another call (rpkt.cc:1023 compares globals::timestep; the cell state may have changed in between).
-// (Called once per cell-cache tile: only the packets whose cell is in the resident tile are listed, physics.h classify().)
-__global__ void __launch_bounds__(BLOCK) k_classify(Env env, Lists L, int reset_chi) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  int kind = NEXT_DONE;
-  int32_t cellindex = 0;
-  double nu_cmf = 0.;
-  if (i < env.P.n) {
-    PktHot &h = env.P.hot[i];
-    const int type = h.type;
-    cellindex = h.cellindex;
-    nu_cmf = h.nu_cmf;
-    if (reset_chi && h.chi_mgi >= 0) h.chi_mgi = -1;
-    const bool active = type_handled(type) && h.prop_time < env.S.ts_end;
-    const bool waiting = h.pend != PEND_NONE || h.ma_level >= 0;
-    if (active && type_gamma(type) && !waiting) {
-      kind = NEXT_GAMMA;
-    } else if ((waiting || active) && in_tile(env, cellindex)) {
-      if (h.pend != PEND_NONE) {
-        kind = NEXT_SLOW;
-      } else if (h.ma_level >= 0) {
-        kind = NEXT_MA;
-      } else if (type == ARTIS_TYPE_RPKT) {
-        kind = NEXT_RPKT;
-      } else {
-        kind = kpkt_blackbody_case(env, type, cellindex) ? NEXT_BB : NEXT_KPKT;
-      }
-    }
-  }
-  append_by_kind(kind, (int32_t)i, cellindex, nu_cmf, L);
-}
-
-// Adaptive tiles (round 6): how many packets wait in every non-empty cell (the predicate of k_classify, whatever tile is resident), so
-// that the next tile can be put where most of them are; *other: packets that need no cache row (gamma-ray kinds, packets in empty cells)
-__global__ void __launch_bounds__(BLOCK) k_count_waiting(Env env, int32_t *counts, int32_t *other) {
-  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  if (i >= env.P.n) return;
-  const PktHot &h = env.P.hot[i];
-  const int type = h.type;
-  const bool active = type_handled(type) && h.prop_time < env.S.ts_end;
-  const bool waiting = h.pend != PEND_NONE || h.ma_level >= 0;
-  if (!(waiting || active)) return;
-  const int c = env.M.propcell_nonemptymgi[h.cellindex];
-  if ((active && type_gamma(type) && !waiting) || c < 0)
-    atomicAdd(other, 1);
-  else
-    atomicAdd(&counts[c], 1);
-}
-// ---- counting sort of a work list by its entries' keys (propagation cell, frequency bin).
-// Within a cell, r-packets are ordered by comoving frequency like the reference's own packet sort
-// (compare_packet_order, update_packets.cc:363): neighbouring lanes then walk the same part of the line list and
-// the same window of bound-free continua.
-// MANY keys (a 3D grid: cells x bins, millions): two passes whose only atomics are LDS atomics (device-wide atomics on random
-// addresses are carried out beyond the XCDs' L2s; one per entry was the whole cost of the sort they replaced).
-//  pass 1, by the key's high digit (at most SORT_HI_MAX buckets): k_sort_tilehist counts every tile of SORT_TILE entries in LDS and stores
-//    the counts in its column of a [bucket][tile] matrix; the k_scan_* kernels below scan the matrix; k_sort_tilescatter loads a tile's
-//    cursors from its scanned column and places (key, entry) pairs, bucket by bucket, in the intermediate buffer.
-//  pass 2, by the low digit inside each bucket (a contiguous segment of the intermediate buffer): k_sort_plan cuts the segments into chunks
-//    of at most SORT_SEG_CAP entries; k_sort_segments gives every chunk a workgroup that counts the segment's low digits in LDS, scans
-//    them there and writes its chunk's entries to their places. A segment of several chunks is counted by each of its workgroups (reads
-//    only, from the L2), so a skewed list costs reads, never a workgroup that places a whole bucket on its own.
-// Nothing is zeroed per sort, and the scans cover buckets x tiles counters instead of one per key.
-constexpr int SORT_HI_BITS = 11;
-constexpr int SORT_HI_MAX = 1 << SORT_HI_BITS;
-constexpr int SORT_LO_BITS_MAX = 14;  // pass 2's two LDS tables: 2 x 2^14 x 4 B = 128 KB of a workgroup's 160 KB
-constexpr int64_t SORT_MAX_KEYS = (int64_t)1 << (SORT_HI_BITS + SORT_LO_BITS_MAX);  // 2^25: a 100^3 grid x SORT_NUBINS
-constexpr int SORT_TILE = 8192;     // entries per workgroup of pass 1
-constexpr int SORT_TB = 512;
-constexpr int SORT_SEG_CAP = 8192;  // entries a workgroup of pass 2 places
-__global__ void __launch_bounds__(SORT_TB) k_sort_tilehist(const int32_t *keys, int32_t n, int lobits, int nb, int32_t ntiles, int32_t *mat) {
-  __shared__ int32_t h[SORT_HI_MAX];
-  for (int b = threadIdx.x; b < nb; b += SORT_TB) h[b] = 0;
-  __syncthreads();
-  const int64_t lo = (int64_t)blockIdx.x * SORT_TILE, hi = (lo + SORT_TILE < n) ? lo + SORT_TILE : n;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += SORT_TB) atomicAdd(&h[keys[i] >> lobits], 1);
-  __syncthreads();
-  for (int b = threadIdx.x; b < nb; b += SORT_TB) mat[(int64_t)b * ntiles + blockIdx.x] = h[b];
-}
-// mat: the scanned matrix, mat[b][tile] = where the tile's first entry of bucket b goes
-__global__ void __launch_bounds__(SORT_TB) k_sort_tilescatter(const int32_t *list, const int32_t *keys, int32_t n, int lobits, int nb, int32_t ntiles,
-                                                              const int32_t *mat, int2 *pairs) {
-  __shared__ int32_t h[SORT_HI_MAX];
-  for (int b = threadIdx.x; b < nb; b += SORT_TB) h[b] = mat[(int64_t)b * ntiles + blockIdx.x];
-  __syncthreads();
-  const int64_t lo = (int64_t)blockIdx.x * SORT_TILE, hi = (lo + SORT_TILE < n) ? lo + SORT_TILE : n;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += SORT_TB) {
-    const int32_t k = keys[i];
-    pairs[atomicAdd(&h[k >> lobits], 1)] = make_int2(k, list[i]);
-  }
-}
-// one workgroup: seg[b] = where bucket b begins (seg[nb] = n), chunk_base[b] = chunks of the buckets before it (chunk_base[nb] = all chunks)
-__global__ void __launch_bounds__(1024) k_sort_plan(const int32_t *mat, int32_t ntiles, int nb, int32_t n, int32_t *seg, int32_t *chunk_base) {
-  __shared__ int32_t part[1024];
-  const int t = threadIdx.x;
-  int32_t c[2];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const int b = 2 * t + k;
-    c[k] = 0;
-    if (b < nb) {
-      const int32_t s0 = mat[(int64_t)b * ntiles], s1 = (b + 1 < nb) ? mat[(int64_t)(b + 1) * ntiles] : n;
-      seg[b] = s0;
-      c[k] = (s1 - s0 + SORT_SEG_CAP - 1) / SORT_SEG_CAP;
-    }
-  }
-  if (t == 0) seg[nb] = n;
-  part[t] = c[0] + c[1];
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const int32_t add = (t >= off) ? part[t - off] : 0;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
-  const int32_t run = part[t] - c[0] - c[1];
-  if (2 * t < nb) chunk_base[2 * t] = run;
-  if (2 * t + 1 < nb) chunk_base[2 * t + 1] = run + c[0];
-  if (t == 1023) chunk_base[nb] = part[1023];
-}
-// a workgroup per chunk; sm[]: the segment's count of every low digit, then the cursors; behind it, for a later chunk of a segment, the
-// counts of the chunks before it
-__global__ void __launch_bounds__(BLOCK) k_sort_segments(const int2 *pairs, int lobits, int nb, const int32_t *seg, const int32_t *chunk_base,
-                                                         int32_t *out) {
-  extern __shared__ int32_t sm[];
-  __shared__ int32_t part[BLOCK];
-  __shared__ int s_bucket;
-  const int t = threadIdx.x;
-  const int nlow = 1 << lobits, mask = nlow - 1;
-  if (t == 0) {
-    int b = -1;
-    if ((int32_t)blockIdx.x < chunk_base[nb]) {  // the last bucket whose chunks begin at or before this one
-      int lo = 0, hi = nb - 1;
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (chunk_base[mid] <= (int32_t)blockIdx.x)
-          lo = mid;
-        else
-          hi = mid - 1;
-      }
-      b = lo;
-    }
-    s_bucket = b;
-  }
-  __syncthreads();
-  const int b = s_bucket;
-  if (b < 0) return;
-  const int32_t s0 = seg[b], s1 = seg[b + 1];
-  const int32_t c0 = s0 + ((int32_t)blockIdx.x - chunk_base[b]) * SORT_SEG_CAP, c1 = (s1 - c0 > SORT_SEG_CAP) ? c0 + SORT_SEG_CAP : s1;
-  int32_t *tot = sm, *before = sm + nlow;
-  const bool later = c0 > s0;
-  for (int d = t; d < nlow; d += BLOCK) {
-    tot[d] = 0;
-    if (later) before[d] = 0;
-  }
-  __syncthreads();
-  for (int32_t i = s0 + t; i < c0; i += BLOCK) {
-    const int d = pairs[i].x & mask;
-    atomicAdd(&tot[d], 1);
-    atomicAdd(&before[d], 1);
-  }
-  for (int32_t i = c0 + t; i < s1; i += BLOCK) atomicAdd(&tot[pairs[i].x & mask], 1);
-  __syncthreads();
-  // exclusive scan of tot[]: a run of digits per thread, the threads' sums, the runs again
-  const int per = (nlow + BLOCK - 1) / BLOCK;
-  const int d0 = (t * per < nlow) ? t * per : nlow, d1 = (d0 + per < nlow) ? d0 + per : nlow;
-  int32_t sum = 0;
-  for (int d = d0; d < d1; d++) sum += tot[d];
-  part[t] = sum;
-  __syncthreads();
-  for (int off = 1; off < BLOCK; off <<= 1) {
-    const int32_t add = (t >= off) ? part[t - off] : 0;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
-  int32_t run = part[t] - sum;
-  for (int d = d0; d < d1; d++) {
-    const int32_t v = tot[d];
-    tot[d] = run + (later ? before[d] : 0);
-    run += v;
-  }
-  __syncthreads();
-  for (int32_t i = c0 + t; i < c1; i += BLOCK) {
-    const int2 p = pairs[i];
-    out[s0 + atomicAdd(&tot[p.x & mask], 1)] = p.y;
-  }
-}
-// exclusive scan of a table of counts (the few-keys histogram, the many-keys matrix) in three steps: per-block scan of SCAN_TILE
-// counts, scan of the block totals (one block), add the block offsets. A table of one tile is done after the first step.
-constexpr int SCAN_TILE = 8192;  // keys per block of 1024 threads (8 per thread)
-__global__ void __launch_bounds__(1024) k_scan_tiles(int32_t *hist, int32_t nkeys, int32_t *tile_totals) {
-  __shared__ int32_t part[1024];
-  const int t = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)t * 8;
-  int32_t v[8];
-  int32_t sum = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    v[k] = (base + k < nkeys) ? hist[base + k] : 0;
-    sum += v[k];
-  }
-  part[t] = sum;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan of the per-thread sums
-    const int32_t add = (t >= off) ? part[t - off] : 0;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
-  int32_t run = part[t] - sum;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    if (base + k < nkeys) hist[base + k] = run;
-    run += v[k];
-  }
-  if (t == 1023) tile_totals[blockIdx.x] = part[1023];
-}
-__global__ void __launch_bounds__(1024) k_scan_totals(int32_t *tile_totals, int32_t ntiles) {
-  __shared__ int32_t part[1024];
-  const int t = threadIdx.x;
-  int32_t carry = 0;
-  for (int start = 0; start < ntiles; start += 1024) {
-    const int i = start + t;
-    const int32_t v = (i < ntiles) ? tile_totals[i] : 0;
-    part[t] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      const int32_t add = (t >= off) ? part[t - off] : 0;
-      __syncthreads();
-      part[t] += add;
-      __syncthreads();
-    }
-    if (i < ntiles) tile_totals[i] = carry + part[t] - v;
-    carry += part[1023];
-    __syncthreads();
-  }
-}
-__global__ void __launch_bounds__(1024) k_scan_add(int32_t *hist, int32_t nkeys, const int32_t *tile_totals) {
-  const int32_t off = tile_totals[blockIdx.x];
-  const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * 8;
-#pragma unroll
-  for (int k = 0; k < 8; k++)
-    if (base + k < nkeys) hist[base + k] += off;
-}
-// The same two steps for FEW keys (1D and 2D models, small 3D grids: a few hundred cells). With one global atomic per
-// entry the entries of a cell serialise on its counter (measured on a 6^3 grid with 1e7 packets: 7 ms per sort kernel,
-// 36 % of the GPU time of a step, against 0.2 ms on the 50^3 grid). Here a workgroup counts its contiguous chunk of the
-// list in LDS and touches each global counter once.
-constexpr int SORT_LDS_KEYS = 8192;
-constexpr int SORT_LDS_GRID = 2048;
-__global__ void __launch_bounds__(BLOCK) k_sort_hist_lds(const int32_t *keys, int32_t n, int32_t *hist, int32_t nkeys) {
-  __shared__ int32_t h[SORT_LDS_KEYS];
-  for (int k = threadIdx.x; k < nkeys; k += BLOCK) h[k] = 0;
-  __syncthreads();
-  const int64_t chunk = ((int64_t)n + gridDim.x - 1) / gridDim.x;
-  const int64_t lo = chunk * blockIdx.x, hi = (lo + chunk < n) ? lo + chunk : n;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += BLOCK) atomicAdd(&h[keys[i]], 1);
-  __syncthreads();
-  for (int k = threadIdx.x; k < nkeys; k += BLOCK)
-    if (h[k] != 0) atomicAdd(&hist[k], h[k]);
-}
-__global__ void __launch_bounds__(BLOCK) k_sort_scatter_lds(const int32_t *list, const int32_t *keys, int32_t n, int32_t *offsets, int32_t *out,
-                                                            int32_t nkeys) {
-  __shared__ int32_t h[SORT_LDS_KEYS];
-  for (int k = threadIdx.x; k < nkeys; k += BLOCK) h[k] = 0;
-  __syncthreads();
-  const int64_t chunk = ((int64_t)n + gridDim.x - 1) / gridDim.x;
-  const int64_t lo = chunk * blockIdx.x, hi = (lo + chunk < n) ? lo + chunk : n;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += BLOCK) atomicAdd(&h[keys[i]], 1);
-  __syncthreads();
-  for (int k = threadIdx.x; k < nkeys; k += BLOCK)  // the workgroup's range of each key's output
-    if (h[k] != 0) h[k] = atomicAdd(&offsets[k], h[k]);
-  __syncthreads();
-  for (int64_t i = lo + threadIdx.x; i < hi; i += BLOCK) out[atomicAdd(&h[keys[i]], 1)] = list[i];
-}
-inline int sort_lds_grid(int64_t n) {
-  const int64_t b = (n + BLOCK - 1) / BLOCK;
-  return (int)(b < SORT_LDS_GRID ? b : SORT_LDS_GRID);
-}
-
-// ------------------------------------------------------------------ the propagation kernels
-// They are PERSISTENT, work-pulling kernels: a lane that has finished with its packet (budget used up, packet handed
-// to another list, escaped, end of timestep) immediately takes the next packet of the work list instead of idling
-// until the slowest lane of its wave is done. The list is sorted by cell and cut into `nchunks` contiguous chunks with
-// one cursor each -- one chunk per WAVE when the list is long enough: a wave then walks its own run of cells, so at any
-// time its lanes sit in one or two cells and read the same cell-cache lines. The chunks of the waves of one XCD are
-// adjacent (blocks b and b+8 share an XCD, so each XCD's L2 sees one contiguous range of cells). A wave whose chunk is
-// used up steals from the other chunks, its own XCD's first. Placement only affects speed, never results.
-#ifndef ARTIS_RPKT_WAVES
-#define ARTIS_RPKT_WAVES 2
-#endif
-#ifndef ARTIS_THERMAL_WAVES
-#define ARTIS_THERMAL_WAVES 4
-#endif
-#include "work_pull.h"  // MAX_CHUNKS, Puller, puller_init(), chunk_at(), pull(): handing the list's indices to the waves
-// before a launch of the kernel of one kind: its own list's counter, the alternate counter and the chunk cursors (and the flag) start at zero
-__global__ void __launch_bounds__(BLOCK) k_launch_reset(int32_t *count, int kind, int32_t *cursors) {
-  for (int i = threadIdx.x; i < PULL_SLOTS; i += BLOCK) cursors[i] = 0;
-  if (threadIdx.x == 0) {
-    count[kind] = 0;
-    count[NEXT_NKINDS] = 0;
-  }
-}
-// chunks for a list of n entries consumed by `nwaves` waves: one per wave, fewer when the list is short
-inline int chunks_for(int64_t n, int nwaves) {
-  int64_t c = std::min<int64_t>(nwaves, n / 128);
-  c = std::max<int64_t>(8, (c / 8) * 8);
-  return (int)std::min<int64_t>(c, MAX_CHUNKS);
-}
-
-#ifndef ARTIS_RPKT_SPLIT_ABSORB
-#define ARTIS_RPKT_SPLIT_ABSORB 0  // (1: measured round 5: k_rpkt 265 -> 258 ms, k_slow 16 -> 32 ms, step unchanged, scratch unchanged: off) free-free / bound-free absorptions of r-packets carried out by the slow-path kernel (physics.h PEND_RPKT_ABSORB)
-#endif
-// r-packets in flight: boundary distance, continuum opacity, line-by-line Sobolev walk, estimators, events.
-// CONT_LDS: the static table of bound-free continua (ContPack: edge frequency, target probability, cross-section table,
-// ground-continuum index; 32 B per continuum) is copied into LDS once per workgroup and every read of it in the opacity
-// sum (rpkt.cc:721, two of the ~five reads per continuum visited) is a ds_read that does not touch the vector L1.
-constexpr int CONT_LDS_MAX = 2048;  // continua (64 KB per workgroup, two workgroups per CU)
-// LDS accumulators of per-cell estimators for models with few cells (physics.h Env::cellest_lds)
-constexpr int RPKT_CELLEST_CAP = 512;      // cells: 3 estimators x 8 B x 512 = 12 KB per workgroup (next to the 64 KB above)
-constexpr int RPKT_CELLEST_CAP_NOCONT = 3072;  // ... 72 KB in the kernel form without the continuum table in LDS
-constexpr int GAMMA_CELLEST_CAP = 2048;    // cells: 16 KB per workgroup
-constexpr int THERMAL_CELLEST_CAP = 4096;  // cells: 32 KB per workgroup, four workgroups per CU
-__device__ inline void cellest_begin(Env &env, double *lds, int n, int nthreads, const double *a0, const double *a1 = nullptr,
-                                     const double *a2 = nullptr) {
-  const int nkinds = a2 ? 3 : (a1 ? 2 : 1);
-  for (int i = threadIdx.x; i < n * nkinds; i += nthreads) lds[i] = 0.;
-  env.cellest_lds = lds;
-  env.cellest_n = n;
-  env.cellest_owner[0] = a0;
-  env.cellest_owner[1] = a1;
-  env.cellest_owner[2] = a2;
-}
-__device__ inline void scalars_begin(Env &env, double *lds) {
-  if (threadIdx.x < ARTIS_NSCALARS) lds[threadIdx.x] = 0.;
-  env.scalars_lds = (env.scalars_in_lds && env.E.scalars != nullptr) ? lds : nullptr;
-}
-__device__ inline void scalars_flush(const Env &env) {  // after a __syncthreads()
-  if (env.scalars_lds != nullptr && threadIdx.x < ARTIS_NSCALARS && env.scalars_lds[threadIdx.x] != 0.)
-    unsafeAtomicAdd(&env.E.scalars[threadIdx.x], env.scalars_lds[threadIdx.x]);
-}
-// the estimator form k_thermal<.., TABLES_LDS> takes (its own choice at the top of the kernel): artis_amd_last_estimator_forms
-inline int32_t thermal_est_form(const Env &env, int tables_lds) {
-  if (env.cellest_n_t > 0) return ARTIS_AMD_EST_THERMAL_LDS;
-  return (tables_lds != 2 && env.estcache_on) ? ARTIS_AMD_EST_THERMAL_WAVECACHE : ARTIS_AMD_EST_THERMAL_GLOBAL;
-}
-// call after a __syncthreads(): the workgroup's sums of one estimator go to the global array
-__device__ inline void cellest_flush(const Env &env, int kind, double *global_array, int nthreads) {
-  for (int c = threadIdx.x; c < env.cellest_n; c += nthreads) {
-    const double v = env.cellest_lds[(kind * env.cellest_n) + c];
-    if (v != 0.) unsafeAtomicAdd(&global_array[(int64_t)c * env.est_stride], v);
-  }
-}
-// One workgroup of 768 threads per CU: 3 waves/SIMD at 168 VGPRs (the LDS tables allow two workgroups per CU, so 256-thread
-// workgroups stop at 2 waves/SIMD whatever their registers). Measured against 256 x 2 (2 waves/SIMD, 256 VGPRs): k_rpkt
-// 352 -> 339 ms (classic), 398 -> 379 (kilonova_lte), k_rpkt + k_bfest_dense 825 -> 781 (nltenebular); 1024 x 1 (4
-// waves/SIMD, 128 VGPRs, 768 B of scratch): 457 ms.
-#ifndef ARTIS_RPKT_TB
-#define ARTIS_RPKT_TB 768  // threads per workgroup of k_rpkt ...
-#define ARTIS_RPKT_WGS 1   // ... and workgroups per CU
-#endif
-// LINE_LDS (ARTIS_AMD_LINELDS=1; instead of the continuum table, which it leaves no room for): the line list's frequencies
-// (globals::linelist nu, rpkt.cc:106-207 get_possible_event: one of the two reads per line visited, the other being the cell's
-// population factor) in LDS, the whole list when it has at most LINE_LDS_MAX lines. What a per-cell, per-wave WINDOW of
-// {frequency, population factor} pairs would need -- many lanes of a wave in one cell and one stretch of the list -- the
-// cell-sorted work list does not give: a wave's 64 packets sit in ~21 cells (2.6 lanes per cell) and
-// anywhere in the spectrum. Measured slower than the continuum table in LDS: profiles/r04/line_window.md.
-constexpr int LINE_LDS_MAX = 14336;  // lines (112 KB)
-template <bool CONT_LDS, int TB, bool LINE_LDS = false>
-__global__ void __launch_bounds__(TB, ARTIS_RPKT_WGS) k_rpkt(Env env, const int32_t *list, int32_t n, Lists next,
-                                                                   unsigned long long *gstats, int budget, int32_t *cursors, int nchunks,
-                                                                   int drain_budget) {
-  __shared__ stat_t lstats[ARTIS_NSTATS];
-  __shared__ ContPack lds_cont[CONT_LDS ? CONT_LDS_MAX : 1];
-  __shared__ double lds_line_nu[LINE_LDS ? LINE_LDS_MAX : 1];
-  __shared__ double lds_cellest[3 * ((CONT_LDS || LINE_LDS) ? RPKT_CELLEST_CAP : RPKT_CELLEST_CAP_NOCONT)];
-  constexpr int NEC = LINE_LDS ? 1 : ESTCACHE_SLOTS;       // (the line list in LDS leaves no room for the caches)
-  __shared__ double lds_estcache[(TB / 64) * NEC * 3];   // per wave: the accumulators of ESTCACHE_SLOTS cells (physics.h Env::estcache) ...
-  __shared__ int32_t lds_esttag[(TB / 64) * NEC * 2];    // ... whose cells they are, and the claims of an eviction
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  cellest_begin(env, lds_cellest, env.cellest_n_r, TB, env.E.J, env.E.nuJ, env.E.ffheatingestimator);
-  env.estcache = nullptr;
-  env.estcache_nv = 0;
-  if (!LINE_LDS && env.estcache_on && env.cellest_n_r == 0) {  // many cells: the wave's own cache instead of the workgroup's array
-    const int w = threadIdx.x >> 6;
-    env.estcache_nv = 3;
-    env.estcache = lds_estcache + (w * NEC * 3);
-    env.estcache_tag = lds_esttag + (w * NEC * 2);
-    for (int l = threadIdx.x & 63; l < NEC; l += 64) {
-      env.estcache_tag[l] = -1;
-      env.estcache_tag[NEC + l] = -1;
-      env.estcache[(l * 3) + 0] = 0.;
-      env.estcache[(l * 3) + 1] = 0.;
-      env.estcache[(l * 3) + 2] = 0.;
-    }
-  }
-  if (LINE_LDS) {
-    for (int i = threadIdx.x; i < env.M.nlines; i += TB) lds_line_nu[i] = env.M.line_nu[i];
-    env.M.line_nu = lds_line_nu;
-  }
-  if (CONT_LDS) {
-    const D2 *src = (const D2 *)env.M.cont_pack;
-    D2 *dst = (D2 *)lds_cont;
-    for (int i = threadIdx.x; i < env.M.nbfcontinua * 2; i += TB) dst[i] = src[i];
-    env.M.cont_pack = lds_cont;
-    env.cont_in_lds = 1;
-  }
-  __syncthreads();
-  env.stats = lstats;
-  const double ts_end = env.S.ts_end;
-  Puller q;
-  puller_init(q, n, nchunks);
-  bool have = false;
-  bool drained = false;  // the launch's work list is used up (k_thermal: same hand-over to the next launch)
-  int32_t pi = 0;
-  int steps = 0;
-  Pkt p;
-  Chi x;
-#ifdef ARTIS_PROFILE
-  long long tprev = clock64();
-#endif
-  while (true) {
-    const int32_t idx = pull(q, !have, cursors);
-    if (idx >= 0) {
-      pi = list[idx];
-      pkt_load(env.P, pi, p);
-      chi_load(env.P, pi, p, x);
-      steps = 0;
-      have = true;
-    }
-    if (!drained && q.exhausted) {
-      drained = true;
-      if ((threadIdx.x & 63) == 0) __hip_atomic_store(&cursors[MAX_CHUNKS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (!drained && drain_budget < budget && (steps & 1) == 0)
-      drained = __hip_atomic_load(&cursors[MAX_CHUNKS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-    if (!__any(have)) {
-      if (q.exhausted) break;
-      continue;
-    }
-#define ROUND_LEAVE(n) ((n) >= budget || (drained && (n) >= drain_budget))
-#define ROUND_PUT(kind_, pi_) append_by_kind(kind_, pi_, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion))
-#include "rpkt_round.inc"
-#undef ROUND_LEAVE
-#undef ROUND_PUT
-  }
-  __syncthreads();
-  if (env.estcache != nullptr) {  // the wave's accumulators go to the cells' records: a lane per slot
-    for (int l = threadIdx.x & 63; l < NEC; l += 64) {
-      const int cell = env.estcache_tag[l];
-      if (cell < 0) continue;
-      const double s0 = env.estcache[(l * 3) + 0], s1 = env.estcache[(l * 3) + 1], s2 = env.estcache[(l * 3) + 2];
-      if (s0 != 0.) unsafeAtomicAdd(&env.E.J[(int64_t)cell * env.est_stride], s0);
-      if (s1 != 0.) unsafeAtomicAdd(&env.E.nuJ[(int64_t)cell * env.est_stride], s1);
-      if (s2 != 0.) unsafeAtomicAdd(&env.E.ffheatingestimator[(int64_t)cell * env.est_stride], s2);
-    }
-  }
-  cellest_flush(env, CELLEST_J, env.E.J, TB);
-  cellest_flush(env, CELLEST_NUJ, env.E.nuJ, TB);
-  cellest_flush(env, CELLEST_FFHEAT, env.E.ffheatingestimator, TB);
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-
-#if ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON
-// The deferred updates of the detailed bound-free estimators (radfield.cc:215). A record's continua are the kept ones of
-// its window [begin, end); LPR lanes share the record (cell, frequency, weight) and take one kept continuum each, so the
-// lanes are busy however long the window is (a lane-per-packet loop ran at 17 % of the lanes). Which continuum is the
-// k-th kept one of the window comes from two small per-cell tables made with the keep bitmap (k_keptlist): the kept
-// continua as a list, and the number of kept continua below each bitmap word -- two reads and two bit counts give the
-// window's places [r0, r1) in the list. (Before: prefix sums of the words' bit counts over the lanes, a bisection with six
-// ds_bpermute and a select-k-th-bit per lane and round: 2.5x the VALU instructions.) The contributions are the ones
-// update_bfestimators() would have added in place (same arithmetic); only the order of the f64 atomic additions differs.
-// (Keeping a cell's sums in LDS across a run of records of the same cell -- per wave, or per workgroup with ds_add_f64 --
-// was measured and lost, 651 / 427 ms against 364 ms; so did sorting the records by cell first and summing a cell's whole
-// run in an LDS row, 1101 vs 989 ms for k_rpkt + this kernel, profiles/r03/bfest_sorted_lds_rows.patch. Compiled out, the
-// additions are worth 98 of the 989 ms.)
-// CONT_LDS: the static continuum table (ContPack, two of a contribution's ~six 16-byte reads) is staged in LDS by a
-// workgroup of DENSE_TB threads, one per CU.
-constexpr int DENSE_TB = 1024;
-// LPR lanes per record: a window holds ~30 kept continua (ARTIS_AMD_DENSE_LPR = 64, 32 or 16)
-#ifndef ARTIS_DENSE_WGS
-#define ARTIS_DENSE_WGS 2  // workgroups of DENSE_TB threads per CU: 8 waves/SIMD at 60 VGPRs (1: 4 waves/SIMD; k_rpkt + this kernel 781 -> 774 ms)
-#endif
-template <bool CONT_LDS, int TB, int LPR>
-__global__ void __launch_bounds__(TB, (TB == DENSE_TB ? ARTIS_DENSE_WGS : 1)) k_bfest_dense(Env env) {
-  __shared__ ContPack lds_cont[CONT_LDS ? CONT_LDS_MAX : 1];
-  if (CONT_LDS) {
-    const D2 *src = (const D2 *)env.M.cont_pack;
-    D2 *dst = (D2 *)lds_cont;
-    for (int i = threadIdx.x; i < env.M.nbfcontinua * 2; i += TB) dst[i] = src[i];
-    env.M.cont_pack = lds_cont;
-    env.cont_in_lds = 1;
-    __syncthreads();
-  }
-  static_assert(LPR == 64 || LPR == 32 || LPR == 16, "lanes per record");
-  const DevModel &M = env.M;
-  const int n = min(*env.bfev_count, env.bfev_cap);
-  const int lane = threadIdx.x & (LPR - 1);
-  const int unit = (blockIdx.x * TB + threadIdx.x) / LPR;
-  const int nunits = gridDim.x * (TB / LPR);
-  for (int ei = unit; ei < n; ei += nunits) {
-    const BfEvent ev = env.bfev[ei];
-    const int c = ev.c;
-    const double nu = ev.nu;
-    const float T_e = env.C.Te[c];
-    // the record's continua are the kept ones of [begin, end): places [r0, r1) of the cell's list of kept continua
-    int r0, r1;
-    kept_range(env, c, ev.begin, ev.end, r0, r1);
-    const double ex = exp(-HOVERKB * nu / T_e);
-    const bool split_usable = (ex >= DBLMIN);
-    const int32_t *list = env.K.allcont_keptlist + (krow(env, c) * M.nbfcontinua);
-    const D2 *keptpair = env.K.allcont_keptpair + (krow(env, c) * M.nbfcontinua);
-    // the sums go to the continuum's place in the list when the call keeps them there (all cells resident), else to its
-    // estimator: ~30 additions of a record then fall into 4-5 neighbouring 64-byte sectors instead of ~16 scattered ones
-    // (k_rpkt + this kernel 978 -> 858 ms per step; with the additions compiled out: 891)
-    double *dst = env.bfrate_kept ? env.bfrate_kept + ((int64_t)c * M.nbfcontinua) : env.E.bfrate_raw + ((int64_t)c * M.nbfestim);
-    for (int r = r0 + lane; r < r1; r += LPR) {
-      const int i = list[r];
-      const double ep = keptpair[r].y;
-      const int bi = bfestimindex(M, i);
-      if (bi >= 0) ARTIS_EST_ADD(&dst[env.bfrate_kept ? r : bi], bf_sigma_contr_ep(env, c, i, nu, T_e, ex, split_usable, ep) * ev.w);
-    }
-  }
-}
-// the sums kept by place in the list go to their estimators (one wave per cell; the places are left zero for the next call)
-__global__ void __launch_bounds__(BLOCK) k_bfrate_expand(Env env) {
-  const int64_t wave = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  const DevModel &M = env.M;
-  if (wave >= M.npts_nonempty) return;
-  const int c = (int)wave;
-  const int nw = M.nkeepwords;
-  const int nkept = env.K.allcont_keepprefix[(krow(env, c) * nw) + nw - 1] + __popcll(env.K.allcont_keepbits[(krow(env, c) * nw) + nw - 1]);
-  const int32_t *list = env.K.allcont_keptlist + (krow(env, c) * M.nbfcontinua);
-  double *kept = env.bfrate_kept + ((int64_t)c * M.nbfcontinua);
-  double *dst = env.E.bfrate_raw + ((int64_t)c * M.nbfestim);
-  for (int r = lane; r < nkept; r += 64) {
-    const double v = kept[r];
-    if (v != 0.) {
-      dst[bfestimindex(M, list[r])] += v;  // (a continuum without an estimator was never added to: v == 0)
-      kept[r] = 0.;
-    }
-  }
-}
-#endif
-
-// gamma packets (and the non-thermal deposits they end in): one do_gamma() call per iteration, same persistent
-// work-pulling form as k_rpkt; a packet that has thermalised leaves as a k-packet for the thermal list
-#ifndef ARTIS_GAMMA_WAVES
-#define ARTIS_GAMMA_WAVES 2
-#endif
-__global__ void __launch_bounds__(BLOCK, ARTIS_GAMMA_WAVES) k_gamma(Env env, const int32_t *list, int32_t n, Lists next,
-                                                                     unsigned long long *gstats, int budget, int32_t *cursors, int nchunks) {
-  __shared__ stat_t lstats[ARTIS_NSTATS];
-  __shared__ double lds_cellest[GAMMA_CELLEST_CAP];
-  __shared__ double lds_scalars[ARTIS_NSCALARS];
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  scalars_begin(env, lds_scalars);
-  cellest_begin(env, lds_cellest, env.cellest_n_g, BLOCK, env.E.dep_estimator_gamma);
-  __syncthreads();
-  env.stats = lstats;
-  const double ts_end = env.S.ts_end;
-  Puller q;
-  puller_init(q, n, nchunks);
-  bool have = false;
-  int32_t pi = 0;
-  int steps = 0;
-  Pkt p;
-  while (true) {
-    const int32_t idx = pull(q, !have, cursors);
-    if (idx >= 0) {
-      pi = list[idx];
-      pkt_load(env.P, pi, p);
-      steps = 0;
-      have = true;
-    }
-    if (!__any(have)) {
-      if (q.exhausted) break;
-      continue;
-    }
-    int kind = NEXT_DONE;
-    int32_t out_pi = 0;
-    if (have) {
-      bool go = gamma_can_continue(p, ts_end);
-      if (go) {
-        go = gamma_iter(env, p, pi);
-        steps++;
-      }
-      if (!go || steps >= budget) {
-        pkt_store(env.P, pi, p);
-        kind = classify(env, p, ts_end);
-        out_pi = pi;
-        have = false;
-      }
-    }
-    append_by_kind(kind, out_pi, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion));
-  }
-  __syncthreads();
-  cellest_flush(env, CELLEST_DEPGAMMA, env.E.dep_estimator_gamma, BLOCK);
-  scalars_flush(env);
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-
-// Thermal packets (k-packets and walking macro-atoms) are advanced by ONE persistent kernel, so that the k-packet ->
-// macro-atom -> k-packet cycle (tens of times per packet and timestep, kpkt.cc:51) needs no kernel boundary.
-//
-// Staging macro-atom records in LDS was built and measured in rounds 2 and 3 (per-workgroup slots holding the hot levels'
-// records of the cells in flight, k_thermal<true>; and k_thermal_q, walk contexts in per-wave LDS slots with lanes refilled
-// inside the transition loop): both bit-identical, both slower (profiles/r02/lds_staging.md,
-// profiles/r03/k_thermal_lane_compaction.md). Round 4 took the cumulative sums and targets those variants staged out of
-// the records altogether (tables.h), and the variants with them.
-#ifndef ARTIS_THERMAL_WAVES
-#define ARTIS_THERMAL_WAVES 4
-#endif
-// Fused thermal kernel, phase form (physics.h thermal_iter): up to ARTIS_MA_PHASE macro-atom transitions, then one
-// k-packet step, per iteration; lanes take a new packet between iterations. Workgroups of TB threads on the XCD chunks.
-#ifndef ARTIS_THERMAL_TB
-#define ARTIS_THERMAL_TB BLOCK                 // threads per workgroup of k_thermal,
-#define ARTIS_THERMAL_EU ARTIS_THERMAL_WAVES   // the waves per SIMD its registers are to allow (512 / EU VGPRs) ...
-#define ARTIS_THERMAL_WGS ARTIS_THERMAL_WAVES  // ... and its workgroups per CU
-#endif
-// 1: k_thermal holds no rate-coefficient code: a search its filters cannot decide (3e-4 per transition) is handed to the slow-path
-// kernel with the draw in the packet's pend fields (physics.h PEND_MA_SEARCH / _RADSEARCH / PEND_KPKT_COLLEXC), which re-adds the sums
-// and carries on; the packet is back on the thermal list for the next launch. With the code inlined here the kernel spilled 122
-// instead of 21 registers, reloaded around every phase: 200 GB of scratch traffic per step.
-// (Not in the builds with detailed bound-free estimators -- the nltenebular family: their steps are made of twice as many launch rounds,
-// and every hand-over costs a packet the rest of its launch: measured 1417 ms with, 1403 without.)
-#ifndef ARTIS_THERMAL_SPLIT_EXACT
-#define ARTIS_THERMAL_SPLIT_EXACT (ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON ? 0 : 1)
-#endif
-#ifndef ARTIS_MA_DEFER_EXACT
-#define ARTIS_MA_DEFER_EXACT 1  // the re-adding of a search's sums outside the transition loop (physics.h ma_jump_internal<true>)
-#endif
-// TABLES_LDS: the two static tables a transition's target is read from -- the target level of every entry of alltrans
-// (2 bytes) and the LevelPack of every level (16 bytes) -- are copied into LDS once per workgroup (one workgroup of 1024
-// threads per CU: the same 4 waves/SIMD at 128 VGPRs), and a transition reads its target with two ds_reads instead of a
-// 16-byte gather from the static target table in L2: of a transition's three dependent reads (action filter; the
-// direction's filter, in the sector the first one brought; the target) one long wait is left. For atomic data whose
-// tables fit (MA_LDS_LEVELS / MA_LDS_TRANS: the bench's 1567 levels and 27 238 entries take 80 KB); larger data keep the
-// target table in HBM. Static tables, the same for every cell: nothing to stage per cell (what lost in rounds 2-3).
-// TABLES_LDS = 2: atomic data whose alltrans table does not fit (the 110 860-line set: 221 720 entries) keep the 2-byte target
-// levels in HBM (443 KB instead of the 3.5 MB of 16-byte targets: L2-resident beside the cells' records) and the LevelPack
-// table alone in LDS (up to MA_LDS_LEVELS2 levels).
-constexpr int MA_LDS_LEVELS = 2048;   // 32 KB
-constexpr int MA_LDS_TRANS = 32768;   // 64 KB
-constexpr int MA_LDS_LEVELS2 = 9856;  // 154 KB (round 6: 6144 = 96 KB until the workgroup's per-cell estimator accumulators -- 32 KB that only models
-                                      // with few cells use -- were left out of this form: the 4e5-line set's 8 457 levels fit now; a model with few cells AND
-                                      // more than MA_LDS_LEVELS levels takes the form without LDS tables)
-template <int TB, int TABLES_LDS, bool COLD = false>
-__global__ void __launch_bounds__(TB, (TABLES_LDS ? 1 : ARTIS_THERMAL_EU)) k_thermal(Env env, const int32_t *list, int32_t n, Lists next,
-                                                                     unsigned long long *gstats, int budget, int32_t *cursors,
-                                                                     int nchunks, int chunk_mode, int drain_budget) {
-  __shared__ stat_t lstats[ARTIS_NSTATS];
-  __shared__ double lds_cellest[TABLES_LDS == 2 ? 1 : THERMAL_CELLEST_CAP];
-  __shared__ LevelPack lds_levelpack[TABLES_LDS == 1 ? MA_LDS_LEVELS : (TABLES_LDS == 2 ? MA_LDS_LEVELS2 : 1)];
-  __shared__ uint16_t lds_tlevel[TABLES_LDS == 1 ? MA_LDS_TRANS : 8];
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  cellest_begin(env, lds_cellest, env.cellest_n_t, TB, env.E.colheatingestimator);
-  env.estcache = nullptr;
-  env.estcache_nv = 0;
-  // many cells: the workgroup's array is not in use; its LDS holds the waves' caches of per-cell sums instead (physics.h Env::estcache): per wave
-  // ESTCACHE_SLOTS doubles, then per wave 2 x ESTCACHE_SLOTS int32 (the slots' cells, the claims)
-  static_assert(TABLES_LDS == 2 || (TB / 64) * ESTCACHE_SLOTS * 2 <= THERMAL_CELLEST_CAP, "the waves' estimator caches take the few-cells array's LDS");
-  if (TABLES_LDS != 2 && env.estcache_on && env.cellest_n_t == 0) {
-    const int w = threadIdx.x >> 6;
-    env.estcache = lds_cellest + (w * ESTCACHE_SLOTS);
-    env.estcache_tag = (int32_t *)(lds_cellest + ((TB / 64) * ESTCACHE_SLOTS)) + (w * ESTCACHE_SLOTS * 2);
-    env.estcache_nv = 1;
-    for (int l = threadIdx.x & 63; l < ESTCACHE_SLOTS; l += 64) {
-      env.estcache[l] = 0.;
-      env.estcache_tag[l] = -1;
-      env.estcache_tag[ESTCACHE_SLOTS + l] = -1;
-    }
-  }
-  if (TABLES_LDS) {
-    for (int i = threadIdx.x; i < env.M.nlevels; i += TB) lds_levelpack[i] = env.M.level_pack[i];
-    env.M.level_pack = lds_levelpack;
-    if (TABLES_LDS == 1) {
-      const uint32_t *src = (const uint32_t *)env.M.alltrans_tlevel16;  // (the allocation is padded to whole words)
-      uint32_t *dst = (uint32_t *)lds_tlevel;
-      for (int i = threadIdx.x; i < (env.M.nalltrans + 1) / 2; i += TB) dst[i] = src[i];
-      env.M.alltrans_tlevel16 = lds_tlevel;
-    }
-    env.ma_tables_in_lds = 1;
-  }
-  __syncthreads();
-  env.stats = lstats;
-  const double ts_end = env.S.ts_end;
-  Puller q;
-  puller_init(q, n, nchunks, chunk_mode);
-  bool have = false;
-  int32_t pi = 0;
-  int units = 0;
-  bool drained = false;  // the launch's work list is used up (any wave found out)
-  Pkt p;
-  MACtx k;
-#ifdef ARTIS_PROFILE
-#define PROF_ADD(slot, dt) \
-  do {                     \
-    if ((threadIdx.x & 63) == 0) atomicAdd(&lstats[slot], (stat_t)((dt) >> 4)); \
-  } while (0)
-  long long tprev = clock64();
-#endif
-  while (true) {
-    const int32_t idx = pull(q, !have, cursors);
-    if (idx >= 0) {
-      pi = list[idx];
-      pkt_load_thermal(env.P, pi, p);  // the hot line only
-      k = ma_ctx(env, p);
-      units = 0;
-      have = true;
-    }
-    if (!__any(have)) {
-      if (q.exhausted) break;
-      continue;
-    }
-    // Once the work list is used up, the launch lasts as long as its slowest packets keep their lanes (up to `budget`
-    // units each) while the rest of the GPU idles. In a launch whose successor is large anyway (drain_budget set by the
-    // host), a packet then leaves after drain_budget units for that next launch, where its work runs beside a full list.
-    // (Where a packet is handed from launch to launch never changes it: budgets are placement, tested.)
-    // BEFORE the list is used up such a launch has no unit budget (the host passes budget = INT_MAX, launch_thermal(); ARTIS_AMD_BUDGET_T_BULK
-    // gives it one): holding the lane costs nothing while the wave's other lanes keep pulling, and the hand-over ends the launch anyway. A budget
-    // there only stored, listed, sorted and loaded a long history again every round, and left it to run alone at the step's end.
-#define ROUND_BEFORE_LEAVE \
-    if (!drained && q.exhausted) { \
-      drained = true; \
-      if ((threadIdx.x & 63) == 0) __hip_atomic_store(&cursors[MAX_CHUNKS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
-    } \
-    if (!drained && drain_budget < budget) \
-      drained = __hip_atomic_load(&cursors[MAX_CHUNKS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-#define ROUND_LEAVE(n) ((n) >= budget || (drained && (n) >= drain_budget))
-#define ROUND_PUT(kind_, pi_) append_by_kind(kind_, pi_, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion))
-#include "thermal_round.inc"
-#undef ROUND_BEFORE_LEAVE
-#undef ROUND_LEAVE
-#undef ROUND_PUT
-  }
-  __syncthreads();
-  if (env.estcache_nv == 1) {  // the wave's sums go to the cells' records
-    for (int l = threadIdx.x & 63; l < ESTCACHE_SLOTS; l += 64) {
-      const int cell = env.estcache_tag[l];
-      const double s0 = env.estcache[l];
-      if (cell >= 0 && s0 != 0.) unsafeAtomicAdd(&env.E.colheatingestimator[(int64_t)cell * env.est_stride], s0);
-    }
-  }
-  cellest_flush(env, CELLEST_COLHEAT, env.E.colheatingestimator, TB);
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-
-// ---- k_thermal_q (round 5; ARTIS_AMD_REFILL=1): the thermal kernel with the macro-atom walk DECOUPLED from the packet, so that the
-// transition loop's lanes are refilled inside the loop. Round 3 built this once (profiles/r03/k_thermal_lane_compaction.md: lanes 35 -> 50,
-// and slower, because a transition was then three dependent L2 gathers whose wait grew with the lanes in flight). A transition is now one
-// 64-byte sector of the cell's record and two reads of static tables in LDS, and k_thermal runs at 37 of 64 lanes in a loop that is bound
-// by instruction issue: re-measured here under today's read pattern.
-// A wave owns TQ_V (> 64) packets. What a walk needs of a packet -- generator state, cell, ion's first level, level, counters: 36 B -- is its
-// WALK CONTEXT, kept in the wave's LDS slots; the packet's hot line rests in memory meanwhile. Two phases alternate per wave:
-//   walk:    every lane holds one context in registers and makes one transition per round; a lane whose walk ends (any process but an
-//            internal transition, an undecided search, the launch budget) writes the context back, pushes the slot on the wave's SERVICE
-//            stack and pops the next READY slot in the same round (ballot + popcount);
-//   service: once 64 slots wait (or the walkers run short), ONE full-wave pass reloads those packets' hot lines, carries out the process
-//            that ended each walk (ma_jump_exit), makes the k-packet step that follows, and either prepares the next walk (slot READY, hot
-//            line stored) or retires the packet (stored, appended to the list of its next kind) and pulls a new one into the slot.
-// Per packet the same functions run in the same order on the packet's own generator as in k_thermal: identical packets, generator states
-// and counters (GPU test); estimator sums differ by the order of their additions only.
-#ifndef ARTIS_TQ_SLOTS
-#define ARTIS_TQ_SLOTS 128
-#endif
-constexpr int TQ_V = ARTIS_TQ_SLOTS;  // slots per wave: 64 walking + a buffer that lets a full service pass fall due before the walkers starve
-static_assert(TQ_V >= 64 && TQ_V <= 256, "slot indices are kept in bytes");
-enum { TQ_EMPTY = -2, TQ_BUDGET = -3 };  // action of a slot on the service stack: no packet | walk interrupted by the launch budget
-struct TQWave {  // SoA: a lane reads field[its slot]
-  uint32_t s0[TQ_V], s1[TQ_V], s2[TQ_V], s3[TQ_V];
-  // lv = level within the ion | the ion's first level << 16; cnt = units | njumps << 16; act = (action + 3) | the draw of an undecided search << 7
-  int32_t pi[TQ_V], c[TQ_V], lv[TQ_V], cnt[TQ_V];
-  uint32_t act[TQ_V];
-  uint8_t ready[TQ_V];    // stack of the slots whose walk can go on
-  uint8_t service[TQ_V];  // stack of the slots that wait for the service pass
-};
-template <int TB, bool COLD = false>
-__global__ void __launch_bounds__(TB, 1) k_thermal_q(Env env, const int32_t *list, int32_t n, Lists next, unsigned long long *gstats, int budget,
-                                                     int32_t *cursors, int nchunks, int drain_budget, int low_water) {
-  // dynamic LDS: [TQWave x waves | LevelPack x nlevels | uint16 x nalltrans (padded to words)]
-  extern __shared__ __attribute__((aligned(16))) unsigned char tq_lds[];
-  __shared__ stat_t lstats[ARTIS_NSTATS];
-  TQWave *tq = (TQWave *)tq_lds;
-  LevelPack *lds_levelpack = (LevelPack *)(tq_lds + (((sizeof(TQWave) * (TB / 64)) + 15) & ~(size_t)15));
-  uint16_t *lds_tlevel = (uint16_t *)(lds_levelpack + env.M.nlevels);
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  for (int i = threadIdx.x; i < env.M.nlevels; i += TB) lds_levelpack[i] = env.M.level_pack[i];
-  {
-    const uint32_t *src = (const uint32_t *)env.M.alltrans_tlevel16;  // (the allocation is padded to whole words)
-    uint32_t *dst = (uint32_t *)lds_tlevel;
-    for (int i = threadIdx.x; i < (env.M.nalltrans + 1) / 2; i += TB) dst[i] = src[i];
-  }
-  env.M.level_pack = lds_levelpack;
-  env.M.alltrans_tlevel16 = lds_tlevel;
-  env.ma_tables_in_lds = 1;
-  env.cellest_lds = nullptr;
-  env.cellest_n = 0;
-  __syncthreads();
-  env.stats = lstats;
-  const double ts_end = env.S.ts_end;
-  const int lane = threadIdx.x & 63;
-  const unsigned long long lanebit = 1ull << lane;
-  TQWave &Q = tq[threadIdx.x >> 6];
-  Puller q;
-  puller_init(q, n, nchunks, 0);
-  // wave-uniform stack heights; every slot starts empty and waits for a packet
-  int nready = 0, nservice = TQ_V, ndead = 0;
-  for (int i = lane; i < TQ_V; i += 64) {
-    Q.service[i] = (uint8_t)i;
-    Q.act[i] = (uint32_t)(TQ_EMPTY + 3);
-  }
-  __builtin_amdgcn_wave_barrier();
-  bool drained = false;
-#ifdef ARTIS_PROFILE
-  long long tq_t = clock64();  // wave clocks / 16 of the two phases in the spare stats slots 42 (service) and 43 (walk)
-#define TQ_PROF(slot)                                                                   \
-  do {                                                                                  \
-    const long long now = clock64();                                                    \
-    if (lane == 0) atomicAdd(&lstats[slot], (stat_t)((now - tq_t) >> 4));               \
-    tq_t = now;                                                                         \
-  } while (0)
-#else
-#define TQ_PROF(slot) ((void)0)
-#endif
-#if defined(ARTIS_PROFILE) && !defined(ARTIS_PROFILE_MA)
-  long long tq_s = clock64();
-#define TQ_SUB(slot)                                                                    \
-  do {                                                                                  \
-    const long long now = clock64();                                                    \
-    if (lane == 0) atomicAdd(&lstats[slot], (stat_t)((now - tq_s) >> 4));               \
-    tq_s = now;                                                                         \
-  } while (0)
-#else
-#define TQ_SUB(slot) ((void)0)
-#endif
-  while (true) {
-    // ---------------- service passes: while a full wave of slots waits, or the walkers would run short
-    while (nservice >= 64 || (nservice > 0 && nready < low_water)) {
-#if defined(ARTIS_PROFILE) && !defined(ARTIS_PROFILE_MA)
-      tq_s = clock64();
-#endif
-      const int take = min(64, nservice);
-      const bool has = lane < take;
-      const int s = has ? (int)Q.service[nservice - 1 - lane] : 0;
-      nservice -= take;
-      const uint32_t actw = has ? Q.act[s] : (uint32_t)(TQ_EMPTY + 3);
-      const int act = (int)(actw & 127u) - 3;
-      const bool isdone = has && act != TQ_EMPTY;
-      const int32_t idx = pull(q, has && !isdone, cursors);
-      if (!drained && q.exhausted) {
-        drained = true;
-        if (lane == 0) __hip_atomic_store(&cursors[MAX_CHUNKS], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      if (!drained && drain_budget < budget) drained = __hip_atomic_load(&cursors[MAX_CHUNKS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-      const int budget_now = drained ? drain_budget : budget;
-      const bool have = isdone || idx >= 0;
-      int32_t pi = 0;
-      int units = 0;
-      Pkt p;
-      MACtx k;
-      if (have) {
-        pi = isdone ? Q.pi[s] : list[idx];
-        pkt_load_thermal(env.P, pi, p);  // the hot line only
-        k = ma_ctx(env, p);
-        if (isdone) {  // the walk's own state is the slot's; the level's record comes from the static table again
-          p.s0 = Q.s0[s]; p.s1 = Q.s1[s]; p.s2 = Q.s2[s]; p.s3 = Q.s3[s];
-          const int lv = Q.lv[s];
-          p.ma_level = lv & 0xFFFF;
-          k.start = lv >> 16;
-          k.start_key = (p.ma_element << 8) | p.ma_ion;
-          const LevelPack lp = env.M.level_pack[k.start + p.ma_level];
-          k.rec = ma_resolve<COLD>(env, k.c, lp.rec_off); k.nd = lp.ndown; k.nu = lp.nup; k.ats = lp.alltrans_startdown;
-          const int cnt = Q.cnt[s];
-          units = cnt & 0xFFFF;
-          k.njumps = cnt >> 16;
-          k.defer = (int)(actw >> 7);
-        }
-      }
-#ifdef ARTIS_PROFILE
-      if (lane == 0) {
-        ARTIS_STAT(env, 47);            // service passes
-        ARTIS_STAT_ADD(env, 44, take);  // ... and the slots they served
-      }
-#endif
-      TQ_SUB(59);  // (-DARTIS_PROFILE: wave clocks / 16 of the parts of a service pass: 59 pull + hot line + context | 60 the process that ended
-                   //  the walk | 61 the k-packet step | 62 prepare + store + context | 63 classify + append + stacks)
-      int kind = NEXT_DONE;
-      int32_t out_pi = 0;
-      bool walking = false;
-      if (have) {  // (one block: split into parts -- as the profile marks would like it -- the compiler spills 93 instead of 13 registers)
-        bool go = thermal_can_continue(p, ts_end);
-        if (isdone) {
-          ma_flush_stats(env, k);
-          const U4 *rec = ma_record<COLD>(env, k);
-          if (act == MA_EXIT_FILL) {
-            p.pend = PEND_MA_FILL;
-          } else if (act == MA_EXIT_DEFER) {
-            if (!ma_jump_deferred_fine<COLD>(env, p, k, rec)) {
-              p.pend = PEND_MA_SEARCH;  // the slow-path kernel re-adds the sums and makes the transition (physics.h ma_slow_search)
-              p.pend_arg = k.defer;
-            }
-          } else if (act >= 0) {
-            ma_jump_exit<true>(env, p, pi, k, rec, act);
-          }
-          chi_after_ma(p);
-          go = thermal_can_continue(p, ts_end);
-        }
-        TQ_SUB(60);
-        if (go) {
-          // a pre-k-packet, or a k-packet in a grey cell, leaves for the blackbody kernel (classify() below)
-          const bool blackbody = (p.type == ARTIS_TYPE_PRE_KPKT) || k.thick;
-          if (kpkt_eligible(p, ts_end) && !blackbody) {
-            do_kpkt<true>(env, p, pi);
-            p.chi_mgi = -1;
-            units++;
-          }
-          go = thermal_can_continue(p, ts_end) && !(blackbody && kpkt_eligible(p, ts_end));
-        }
-        TQ_SUB(61);
-        walking = go && units < budget_now && ma_pending(p) && p.pend == PEND_NONE;
-        if (walking) ma_prepare<COLD>(env, p, k);  // (only k.start is kept: the walk phase reads the level's record shape from LDS)
-        pkt_store_thermal(env.P, pi, p);  // the hot line; the flight line only if an r-packet was emitted
-        if (walking) {
-          Q.s0[s] = p.s0; Q.s1[s] = p.s1; Q.s2[s] = p.s2; Q.s3[s] = p.s3;
-          Q.pi[s] = pi;
-          Q.c[s] = k.c;
-          Q.lv[s] = p.ma_level | (k.start << 16);
-          Q.cnt[s] = units;
-        } else {
-          kind = classify(env, p, ts_end);
-          out_pi = pi;
-        }
-      }
-      TQ_SUB(62);
-      append_by_kind(kind, out_pi, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion));
-      // where the slots go: READY, or back on the service stack as empty (a packet is pulled into it by the next pass), or --
-      // once the work list is used up -- out of use
-      {
-        const unsigned long long rm = __ballot(walking);
-        if (walking) Q.ready[nready + __popcll(rm & (lanebit - 1ull))] = (uint8_t)s;
-        nready += __popcll(rm);
-        const bool again = has && !walking && !q.exhausted;
-        const unsigned long long em = __ballot(again);
-        if (again) {
-          Q.act[s] = (uint32_t)(TQ_EMPTY + 3);
-          Q.service[nservice + __popcll(em & (lanebit - 1ull))] = (uint8_t)s;
-        }
-        nservice += __popcll(em);
-        ndead += take - __popcll(rm) - __popcll(em);
-      }
-      __builtin_amdgcn_wave_barrier();
-      TQ_SUB(63);
-    }
-    TQ_PROF(42);
-    if (nready == 0) break;  // (then nothing waits for service either: every slot is out of use)
-    // ---------------- walk phase
-    {
-      // in the drain (work list used up) a service pass is worth its cost only for a reasonable share of the live slots
-      const int drain_min = max(1, min(16, (TQ_V - ndead) / 4));
-      const int budget_now = drained ? drain_budget : budget;
-      int myslot = -1;
-      int units = 0;
-      Pkt w;  // only the generator state and ma_level are live
-      MACtx k;
-      w.ma_level = -1;
-      k.c = 0; k.cellma = nullptr; k.rec = 0; k.nd = k.nu = 0; k.ats = 0; k.njumps = 0; k.start = 0; k.start_key = -1; k.defer = 0; k.thick = false;
-#ifdef ARTIS_PROFILE
-      int prof_rounds = 0, prof_lanes = 0;  // wave-uniform: rounds of this phase and the lanes that made a transition in them
-#endif
-      while (true) {
-        {  // lanes without a context pop READY slots
-          const bool need = myslot < 0;
-          const unsigned long long m = __ballot(need);
-          if (m != 0 && nready > 0) {
-            const int takeN = min(__popcll(m), nready);
-            const int prefix = __popcll(m & (lanebit - 1ull));
-            if (need && prefix < takeN) {
-              const int s = (int)Q.ready[nready - 1 - prefix];
-              myslot = s;
-              w.s0 = Q.s0[s]; w.s1 = Q.s1[s]; w.s2 = Q.s2[s]; w.s3 = Q.s3[s];
-              const int lv = Q.lv[s];
-              w.ma_level = lv & 0xFFFF;
-              k.c = Q.c[s];
-              k.cellma = env.K.macache + (krow(env, k.c) * env.M.nmacache);
-              k.start = lv >> 16;
-              const LevelPack lp = env.M.level_pack[k.start + w.ma_level];
-              k.rec = ma_resolve<COLD>(env, k.c, lp.rec_off); k.nd = lp.ndown; k.nu = lp.nup; k.ats = lp.alltrans_startdown;
-              const int cnt = Q.cnt[s];
-              units = cnt & 0xFFFF;
-              k.njumps = cnt >> 16;
-            }
-            nready -= takeN;
-          }
-        }
-        const int nactive = __popcll(__ballot(myslot >= 0));
-        if (nactive == 0 || nservice >= 64 || (nactive < low_water && nservice >= drain_min)) break;
-        bool ended = false;
-        int end_action = 0;
-        {
-          const bool go = myslot >= 0;
-#ifdef ARTIS_PROFILE
-          prof_lanes += __popcll(__ballot(go));
-          prof_rounds++;
-#endif
-          if (go) {
-            const int action = ma_jump_internal<true, COLD>(env, w, k, ma_record<COLD>(env, k));
-            units++;
-            if (action >= 0 || units >= budget_now) {
-              ended = true;
-              end_action = action >= 0 ? action : TQ_BUDGET;
-            }
-          }
-        }
-        const unsigned long long em = __ballot(ended);
-        if (em != 0) {
-          if (ended) {
-            const int s = myslot;
-            Q.s0[s] = w.s0; Q.s1[s] = w.s1; Q.s2[s] = w.s2; Q.s3[s] = w.s3;
-            Q.lv[s] = w.ma_level | (k.start << 16);
-            Q.cnt[s] = units | (k.njumps << 16);
-            Q.act[s] = (uint32_t)(end_action + 3) | ((uint32_t)k.defer << 7);
-            Q.service[nservice + __popcll(em & (lanebit - 1ull))] = (uint8_t)s;
-            myslot = -1;
-          }
-          nservice += __popcll(em);
-        }
-      }
-      // park the walks in progress: their slots are READY again
-      const bool parked = myslot >= 0;
-      const unsigned long long pm = __ballot(parked);
-      if (parked) {
-        const int s = myslot;
-        Q.s0[s] = w.s0; Q.s1[s] = w.s1; Q.s2[s] = w.s2; Q.s3[s] = w.s3;
-        Q.lv[s] = w.ma_level | (k.start << 16);
-        Q.cnt[s] = units | (k.njumps << 16);
-        Q.ready[nready + __popcll(pm & (lanebit - 1ull))] = (uint8_t)s;
-      }
-      nready += __popcll(pm);
-#ifdef ARTIS_PROFILE
-      if (lane == 0) {
-        ARTIS_STAT_ADD(env, 46, prof_rounds);  // wave-rounds of the transition loop
-        ARTIS_STAT_ADD(env, 45, prof_lanes);   // ... and the lanes that made a transition in them
-      }
-#endif
-      __builtin_amdgcn_wave_barrier();
-      TQ_PROF(43);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-#ifndef ARTIS_TQ_TB
-#define ARTIS_TQ_TB 768
-#endif
-constexpr int TQ_TB = ARTIS_TQ_TB;  // 12 waves per CU = 3 waves/SIMD at 168 VGPRs (round 3's optimum for this form; the slots of 16 waves and the tables do not fit the LDS)
-inline size_t tq_lds_bytes(int tb, int nlevels, int nalltrans) {
-  return (((sizeof(TQWave) * (size_t)(tb / 64)) + 15) & ~(size_t)15) + (sizeof(LevelPack) * (size_t)nlevels) + (sizeof(uint32_t) * (size_t)((nalltrans + 1) / 2));
-}
-
-// ---- k_late: the END of a population -- the r-packets and thermal packets left once the lists are too short to fill the GPU -- in ONE persistent
-// launch. The split kernels put a device-wide barrier between every r-packet <-> thermal alternation, and below ~1e6 packets every such round costs a
-// floor (its slowest packet's visit) however few packets it holds; the sum over rounds of those maxima is far above the longest single chain. Here a
-// packet goes from one kind of step to the other inside the launch:
-//   geometry   one workgroup of LATE_TB = 512 threads per compute unit (2 waves per SIMD, no spilled register; 768 threads: 3 waves, 34 spilled, measured);
-//   ownership  workgroup b owns a fixed contiguous share of the (sorted) r-packet list and of the thermal list; a packet never changes workgroup, and
-//              nothing waits on another workgroup;
-//   queues     per workgroup one ring per role (r-packet, thermal, slow path) in its slice of a scratch array, capacity = the workgroup's share (a packet sits in
-//              at most one queue); head, reserved and published tail in LDS. A producer stores the packet (the bodies' pkt_store / chi_store /
-//              pkt_store_thermal), writes the entries it reserved, and publishes them in reservation order with a workgroup-scope release; a consumer
-//              reads the published tail with a workgroup-scope acquire, reads the entries, and takes them with a compare-and-swap on the head (entries
-//              [head, published) cannot be overwritten while the head stands: the ring holds as many entries as the workgroup has packets). All waves
-//              of a workgroup share a compute unit and its L1: no device-scope fence;
-//   roles      a wave runs one role at a time (all its lanes in the same body: rpkt_round.inc / thermal_round.inc, the split kernels' own); idle lanes pull
-//              from the role's queue; a lane keeps its packet until its kind changes or it ends -- no budget. The waves start split between the roles
-//              in proportion to the workgroup's two shares (at least one wave each where both are non-empty); a wave whose lanes are all idle and whose
-//              queue is empty takes the other role if that queue is not empty;
-//   slow path  the third role: the rare bound-free actions (k_slow's body: the wave selects the free-bound frequencies of its lanes' emissions, then
-//              advance_slow()), one pull - action - store - put per pass, nothing held between passes. The last wave of a workgroup serves only this
-//              queue (ARTIS_LATE_SLOW_WAVE; it polls with s_sleep while the workgroup has packets), and every other wave whose lanes are all idle looks
-//              at the slow queue first: a packet with a pending action waits for a poll, not for the launch to end and two more to begin;
-//   ejection   a packet whose next kind is a blackbody step, a gamma-ray kind, or that is done, is stored and appended to the ordinary
-//              lists (append_by_kind) exactly as a split kernel would; the host's loop runs those kinds and what comes back is listed again;
-//   the end    `live` (LDS) counts the workgroup's packets that have not been ejected; a wave leaves when it is 0;
-//   estimators plain f64 global atomics (the lists are short here): no per-wave caches, no few-cells LDS arrays;
-//   waits      every wait is for a wave of the same workgroup, so progress is certain; each is capped all the same. An idle wave polls with s_sleep at
-//              most poll_cap times, then counts itself in *bailouts and leaves (it holds no packet; the waves that do carry the workgroup's packets to
-//              their end: a bail-out costs time, never an answer). A producer waits for the reservations before its own to be published -- a few
-//              instructions of another wave -- and, if that never happens, raises error flag 47 and publishes nothing (the call fails; no entry is read that was not written).
-// Dynamic LDS: [stats | counters | LevelPack x nlevels | uint16 target levels x nalltrans | ContPack x nbfcontinua] (late_lds_bytes()).
-#ifndef ARTIS_LATE_KERNEL
-#define ARTIS_LATE_KERNEL (!ARTIS_OPT_VPKT_ON && !ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON)  // the builds that may use k_late
-#endif
-#ifndef ARTIS_LATE_TB
-#define ARTIS_LATE_TB 512  // 2 waves per SIMD at up to 256 VGPRs: no spilled register (768: 3 waves at 168 VGPRs, 34 spilled; profiles/r08/late_kernel.md)
-#endif
-#ifndef ARTIS_LATE_SLOW_INLINE
-// the slow role's body inside k_late's loop, or called from it. Classic options: 255 VGPRs and no spilled register inlined, 26 spilled around the call.
-// The builds with interpolated cross-sections, whose slow path alone takes 256 VGPRs + 22 AGPRs (k_slow): 398 spilled inlined, 95 called
-// (profiles/r10/late_slow_role.md)
-#define ARTIS_LATE_SLOW_INLINE ARTIS_OPT_PHIXS_CLASSIC_NO_INTERPOLATION
-#endif
-#ifndef ARTIS_LATE_SLOW_WAVE
-#define ARTIS_LATE_SLOW_WAVE 1  // the last wave of each workgroup serves the slow-path queue only; 0: idle waves alone do (profiles/r10/late_slow_role.md)
-#endif
-constexpr int LATE_TB = ARTIS_LATE_TB;
-constexpr size_t LATE_LDS_HEAD = (sizeof(stat_t) * ARTIS_NSTATS) + 64;  // statistics, then the queues' counters
-inline size_t late_lds_bytes(int nlevels, int nalltrans, int nbfcontinua) {
-  return LATE_LDS_HEAD + (sizeof(LevelPack) * (size_t)nlevels) + (((sizeof(uint32_t) * (size_t)((nalltrans + 1) / 2)) + 15) & ~(size_t)15) +
-         (sizeof(ContPack) * (size_t)nbfcontinua);
-}
-constexpr int LATE_NQ = 3;  // roles and their queues: 0 = r-packets, 1 = thermal packets, 2 = the slow path
-struct LateArgs {
-  const int32_t *list[LATE_NQ];  // the r-packet, the thermal and the slow-path list, consumed whole
-  int32_t n[LATE_NQ];
-  int32_t *ring[LATE_NQ];        // scratch: [n[0] + n[1] + n[2]] each; workgroup b's slice begins at the sum of its three shares' beginnings
-  int32_t *bailouts;
-  int32_t poll_cap;
-#ifdef ARTIS_PROFILE_LATE
-  int32_t *stamp;  // [packets] when a packet entered the slow queue (clocks / 16, low word)
-#endif
-};
-#if ARTIS_LATE_KERNEL
-struct LateRing {
-  int32_t *ring;   // the workgroup's slice
-  uint32_t cap;
-  int32_t *head, *res, *pub;  // LDS: entries taken | reserved by producers | published (head <= pub <= res <= head + cap)
-};
-__device__ inline void late_push(const LateRing &Q, bool flag, int32_t pi, int32_t *errflag) {
-  const unsigned long long mask = __ballot(flag);
-  if (mask == 0) return;
-  const int lane = threadIdx.x & 63;
-  const int cnt = __popcll(mask);
-  const int prefix = __popcll(mask & ((1ull << lane) - 1ull));
-  const int leader = __ffsll((long long)mask) - 1;
-  int base = 0;
-  if (lane == leader) base = atomicAdd(Q.res, cnt);
-  base = __shfl(base, leader);
-  if (flag) Q.ring[(uint32_t)(base + prefix) % Q.cap] = pi;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // the packet records and the entries, before the entries are published
-  if (lane == leader) {
-    int spins = 0;
-    bool turn = true;
-    while (__hip_atomic_load(Q.pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != base) {  // earlier reservations are published first
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > (1 << 24)) {
-        // never publish over a reservation that was not: the entries stay out of reach, the workgroup's waves run into their poll caps, the
-        // kernel ends and the call fails with this flag
-        if (errflag) *errflag = 47;
-        turn = false;
-        break;
-      }
-    }
-    if (turn) __hip_atomic_store(Q.pub, base + cnt, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-}
-// hands queue entries to the lanes with need == true: the packet's index, or -1. Wave-uniform control flow.
-__device__ inline int32_t late_pull(const LateRing &Q, bool need) {
-  const unsigned long long mask = __ballot(need);
-  if (mask == 0) return -1;
-  const int lane = threadIdx.x & 63;
-  const int prefix = __popcll(mask & ((1ull << lane) - 1ull));
-  const int leader = __ffsll((long long)mask) - 1;
-  int h = 0, t = 0;
-  if (lane == leader) {
-    h = __hip_atomic_load(Q.head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    t = __hip_atomic_load(Q.pub, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-  }
-  h = __shfl(h, leader);
-  t = __shfl(t, leader);
-  const int take = min(__popcll(mask), t - h);
-  if (take <= 0) return -1;
-  int32_t v = -1;
-  if (need && prefix < take) v = __hip_atomic_load(&Q.ring[(uint32_t)(h + prefix) % Q.cap], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  int ok = 0;
-  if (lane == leader) ok = (atomicCAS(Q.head, h, h + take) == h) ? 1 : 0;  // another wave took them first: the caller asks again
-  ok = __shfl(ok, leader);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // the packet records are read after this
-  return ok ? v : -1;
-}
-// k_late's policy for the loop bodies it shares with the split kernels (rpkt_round.inc, thermal_round.inc): no budget; a packet that stays an
-// r-packet or a thermal packet, or has a slow-path action pending, goes to the workgroup's queue of that role, every other packet leaves the kernel
-struct LateSink {
-  LateRing q[LATE_NQ];
-  int32_t *live;
-  int32_t *errflag;
-#ifdef ARTIS_PROFILE_LATE
-  int32_t *stamp;
-#endif
-  // left: this lane gave up packet pi, whose next kind is `kind`. Wave-uniform control flow.
-  // to_list: a slow-path packet that leaves the kernel for the ordinary slow-path list (it waits for a record k_slow has to fill)
-  __device__ void put(bool left, int kind, int32_t pi, const Pkt &p, const Lists &next, bool to_list = false) const {
-    const bool to_r = left && kind == NEXT_RPKT;
-    const bool to_t = left && (kind == NEXT_MA || kind == NEXT_KPKT);
-    // (a packet that waits for a static record the population left out -- tables.h "ABSENT IONS"; this kernel runs where no level is cold --
-    // leaves for the ordinary slow-path list like the kinds the kernel cannot run: k_slow fills such records, between launches)
-    // (from the r-packet and thermal roles that is PEND_MA_FILL alone: an action's record was populated when it was drawn from a moment ago; the
-    // slow role passes to_list for every packet physics.h ma_waits_for_static_fill() flags)
-    const bool to_s = left && kind == NEXT_SLOW && p.pend != PEND_MA_FILL && !to_list;
-#ifdef ARTIS_PROFILE_LATE
-    if (to_s) stamp[pi] = (int32_t)(clock64() >> 4);
-#endif
-    late_push(q[0], to_r, pi, errflag);
-    late_push(q[1], to_t, pi, errflag);
-    late_push(q[2], to_s, pi, errflag);
-    const bool out = left && !to_r && !to_t && !to_s;
-    append_by_kind(out ? kind : NEXT_DONE, pi, p.cellindex, p.nu_cmf, next, (p.ma_element * 5 + p.ma_ion));
-    const unsigned long long om = __ballot(out);
-    if (om != 0 && (int)(threadIdx.x & 63) == __ffsll((long long)om) - 1) atomicSub(live, __popcll(om));  // after the append: `live` 0 = all is on the lists
-  }
-};
-// One pass of the slow-path role: k_slow's body for the packets the wave's lanes have just pulled (got >= 0), without the cold-record fill (no cold
-// levels where k_late runs). The wave selects the free-bound frequencies whatever their number, as in k_tail. Wave-uniform control flow.
-#if ARTIS_LATE_SLOW_INLINE
-__device__ inline
-#else
-__device__ __noinline__
-#endif
-void late_slow_round(const Env &env, const LateSink &sink, const Lists &next, int32_t got) {
-  const bool mine = got >= 0;
-  const int32_t pi = mine ? got : 0;
-  Pkt p;
-  p.cellindex = 0; p.nu_cmf = 0.; p.ma_element = 0; p.ma_ion = 0;
-  FbSel sel;
-  sel.mode = 1;
-  sel.valid = false;
-  sel.element = sel.lowerion = sel.lower = sel.t = 0;
-  sel.T_e = 0.f;
-  sel.zrand = sel.nu = 0.;
-  if (mine) pkt_load(env.P, pi, p);
-#ifdef ARTIS_PROFILE_LATE
-  // (-DARTIS_PROFILE_LATE) stats slots: 42 clocks / 16 the packets waited in the slow queue, 43 the packets, 44 / 45 those that waited longer than
-  // 2^12 / 2^16 units (31 us / 0.5 ms at 2.1 GHz), 46 passes of the role, 47 clocks / 16 of the passes (per wave)
-  const long long tpass0 = clock64();
-  if (mine) {
-    const uint32_t w = (uint32_t)((int32_t)(tpass0 >> 4) - sink.stamp[pi]);
-    atomicAdd(&env.stats[42], (stat_t)w);
-    atomicAdd(&env.stats[43], (stat_t)1);
-    if (w > (1u << 12)) atomicAdd(&env.stats[44], (stat_t)1);
-    if (w > (1u << 16)) atomicAdd(&env.stats[45], (stat_t)1);
-  }
-#endif
-  if (mine && slow_selects_continuum_nu(p)) {
-    Pkt t = p;
-    (void)advance_slow(env, t, pi, &sel);
-  }
-  fbsel_wave(env, sel);
-  int kind = NEXT_DONE;
-  const bool waits = mine && ma_waits_for_static_fill(env, p);
-  if (waits) {
-    kind = NEXT_SLOW;  // (put() sends it on to k_slow, untouched)
-  } else if (mine) {
-    kind = advance_slow(env, p, pi, sel.valid ? &sel : nullptr);
-    pkt_store(env.P, pi, p);
-  }
-  sink.put(mine, kind, pi, p, next, waits);
-#ifdef ARTIS_PROFILE_LATE
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&env.stats[46], (stat_t)1);
-    atomicAdd(&env.stats[47], (stat_t)((clock64() - tpass0) >> 4));
-  }
-#endif
-}
-__global__ void __launch_bounds__(LATE_TB, 1) k_late(Env env, LateArgs a, Lists next, unsigned long long *gstats) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char late_lds[];
-  // this workgroup's shares of the three lists (contiguous; neighbouring shares on one XCD: xcd_chunk) and its slice of the rings
-  const int64_t nwg = gridDim.x, b = xcd_chunk(blockIdx.x, nwg);
-  const int32_t r0 = (int32_t)(((int64_t)a.n[0] * b) / nwg), r1 = (int32_t)(((int64_t)a.n[0] * (b + 1)) / nwg);
-  const int32_t t0 = (int32_t)(((int64_t)a.n[1] * b) / nwg), t1 = (int32_t)(((int64_t)a.n[1] * (b + 1)) / nwg);
-  const int32_t s0 = (int32_t)(((int64_t)a.n[2] * b) / nwg), s1 = (int32_t)(((int64_t)a.n[2] * (b + 1)) / nwg);
-  const int32_t own = (r1 - r0) + (t1 - t0) + (s1 - s0);
-  if (own == 0) return;  // (the whole workgroup)
-  stat_t *lstats = (stat_t *)late_lds;
-  int32_t *ctr = (int32_t *)(late_lds + (sizeof(stat_t) * ARTIS_NSTATS));  // head r, t | reserved r, t | published r, t | live | head, reserved, published s
-  LevelPack *lds_levelpack = (LevelPack *)(late_lds + LATE_LDS_HEAD);
-  uint16_t *lds_tlevel = (uint16_t *)(lds_levelpack + env.M.nlevels);
-  ContPack *lds_cont = (ContPack *)((unsigned char *)lds_tlevel + (((sizeof(uint32_t) * (size_t)((env.M.nalltrans + 1) / 2)) + 15) & ~(size_t)15));
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  for (int i = threadIdx.x; i < env.M.nlevels; i += LATE_TB) lds_levelpack[i] = env.M.level_pack[i];
-  {
-    const uint32_t *src = (const uint32_t *)env.M.alltrans_tlevel16;  // (the allocation is padded to whole words)
-    uint32_t *dst = (uint32_t *)lds_tlevel;
-    for (int i = threadIdx.x; i < (env.M.nalltrans + 1) / 2; i += LATE_TB) dst[i] = src[i];
-  }
-  {
-    const D2 *src = (const D2 *)env.M.cont_pack;
-    D2 *dst = (D2 *)lds_cont;
-    for (int i = threadIdx.x; i < env.M.nbfcontinua * 2; i += LATE_TB) dst[i] = src[i];
-  }
-  const int32_t slice = r0 + t0 + s0;
-  LateSink sink{{{a.ring[0] + slice, (uint32_t)own, ctr + 0, ctr + 2, ctr + 4}, {a.ring[1] + slice, (uint32_t)own, ctr + 1, ctr + 3, ctr + 5},
-                 {a.ring[2] + slice, (uint32_t)own, ctr + 7, ctr + 8, ctr + 9}},
-                ctr + 6, env.errflag
-#ifdef ARTIS_PROFILE_LATE
-                , a.stamp
-#endif
-  };
-  // the queues begin with the workgroup's shares
-  for (int i = threadIdx.x; i < r1 - r0; i += LATE_TB) sink.q[0].ring[i] = a.list[0][r0 + i];
-  for (int i = threadIdx.x; i < t1 - t0; i += LATE_TB) sink.q[1].ring[i] = a.list[1][t0 + i];
-  for (int i = threadIdx.x; i < s1 - s0; i += LATE_TB) {
-    sink.q[2].ring[i] = a.list[2][s0 + i];
-#ifdef ARTIS_PROFILE_LATE
-    a.stamp[a.list[2][s0 + i]] = (int32_t)(clock64() >> 4);
-#endif
-  }
-  if (threadIdx.x == 0) {
-    ctr[0] = ctr[1] = ctr[7] = 0;
-    ctr[2] = ctr[4] = r1 - r0;
-    ctr[3] = ctr[5] = t1 - t0;
-    ctr[8] = ctr[9] = s1 - s0;
-    ctr[6] = own;
-  }
-  env.M.level_pack = lds_levelpack;
-  env.M.alltrans_tlevel16 = lds_tlevel;
-  env.ma_tables_in_lds = 1;
-  env.M.cont_pack = lds_cont;
-  env.cont_in_lds = 1;
-  env.cellest_lds = nullptr;
-  env.cellest_n = 0;
-  env.estcache = nullptr;
-  env.estcache_nv = 0;
-  __syncthreads();
-  env.stats = lstats;
-  const double ts_end = env.S.ts_end;
-  constexpr int NW = LATE_TB / 64;
-  constexpr int NW_RT = ARTIS_LATE_SLOW_WAVE ? NW - 1 : NW;  // the waves that begin in the r-packet and thermal roles
-  // roles: 0 = r-packets, 1 = thermal packets, 2 = the slow path (`home`: the role of the first two a wave came from)
-  const int32_t own_rt = (r1 - r0) + (t1 - t0);
-  int nw_r = own_rt > 0 ? (int)((((int64_t)(r1 - r0) * NW_RT) + (own_rt / 2)) / own_rt) : 0;
-  if (r1 > r0 && t1 > t0) nw_r = max(1, min(NW_RT - 1, nw_r));
-  const bool slow_wave = ARTIS_LATE_SLOW_WAVE && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == NW - 1;
-  int home = __builtin_amdgcn_readfirstlane(((int)(threadIdx.x >> 6) < nw_r) ? 0 : 1);
-  int role = slow_wave ? 2 : home;
-  const auto waiting = [&](int q) {  // entries published and not yet taken
-    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(sink.q[q].pub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) -
-                                          __hip_atomic_load(sink.q[q].head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-  };
-  bool have = false;
-  int32_t pi = 0;
-  int n_it = 0;  // (the bodies count the lane's steps / units; no budget reads them here)
-  int polls = 0;
-  Pkt p;
-  Chi x;
-  MACtx k;
-  long long tprev = 0;
-  while (true) {
-    const int32_t got = late_pull(sink.q[role], !have);
-    if (role == 2) {  // (no lane of a wave in this role holds a packet between passes)
-      if (__any(got >= 0)) {
-        late_slow_round(env, sink, next, got);
-        polls = 0;
-        continue;
-      }
-    } else if (got >= 0) {
-      pi = got;
-      if (role == 0) {
-        pkt_load(env.P, pi, p);
-        chi_load(env.P, pi, p, x);
-      } else {
-        pkt_load_thermal(env.P, pi, p);  // the hot line only
-        k = ma_ctx(env, p);
-      }
-      have = true;
-    }
-    if (!__any(have)) {
-      // a wave whose lanes are all idle: the slow queue first (a packet there waits for nothing else), then its own role's, then the other's
-      if (waiting(2) > 0) {
-        role = 2;
-        continue;
-      }
-      if (!slow_wave) {
-        role = home;
-        if (waiting(home) > 0) continue;  // (another wave was faster: ask again)
-        if (waiting(1 - home) > 0) {
-          role = home = 1 - home;
-          continue;
-        }
-      }
-      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) break;
-      if (++polls > a.poll_cap) {  // the other waves hold what is left and carry it to its end
-        if ((threadIdx.x & 63) == 0) atomicAdd(a.bailouts, 1);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(64);
-      continue;
-    }
-    polls = 0;
-    const bool held = have;
-    constexpr bool COLD = false;  // (no cold levels where this kernel runs)
-#define ROUND_LEAVE(n) false
-#define ROUND_BEFORE_LEAVE
-#define ROUND_PUT(kind_, pi_) sink.put(held && !have, kind_, pi_, p, next)
-    if (role == 0) {
-      int &steps = n_it;
-#include "rpkt_round.inc"
-    } else {
-      int &units = n_it;
-#include "thermal_round.inc"
-    }
-#undef ROUND_LEAVE
-#undef ROUND_BEFORE_LEAVE
-#undef ROUND_PUT
-  }
-  __syncthreads();
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-#endif
-
-// Tail kernel: the LAST few thousand r-packets and thermal packets of a timestep, one per lane, each carried through
-// r-packet steps, macro-atom walks and k-packet steps until it leaves these kinds (end of the timestep, escape, a
-// slow-path action, a gamma-ray type, a blackbody step, another cache tile). The event-split kernels need one launch
-// pair per r-packet <-> thermal alternation of the longest-lived packets, and a launch lasts as long as its slowest
-// packet: with the nltenebular options 530 of 720 launches of a step hold fewer than 10^4 packets and cost 490 ms
-// (the last 150 hold 1-5 packets). Here the packets do not wait for each other. Same functions in the same order per
-// packet as the split kernels (state goes through the packet record at every change of kind, as it does between
-// launches), so the same results; a fat kernel (both bodies: scratch, low occupancy), which is why it is the tail only.
-struct TailLists {
-  const int32_t *list[4];  // the current r-packet, thermal, slow-path and blackbody lists
-  int32_t n[4];
-};
-#ifndef ARTIS_TAIL_WAVES
-#define ARTIS_TAIL_WAVES 2
-#endif
-#ifndef ARTIS_SLOW_WAVE_FB
-#define ARTIS_SLOW_WAVE_FB 1  // free-bound emission frequencies selected by the wave (physics.h FbSel) in k_slow and k_tail
-#endif
-#ifndef ARTIS_TAIL_WAVE_CHI
-#define ARTIS_TAIL_WAVE_CHI 1  // k_tail: the continuum opacity of a step evaluated by the wave (physics.h chi_rpkt_cont_wave); 0: by the packet's lane
-#endif
-#ifndef ARTIS_SLOW_WAVE_FB_MAX
-#define ARTIS_SLOW_WAVE_FB_MAX 6  // ... in k_slow for waves with at most this many emissions
-#endif
-// (Round 5: with the static tables of a transition's target in LDS as in k_thermal -- workgroups of 8 packets, one per compute unit -- the
-// classic tail took 27.6 / 26.7 ms against 29.0 / 25.3, the nltenebular tail 123 against 108: profiles/r05/tail_profile.txt. Not kept.)
-__global__ void __launch_bounds__(BLOCK, ARTIS_TAIL_WAVES) k_tail(Env env, TailLists in, Lists next, unsigned long long *gstats) {
-  __shared__ stat_t lstats[ARTIS_NSTATS];
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  __syncthreads();
-  env.stats = lstats;
-  env.ma_concurrent_fill = 1;  // this kernel's waves fill pool records while others read them: published places are read with acquire (physics.h ma_rowtab_acquire)
-  const double ts_end = env.S.ts_end;
-  // ONE PACKET PER WAVE (lane 0): packets in different kinds of step would otherwise serialise inside a wave (measured
-  // with a packet per lane: slower than the split kernels); the tail has fewer packets than the GPU has waves
-  const int64_t tid = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) >> 6;
-  int kind = NEXT_DONE;
-  int32_t pi = 0, cellindex = 0;
-  double nu_cmf = 0.;
-  // (every lane runs the loop over the packet's kinds of step with lane 0's kind; only lane 0 holds the packet and carries the steps out,
-  // the other 63 join it where the wave works together: the frequency of a free-bound emission, physics.h FbSel)
-  const bool owner = (threadIdx.x & 63) == 0 && tid < (int64_t)in.n[0] + in.n[1] + in.n[2] + in.n[3];
-  Pkt p;
-  if (owner) {
-    int32_t j = (int32_t)tid;
-    int which = 0;
-    while (j >= in.n[which]) j -= in.n[which++];
-    pi = in.list[which][j];
-    pkt_load(env.P, pi, p);
-  }
-#ifdef ARTIS_PROFILE_TAIL
-  // (-DARTIS_PROFILE_TAIL, tools/tail_profile.py) clocks / 16 of the owner lane by kind of step: slots 42 slow, 43 r-packet, 44 thermal, 45 blackbody,
-  // 46 / 47 the r-packet and thermal iterations; 50..53 the same clocks of the waves that ran longer than 2^25 clocks (~15 ms) only
-  long long tp[4] = {0, 0, 0, 0};
-  long long tp_n[2] = {0, 0};
-#define TAILP(i, code)                   \
-  {                                      \
-    const long long tp0_ = clock64();    \
-    code;                                \
-    tp[i] += clock64() - tp0_;           \
-  }
-#else
-#define TAILP(i, code) code
-#endif
-  while (true) {
-    if (owner) kind = classify(env, p, ts_end);
-    const int kind_w = __builtin_amdgcn_readfirstlane(__shfl(kind, 0));
-    if (kind_w == NEXT_SLOW) {
-      if (env.ion_absent != nullptr) {
-        // the packet waits for a static record the population left out (tables.h "ABSENT IONS"): it leaves for the slow-path list, whose kernel
-        // fills such records -- between launches, where no wave reads a record while another writes it (the host runs that list next)
-        const bool hand = owner && ma_waits_for_static_fill(env, p);
-        if (__builtin_amdgcn_readfirstlane(__shfl((int)hand, 0)) != 0) break;  // (kind is NEXT_SLOW)
-      }
-#ifdef ARTIS_PROFILE_TAIL
-      const long long tps0 = clock64();
-#endif
-#if ARTIS_SLOW_WAVE_FB
-      FbSel sel;
-      sel.mode = 1;
-      sel.valid = false;
-      sel.element = sel.lowerion = sel.lower = sel.t = 0;
-      sel.T_e = 0.f;
-      sel.zrand = sel.nu = 0.;
-      if (owner && slow_selects_continuum_nu(p)) {
-        Pkt t = p;
-        (void)advance_slow(env, t, pi, &sel);
-      }
-      fbsel_wave(env, sel);
-#endif
-      {
-        int fc = 0, ful = 0;
-        int32_t funit = 0;
-        const bool fill = ARTIS_MA_WAVE_FILL && owner && p.pend == PEND_MA_FILL && ma_slow_fill_claim(env, p, &fc, &ful, &funit);
-        ma_fill_wave(env, fill, fc, ful);
-        if (fill) ma_slow_fill_publish(env, fc, ful, funit);
-      }
-#if ARTIS_SLOW_WAVE_FB
-      if (owner) (void)advance_slow(env, p, pi, sel.valid ? &sel : nullptr);
-#else
-      if (owner) (void)advance_slow(env, p, pi);
-#endif
-      {
-        // the pool of on-demand records is used up and the packet still waits for a record: it leaves for the slow-path list (the host empties
-        // the pool before that list's next launch); nothing in this kernel could end the wait
-        // (only a packet whose level has no record and none being filled: one whose record another wave is filling goes on -- ADVICE r05)
-        const bool waits = owner && env.M.ncold > 0 && p.pend != PEND_NONE &&
-                           __hip_atomic_load(env.ma_pool_full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 && ma_record_absent(env, p);
-        if (__builtin_amdgcn_readfirstlane(__shfl((int)waits, 0)) != 0) {
-          if (owner) kind = NEXT_SLOW;
-          break;
-        }
-      }
-#ifdef ARTIS_PROFILE_TAIL
-      tp[0] += clock64() - tps0;
-#endif
-    } else if (kind_w == NEXT_RPKT) {
-      // every lane runs the loop over the packet's steps; before a step that evaluates the continuum opacity (do_rpkt_step()'s own conditions:
-      // rpkt_step_evaluates_chi) the WAVE evaluates it -- the window's kept continua side by side, their terms added by the packet's lane in
-      // the sequential loop's order (physics.h chi_bf_gammacontr_wave) -- and the step finds it in the packet's cache
-      Chi x;
-      if (owner) chi_load(env.P, pi, p, x);
-      bool go = owner && rpkt_can_continue(p, ts_end);
-#ifdef ARTIS_PROFILE_TAIL
-      const long long tpr0 = clock64();
-#endif
-      while (__builtin_amdgcn_readfirstlane(__shfl((int)go, 0)) != 0) {
-#if ARTIS_TAIL_WAVE_CHI
-        int cc = 0;
-        const bool need = go && rpkt_step_evaluates_chi(env, p, x, &cc);
-        if (__builtin_amdgcn_readfirstlane(__shfl((int)need, 0)) != 0) {
-          const int cw = __builtin_amdgcn_readfirstlane(__shfl(cc, 0));
-          const double nuw = wave_bcast(p.nu_cmf, 0);
-          const int piw = __builtin_amdgcn_readfirstlane(__shfl(pi, 0));
-          chi_rpkt_cont_wave(env, nuw, x, cw, (int64_t)piw, owner);
-        }
-#endif
-        if (go) {
-          go = rpkt_iter(env, p, pi, x);
-#ifdef ARTIS_PROFILE_TAIL
-          tp_n[0]++;
-#endif
-        }
-      }
-#ifdef ARTIS_PROFILE_TAIL
-      tp[1] += clock64() - tpr0;
-#endif
-      if (owner) chi_store(env.P, pi, p, x);
-    } else if (kind_w == NEXT_MA || kind_w == NEXT_KPKT) {
-      if (owner) {
-        MACtx k = ma_ctx(env, p);
-        bool go = thermal_can_continue(p, ts_end);
-#ifdef ARTIS_PROFILE_TAIL
-        const long long tpt0 = clock64();
-        while (go) {
-          (void)thermal_iter(env, p, pi, k, &go);
-          tp_n[1]++;
-        }
-        tp[2] += clock64() - tpt0;
-#else
-        while (go) (void)thermal_iter(env, p, pi, k, &go);
-#endif
-      }
-    } else if (kind_w == NEXT_BB) {
-      TAILP(3, if (owner) (void)advance_blackbody(env, p, pi));
-    } else {
-      break;
-    }
-  }
-#ifdef ARTIS_PROFILE_TAIL
-  if (owner) {
-    const bool longwave = (tp[0] + tp[1] + tp[2] + tp[3]) > (1LL << 25);
-    for (int i = 0; i < 4; i++) {
-      atomicAdd(&lstats[42 + i], (stat_t)(tp[i] >> 4));
-      if (longwave) atomicAdd(&lstats[50 + i], (stat_t)(tp[i] >> 4));
-    }
-    atomicAdd(&lstats[46], (stat_t)tp_n[0]);
-    atomicAdd(&lstats[47], (stat_t)tp_n[1]);
-    if (longwave) {
-      atomicAdd(&lstats[54], (stat_t)1);
-      atomicAdd(&lstats[55], (stat_t)tp_n[0]);
-      atomicAdd(&lstats[56], (stat_t)tp_n[1]);
-    }
-  }
-#endif
-  if (owner) {
-    pkt_store(env.P, pi, p);
-    cellindex = p.cellindex;
-    nu_cmf = p.nu_cmf;
-  }
-  append_by_kind(kind, pi, cellindex, nu_cmf, next);
-  __syncthreads();
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-
-// slow path: the rare bound-free actions (rate coefficients with exp(), adaptive Gauss-Kronrod frequency sampling)
-// (round 6, with the build's machine LICM off: the classic options' slow path fits 167 VGPRs with 2 spilled, i.e. 3 waves per SIMD instead of 2;
-// the builds with interpolated cross-sections / the nebular family need 170-256 and keep what the compiler chooses)
-#ifndef ARTIS_SLOW_EU
-// (the nebular family's -- NLTE populations, the non-thermal channels -- takes 256 VGPRs + 22 AGPRs alone at one wave per SIMD; held to 256 it
-// spills 48 and runs two: k_slow 70.6 -> 51.4 ms, nltenebular step 1018 -> 1001 ms (profiles/r06/ab_slow.txt); kilonova_lte: no difference)
-#define ARTIS_SLOW_EU (ARTIS_OPT_PHIXS_CLASSIC_NO_INTERPOLATION ? 3 : (ARTIS_OPT_DETAILED_BF_ESTIMATORS_ON ? 2 : 1))
-#endif
-__global__ void __launch_bounds__(BLOCK, ARTIS_SLOW_EU) k_slow(Env env, const int32_t *list, int32_t n, Lists next, unsigned long long *gstats) {
-  __shared__ stat_t lstats[ARTIS_NSTATS];
-  __shared__ double lds_scalars[ARTIS_NSCALARS];
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  scalars_begin(env, lds_scalars);
-  __syncthreads();
-  env.stats = lstats;
-  env.ma_concurrent_fill = 1;  // this kernel's waves fill pool records while others read them: published places are read with acquire (physics.h ma_rowtab_acquire)
-  const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  int kind = NEXT_DONE;
-  int32_t pi = 0, cellindex = 0;
-  double nu_cmf = 0.;
-  // A free-bound emission's frequency (select_continuum_nu ratecoeff.cc:563: up to a hundred adaptive 31-point quadratures) is selected by
-  // the WAVE (physics.h FbSel): the action is first run on a copy of the packet up to the selection, whose arguments are recorded; the
-  // wave's lanes evaluate the abscissae of each rule side by side for one recorded selection after the other; then the action runs for real.
-  // (Round 4: one lane per emission while the other lanes of its wave waited -- lane utilisation 0.11; ARTIS_SLOW_WAVE_FB=0 builds that form.)
-  const bool mine = tid < n;
-  Pkt p;
-  FbSel sel;
-  sel.mode = 1;
-  sel.valid = false;
-  sel.element = sel.lowerion = sel.lower = sel.t = 0;
-  sel.T_e = 0.f;
-  sel.zrand = sel.nu = 0.;
-  if (mine) {
-    pi = list[tid];
-    pkt_load(env.P, pi, p);
-#ifdef ARTIS_PROFILE_SLOW
-    atomicAdd(&lstats[48 + (p.pend < 9 ? p.pend : 9)], (stat_t)1);  // (-DARTIS_PROFILE_SLOW: the slow-path visits by kind of pending action, stats slots 48..57)
-#endif
-  }
-#if ARTIS_SLOW_WAVE_FB
-  {
-    // (only where a few lanes of the wave have an emission: the wave takes them one after the other, each ~9x faster than a lane; with many --
-    // the nltenebular family, where a bound-free action is pending in nearly every round -- the lanes' own selections side by side are faster:
-    // k_slow 83 ms with the wave's form throughout against 68 ms)
-    const bool isfb = mine && slow_selects_continuum_nu(p);
-    const int nfb = __popcll(__ballot(isfb));
-    if (nfb > 0 && nfb <= ARTIS_SLOW_WAVE_FB_MAX) {
-      if (isfb) {
-        Pkt t = p;
-        (void)advance_slow(env, t, pi, &sel);
-      }
-      fbsel_wave(env, sel);
-    }
-  }
-#endif
-  if (env.ion_absent != nullptr) {  // a static record the population left out (tables.h "ABSENT IONS"): claimed by the lane, filled by the wave
-    int sc = 0, sul = 0;
-    // (... or that an action of the packet's macro-atom needs again after a refill of its row: physics.h ma_waits_for_static_fill)
-    const bool sfill = mine && ma_waits_for_static_fill(env, p) && ma_static_fill_claim(env, p, &sc, &sul);
-    ma_fill_wave<true>(env, sfill, sc, sul);
-  }
-  {  // a cold level's record (PEND_MA_FILL): claimed by the lane, filled by the wave, published by the lane
-    int fc = 0, ful = 0;
-    int32_t funit = 0;
-    const bool fill = ARTIS_MA_WAVE_FILL && mine && p.pend == PEND_MA_FILL && ma_slow_fill_claim(env, p, &fc, &ful, &funit);
-    ma_fill_wave(env, fill, fc, ful);
-    if (fill) ma_slow_fill_publish(env, fc, ful, funit);
-  }
-  if (mine) {
-    kind = advance_slow(env, p, pi, sel.valid ? &sel : nullptr);
-    pkt_store(env.P, pi, p);
-    cellindex = p.cellindex;
-    nu_cmf = p.nu_cmf;
-  }
-  append_by_kind(kind, pi, cellindex, nu_cmf, next);
-  __syncthreads();
-  scalars_flush(env);
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-
-// blackbody emission of pre-k-packets and of k-packets in grey cells: one do_kpkt_blackbody() per packet
-__global__ void __launch_bounds__(BLOCK) k_blackbody(Env env, const int32_t *list, int32_t n, Lists next, unsigned long long *gstats) {
-  __shared__ stat_t lstats[ARTIS_NSTATS];
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  __syncthreads();
-  env.stats = lstats;
-  const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-  int kind = NEXT_DONE;
-  int32_t pi = 0, cellindex = 0;
-  double nu_cmf = 0.;
-  if (tid < n) {
-    pi = list[tid];
-    Pkt p;
-    pkt_load_thermal(env.P, pi, p);
-    kind = advance_blackbody(env, p, pi);
-    pkt_store_thermal(env.P, pi, p);
-    cellindex = p.cellindex;
-    nu_cmf = p.nu_cmf;
-  }
-  append_by_kind(kind, pi, cellindex, nu_cmf, next);
-  __syncthreads();
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-
-#if ARTIS_OPT_VPKT_ON
-// Virtual packets (vpkt.cc): the emissions and electron scatterings the launch before recorded (physics.h trace_vpkts), one
-// lane per (event, observer direction): the optical depths of every opacity choice along the ray to the grid's edge, then
-// the attenuated energy into that observer's spectrum (f64 atomics). Nothing of the real packets is read or written.
-// Persistent and work-pulling like the propagation kernels: a lane whose ray has ended (left the grid, absorbed beyond tau_max, met a
-// thick cell) takes the next (event, observer) pair at once -- rays cross 1 ... 50 cells, and with one ray per lane from start to end a
-// wave lasted as long as its longest.
-#ifndef ARTIS_VPKT_WGS
-#define ARTIS_VPKT_WGS 4
-#endif
-#ifndef ARTIS_VPKT_TB
-#define ARTIS_VPKT_TB 768  // threads of the one workgroup per CU of the form with the continuum table in LDS: 3 waves/SIMD at 168 VGPRs.
-                          // Virtual-packet bench (1e6 packets, t = 5 d): 1470 / 1284 / 1290 ms per step at 1024 / 768 / 512 (MI355X, round 4)
-#endif
-constexpr int VPKT_CHUNKS = 2048;
-// CONT_LDS (round 4): the static continuum table in LDS as in k_rpkt -- every cell a ray crosses sums the bound-free opacity
-// (chi_bf_gammacontr) -- with ONE workgroup of 1024 threads per CU instead of four of 256 (the same 4 waves/SIMD).
-template <bool CONT_LDS, int TB>
-__global__ void __launch_bounds__(TB, (CONT_LDS ? 1 : ARTIS_VPKT_WGS)) k_vpkt(Env env, unsigned long long *gstats, int32_t *cursors) {
-  __shared__ stat_t lstats[ARTIS_NSTATS];
-  __shared__ ContPack lds_cont[CONT_LDS ? CONT_LDS_MAX : 1];
-  if (threadIdx.x < ARTIS_NSTATS) lstats[threadIdx.x] = 0;
-  if (CONT_LDS) {
-    const D2 *src = (const D2 *)env.M.cont_pack;
-    D2 *dst = (D2 *)lds_cont;
-    for (int i = threadIdx.x; i < env.M.nbfcontinua * 2; i += TB) dst[i] = src[i];
-    env.M.cont_pack = lds_cont;
-    env.cont_in_lds = 1;
-  }
-  __syncthreads();
-  env.stats = lstats;
-  const int nobs = env.M.vpkt->nobsdirections;
-  const int64_t n64 = (int64_t)min(*env.vpkt_count, env.vpkt_cap) * nobs;
-  const VpktSeed *queue = env.vpkt_queue;
-  if (n64 < 0x7FFFFFF0LL) {
-    const int32_t n = (int32_t)n64;
-    Puller q;
-    puller_init(q, n, VPKT_CHUNKS);
-    bool have = false;
-    VRay ray;
-    while (true) {
-      const int32_t idx = pull(q, !have, cursors);
-      if (idx >= 0) have = vray_begin_seed(env, queue[idx / nobs], idx % nobs, ray);
-      if (!__any(have)) {
-        if (q.exhausted) break;
-        continue;
-      }
-      if (have) have = vray_step(env, ray);
-    }
-  } else {  // (more pairs than a list index holds: one ray per lane from start to end)
-    for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n64; i += (int64_t)gridDim.x * TB) {
-      const VpktSeed seed = queue[i / nobs];
-      vpkt_trace_seed_direction(env, seed, (int)(i % nobs));
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < ARTIS_NSTATS && lstats[threadIdx.x] != 0) atomicAdd(&gstats[threadIdx.x], lstats[threadIdx.x]);
-}
-#endif
+// ------------------------------------------------------------------ the kernels, inside this anonymous namespace, in the order they build on each other
+#include "cellcache_kernels.h"      // populate kernels
+#include "list_kernels.h"           // packet layout, work lists, k_classify
+#include "sort_kernels.h"           // the work lists' sorts
+#include "rpkt_kernels.h"           // work pulling, k_rpkt, the dense bound-free estimator rows
+#include "gamma_kernel.h"           // k_gamma
+#include "thermal_kernels.h"        // k_thermal
+#include "thermal_refill_kernel.h"  // k_thermal_q
+#include "late_kernel.h"            // k_late
+#include "tail_slow_kernels.h"      // k_tail, k_slow, k_blackbody
+#include "vpkt_kernel.h"            // k_vpkt
 
 inline int nblocks(int64_t n) { return (int)((n + BLOCK - 1) / BLOCK); }
 
@@ -2152,7 +311,7 @@ struct artis_amd_engine {
   bool estcache = true;        // ARTIS_AMD_ESTCACHE=0: k_rpkt without its waves' caches of per-cell accumulators (physics.h Env::estcache)
   int sort_maxpc_r = 20000;
   int sort_maxpc_t = 600;
-  // one list chunk per wave instead of one per XCD (artis_engine.hip pull): measured on MI355X, 1e7 packets: k_rpkt -4 %
+  // one list chunk per wave instead of one per XCD (work_pull.h pull): measured on MI355X, 1e7 packets: k_rpkt -4 %
   // (a wave's lanes share continuum windows and line ranges), k_thermal +30 % (every wave then has its own cells in
   // flight and the L2 working set of macro-atom records triples)
   bool wave_chunks_r = true, wave_chunks_t = false;

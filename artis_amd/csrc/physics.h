@@ -4447,7 +4447,7 @@ AHD void ma_slow_fill(const Env &env, Pkt &p) {
 AHD bool ma_slow_record_ready(const Env &env, Pkt &p) {
   const DevModel &M = env.M;
   // (tables.h "ABSENT IONS") ... or it was a static record filled on demand, and the row's refill has put the marker back: the slow-path kernel
-  // fills it again (the action's lane claims it first, artis_engine.hip k_slow); while another wave is at it, ask again. A record that is
+  // fills it again (the action's lane claims it first, tail_slow_kernels.h k_slow); while another wave is at it, ask again. A record that is
   // there may have been completed by another wave of this very launch: its loads come after an acquire (the filler's release: populate_macroatom).
   // (Only the records of an ion that is absent in the cell are ever filled on demand: every other action pays one byte's read.)
   if (env.ion_absent != nullptr && ma_level_static(env, p) && ma_ion_absent(env, M.propcell_nonemptymgi[p.cellindex], uion(M, p.ma_element, p.ma_ion))) {
@@ -4473,7 +4473,7 @@ AHD bool ma_slow_record_ready(const Env &env, Pkt &p) {
 }
 
 #if defined(__HIPCC__) && !defined(ARTIS_HOST_EMU)
-// ma_slow_fill() in three parts for the kernels that let the WAVE fill the record (artis_engine.hip ma_fill_record_wave): the lane claims the
+// ma_slow_fill() in three parts for the kernels that let the WAVE fill the record (cellcache_kernels.h ma_fill_record_wave): the lane claims the
 // level's place and takes units of the pool (true: this lane's record is to be filled at *unit; the packet's pend is cleared either way),
 // the wave fills, the lane publishes.
 __device__ inline bool ma_slow_fill_claim(const Env &env, Pkt &p, int *c_out, int *ul_out, int32_t *unit_out) {
@@ -5902,7 +5902,7 @@ AHD bool thermal_can_continue(const Pkt &p, double ts_end) {
   return pkt_active(p, ts_end) && p.type != ARTIS_TYPE_RPKT && !type_gamma(p.type);
 }
 // returns the units of work done (transitions + k-packet steps); *go = the packet can take another iteration.
-// (artis_engine.hip k_thermal spells the two phases out so that the wave reconverges between them.)
+// (thermal_round.inc, the body of k_thermal, spells the two phases out so that the wave reconverges between them.)
 AHD int thermal_iter(const Env &env, Pkt &p, int64_t pi, MACtx &k, bool *go) {
   const double ts_end = env.S.ts_end;
   int j = 0;

@@ -1,5 +1,5 @@
-// work_pull.h -- how the persistent, work-pulling kernels hand the indices of their work list to their waves (artis_engine.hip "the propagation
-// kernels"): Puller, puller_init(), chunk_at(), pull(). Included by artis_engine.hip inside its namespace; the same text compiles for the host under
+// work_pull.h -- how the persistent, work-pulling kernels hand the indices of their work list to their waves (rpkt_kernels.h "the propagation
+// kernels"): Puller, puller_init(), chunk_at(), pull(). Included by rpkt_kernels.h inside artis_engine.hip's namespace; the same text compiles for the host under
 // ARTIS_HOST_EMU (tests/pull_host), where one host thread stands for a wave: it calls puller_place() and pull_wave() with the mask of its asking
 // lanes. No includes of its own: <cstdint> comes from the including file.
 //

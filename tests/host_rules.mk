@@ -1,5 +1,6 @@
-# Shared by tests/radfield_host and tests/ionbal_host: lib$(NAME)_<preset>.so from $(NAME).cc, one per options preset of $(PRESETS).
+# Shared by the tests/*_host harnesses that build one library per options preset: lib$(NAME)_<preset>.so from $(NAME).cc, one per options preset of $(PRESETS).
 # Same FP flags as tests/hostemu.
+include ../csrc_deps.mk
 CXX ?= g++
 CXXFLAGS = -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wextra -Wno-unused-parameter -Wno-unused-function -Wno-unused-variable -Wno-unknown-pragmas -pthread
 upper = $(shell echo $(1) | tr a-z A-Z)

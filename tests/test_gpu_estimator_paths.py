@@ -1,7 +1,7 @@
 """GPU tests of the ways the kernels ADD UP the per-cell estimators, each against the CPU oracle with the per-entry bar of
 parity.compare_estimators, and each form against the others on the device (run with `pytest -m gpu`).
 
-Which form a kernel takes follows from the number of non-empty cells (artis_engine.hip: RPKT_CELLEST_CAP 512 with the
+Which form a kernel takes follows from the number of non-empty cells (rpkt_kernels.h: RPKT_CELLEST_CAP 512 with the
 continuum table in LDS, RPKT_CELLEST_CAP_NOCONT 3072 without it, GAMMA_CELLEST_CAP 2048, THERMAL_CELLEST_CAP 4096) and from
 the ARTIS_AMD_* switches:
 - the workgroup's LDS array of per-cell sums (cellest_add / cellest_flush) at or below a cap;

@@ -1,4 +1,4 @@
-"""GPU tests of the many-keys work-list sort (artis_engine.hip k_sort_tilehist / k_sort_tilescatter / k_sort_plan / k_sort_segments), through
+"""GPU tests of the many-keys work-list sort (sort_kernels.h k_sort_tilehist / k_sort_tilescatter / k_sort_plan / k_sort_segments), through
 artis_amd_debug_sort_list on the engine of a 5^3 model. Every case asserts that the output is a permutation of the list and that the keys of
 its entries, read back through each entry's position in the input, are non-decreasing. The order among equal keys is free.
 
