@@ -203,6 +203,15 @@ _CELL_OPTIONAL = ("levelpops", "corrphotoioncoeff", "radfieldbin_W", "radfieldbi
                   "nt_ionenfrac_num_auger", "nt_exc_count", "nt_exc_frac_deposition", "nt_exc_ratecoeffperdeposition",
                   "nt_exc_alltransindex", "nt_excitations_stored", "expansionopacities", "expansionopacity_planck_cumulative", "Jb_lu_normed",
                   "elem_meanweight")
+# enum artis_amd_cc_array of include/artis_amd.h (artis_amd_debug_cellcache_array): name -> (enumerator, element type, elements per entry)
+CC_ARRAYS = {
+    "line_dpop": (0, np.float64, 1), "bf_radrecomb": (1, np.float64, 1), "bf_colrecomb": (2, np.float64, 1), "bf_colion": (3, np.float64, 1),
+    "bf_cooling": (4, np.float64, 1), "allcont_pair": (5, np.float64, 2), "allcont_keptlist": (6, np.int32, 1),
+    "allcont_keepprefix": (7, np.int32, 1), "allcont_keptpair": (8, np.float64, 2), "cool_guide": (9, np.uint16, 1),
+    "ion_cooling_C": (10, np.float64, 1), "expansionopacities": (11, np.float32, 1),
+    "expansionopacity_planck_cumulative": (12, np.float64, 1), "nt_ionratecoeff": (13, np.float64, 1), "nt_ionenrate_cum": (14, np.float64, 1),
+    "allcont_keepbits": (15, np.uint64, 1),
+}
 NT_NAUGER = 3  # NT_MAX_AUGER_ELECTRONS + 1
 RADFIELDBINCOUNT = 256
 # options presets with the multibin radiation field and the detailed bound-free estimators (artisoptions_nltenebular.h and

@@ -2,6 +2,7 @@
 // cache (the decisions are cache_residency.h's; here are the copies and the fills they ask for), and the entry points that populate, describe
 // and inspect the cache. The sizing of the rows stays with engine_fill, which artis_amd_engine_plan shares.
 #pragma once
+#include "cellcache_view.h"
 namespace {
 // ---- populate_tile()'s steps
 // The pool of on-demand records: a fill of the whole cache empties it. A fill of some cells of a tiled cache leaves it alone -- the cells that stay
@@ -149,6 +150,22 @@ void choose_cells(artis_amd_engine *e, const std::vector<int32_t> &waiting, std:
   artis_residency::choose_cells(e->cc.res, waiting, h.npts_nonempty, e->cc.tile_block, e->cc.sparse_fill, e->cc.sparse_max_listed, win_lo, grid, want,
                                 holds, sparse);
 }
+// the debug views: the row of cell c, once the cache is filled (one tile) or the cell resident (several)
+int debug_row_of(artis_amd_engine *e, int c, int *row) {
+  *row = c;
+  if (e->cc.ntiles == 1) {  // the cache has to be filled
+    if (e->cc.tile_valid_lo != 0) {
+      int rc = populate_tile(e, nullptr);
+      if (rc != ARTIS_OK) return rc;
+    }
+  } else {  // the cell has to be resident
+    int64_t nfilled = 0;
+    int rc = make_resident(e, std::vector<int32_t>{(int32_t)c}, nullptr, &nfilled);
+    if (rc != ARTIS_OK) return rc;
+    *row = e->cc.res.krow[(size_t)c];  // its row
+  }
+  return ARTIS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -184,17 +201,7 @@ int artis_amd_debug_cellcache(artis_amd_engine *e, int c, double *levelpops, dou
   HIP_TRY(hipSetDevice(e->device));
   const DevModel &h = e->Mh;
   const int cell = c;
-  if (e->cc.ntiles == 1) {  // the cache has to be filled
-    if (e->cc.tile_valid_lo != 0) {
-      int rc = populate_tile(e, nullptr);
-      if (rc != ARTIS_OK) return rc;
-    }
-  } else {  // the cell has to be resident
-    int64_t nfilled = 0;
-    int rc = make_resident(e, std::vector<int32_t>{(int32_t)c}, nullptr, &nfilled);
-    if (rc != ARTIS_OK) return rc;
-    c = e->cc.res.krow[(size_t)c];  // its row
-  }
+  if (const int rc = debug_row_of(e, cell, &c)) return rc;
 #define DL(dst, f, T, per)                                                                                            \
   if (dst && (per) > 0) HIP_TRY(hipMemcpy(dst, e->K.f + (int64_t)c * (per), sizeof(T) * (size_t)(per), hipMemcpyDeviceToHost));
   DL(levelpops, levelpops, double, h.nlevels)
@@ -235,6 +242,33 @@ int artis_amd_debug_cellcache(artis_amd_engine *e, int c, double *levelpops, dou
   DL(ion_cooling_contribs, ion_cooling_contribs, double, h.nions)
   DL(chi_ff_nnionpart, chi_ff_nnionpart, double, 1)
 #undef DL
+  return ARTIS_OK;
+}
+
+int artis_amd_debug_cellcache_array(artis_amd_engine *e, int c, int which, void *dst, int64_t dst_bytes, int64_t *written_bytes) {
+  if (written_bytes) *written_bytes = 0;
+  if (!e || !e->have_cells || c < 0 || c >= e->Mh.npts_nonempty || !dst) {
+    g_last_error = "bad cell index, no cell state or no buffer";
+    return ARTIS_ERR_ARG;
+  }
+  CcArrayView v;
+  if (!cc_array_view(e->Mh, e->C, e->K, e->expopac_own, which, &v)) {
+    g_last_error = "cell-cache array " + std::to_string(which) + " does not exist in this build or model";
+    return ARTIS_ERR_ARG;
+  }
+  const int64_t bytes = (int64_t)v.elem * v.per;
+  if (dst_bytes < bytes) {
+    if (written_bytes) *written_bytes = bytes;  // (nothing was written: what the row needs)
+    g_last_error = "cell-cache array " + std::to_string(which) + ": the row has " + std::to_string((long long)bytes) + " bytes, the buffer " +
+                   std::to_string((long long)dst_bytes);
+    return ARTIS_ERR_ARG;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  int row = c;
+  if (const int rc = debug_row_of(e, c, &row)) return rc;
+  const int64_t r = v.by_row ? row : c;
+  HIP_TRY(hipMemcpy(dst, (const char *)v.base + (r * bytes), (size_t)bytes, hipMemcpyDeviceToHost));
+  if (written_bytes) *written_bytes = bytes;
   return ARTIS_OK;
 }
 

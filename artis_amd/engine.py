@@ -128,6 +128,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_set_cellstate_photoion", "artis_amd_photoion_download",
     "artis_amd_sizeof_config", "artis_amd_config_default", "artis_amd_engine_create_ex", "artis_amd_engine_config",
     "artis_amd_sizeof_plan", "artis_amd_engine_plan",
+    "artis_amd_debug_cellcache_array",
 ]
 
 
@@ -654,6 +655,26 @@ class Engine:
         self._check(self.L.artis_amd_debug_cellcache(*args))
         out["chi_ff_nnionpart"] = chi.value
         return out
+
+    def debug_cellcache_array(self, c: int, which) -> np.ndarray:
+        """artis_amd_debug_cellcache_array: one array of cell c's row as stored, typed (abi.CC_ARRAYS: name -> (enumerator, dtype, doubles per
+        element); the two arrays of pairs come as (n, 2) float64). which: a name of abi.CC_ARRAYS or an enumerator. EngineError where the
+        array does not exist in this build or model."""
+        idx, dtype, width = abi.CC_ARRAYS[which] if isinstance(which, str) else next(v for v in abi.CC_ARRAYS.values() if v[0] == int(which))
+        itemsize = np.dtype(dtype).itemsize
+        need = C.c_int64(0)
+        probe = np.zeros(1, dtype=np.uint8)
+        self.L.artis_amd_debug_cellcache_array.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        rc = self.L.artis_amd_debug_cellcache_array(self.h, int(c), idx, probe.ctypes.data_as(C.c_void_p), 0, C.byref(need))  # (asks for the row's size)
+        if need.value <= 0:
+            self._check(rc)
+            raise EngineError(f"artis_amd_debug_cellcache_array({which}): no size reported")
+        assert need.value % (itemsize * width) == 0, (which, need.value)
+        buf = np.zeros(need.value // itemsize, dtype=dtype)
+        written = C.c_int64(0)
+        self._check(self.L.artis_amd_debug_cellcache_array(self.h, int(c), idx, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(written)))
+        assert written.value == buf.nbytes, (which, written.value, buf.nbytes)
+        return buf.reshape(-1, 2) if width == 2 else buf
 
     def debug_sort_list(self, keys, lst, nkeys: int):
         """lst's entries ordered by non-decreasing key, by the many-keys work-list sort (artis_amd_debug_sort_list); keys[i] in [0, nkeys)

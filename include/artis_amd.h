@@ -712,6 +712,37 @@ int artis_amd_debug_cellcache(artis_amd_engine *eng, int nonemptymgi, double *le
                               double *matrans, double *allcont_nnlevel, double *allcont_departure,
                               double *allcont_edgepart, uint64_t *allcont_keepbits, double *corrphotoioncoeff,
                               double *cooling_contrib, double *ion_cooling_contribs, double *chi_ff_nnionpart);
+/* Diagnostics: ONE array of a cell's row AS STORED -- the arrays the view above does not show: what the population keeps for the
+ * packet kernels beside the reference's spans, the engine's own expansion-opacity tables and the derived non-thermal arrays. The cell is made
+ * resident or the cache filled exactly as by artis_amd_debug_cellcache(), and the row is found through the row table (a tiled cache: the row
+ * of a cell is not its index). `dst` receives the row's bytes, *written_bytes (may be NULL) their number.
+ *   element types: double, but ALLCONT_PAIR / _KEPTPAIR {double, double}; ALLCONT_KEEPBITS uint64 (the padded row, nkeepwords words);
+ *   ALLCONT_KEPTLIST / _KEEPPREFIX int32; COOL_GUIDE uint16; EXPANSIONOPACITIES float.
+ *   ALLCONT_KEPTLIST and _KEPTPAIR have a place for every continuum; the population writes the first (number of set keep bits) places.
+ * ARTIS_ERR_ARG: the array does not exist in this build or model (LINE_DPOP of an engine that forms the factors on the fly; COOL_GUIDE without
+ * guides; the expansion tables of another build or handed over by the host, the Planck integral without RPKT_BB_THERMALISATION; the non-thermal
+ * arrays without NT_ON), an unknown enumerator, or dst_bytes smaller than the row (nothing is copied then, and *written_bytes receives the
+ * row's size; in the other two cases it receives 0). */
+enum artis_amd_cc_array {
+  ARTIS_AMD_CC_LINE_DPOP = 0,           /* [ndpop] */
+  ARTIS_AMD_CC_BF_RADRECOMB = 1,        /* [nphixstargets_total] */
+  ARTIS_AMD_CC_BF_COLRECOMB = 2,
+  ARTIS_AMD_CC_BF_COLION = 3,
+  ARTIS_AMD_CC_BF_COOLING = 4,
+  ARTIS_AMD_CC_ALLCONT_PAIR = 5,        /* [nbfcontinua][2] */
+  ARTIS_AMD_CC_ALLCONT_KEPTLIST = 6,    /* [nbfcontinua] */
+  ARTIS_AMD_CC_ALLCONT_KEEPPREFIX = 7,  /* [nkeepwords] */
+  ARTIS_AMD_CC_ALLCONT_KEPTPAIR = 8,    /* [nbfcontinua][2] */
+  ARTIS_AMD_CC_COOL_GUIDE = 9,          /* [nguide] */
+  ARTIS_AMD_CC_ION_COOLING_C = 10,      /* [nions] the ions' cooling totals before the prefix sum */
+  ARTIS_AMD_CC_EXPANSIONOPACITIES = 11,              /* [ARTIS_EXPOPAC_NBINS] float */
+  ARTIS_AMD_CC_EXPANSIONOPACITY_PLANCK_CUMULATIVE = 12, /* [ARTIS_EXPOPAC_NBINS] */
+  ARTIS_AMD_CC_NT_IONRATECOEFF = 13,    /* [nions] */
+  ARTIS_AMD_CC_NT_IONENRATE_CUM = 14,   /* [nions] */
+  ARTIS_AMD_CC_ALLCONT_KEEPBITS = 15,   /* [nkeepwords] the whole padded row of the bitmap */
+  ARTIS_AMD_CC_COUNT = 16
+};
+int artis_amd_debug_cellcache_array(artis_amd_engine *eng, int nonemptymgi, int which, void *dst, int64_t dst_bytes, int64_t *written_bytes);
 /* Test / debug: the many-keys work-list sort (more than 8192 keys) on host arrays. keys[i] in [0, nkeys) is the key of list[i]; out[0..n)
  * receives list's entries ordered by non-decreasing key (any order among equal keys). A list shorter than 512 entries is copied as it is, as
  * the propagation leaves it. The engine's lists are not touched (its sort scratch is used, and grown for a longer list). ARTIS_ERR_UNSUPPORTED for more keys than the sort

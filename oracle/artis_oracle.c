@@ -1517,12 +1517,17 @@ static inline double get_linedistance(double prop_time, double nu_cmf, double nu
 #endif
 }
 /* get_tau_sobolev<true> rpkt.cc:75 */
-static inline double get_tau_sobolev(const Oracle *o, const CellCache *cc, int lineindex, double t_current) {
+static inline double tau_sobolev_popfactor(const Oracle *o, const CellCache *cc, int lineindex, double *absorbed, double *stimulated) {
   const double n_l = cc->levelpops[o->m->line_uniquelevelindex_lower[lineindex]];
   const double n_u = cc->levelpops[o->m->line_uniquelevelindex_upper[lineindex]];
   const double B_ul = o->m->line_B_ul[lineindex];
   const double B_lu = o->m->line_B_lu[lineindex];
-  return dmax(((B_lu * n_l) - (B_ul * n_u)) * HCLIGHTOVERFOURPI * t_current, 0.);
+  if (absorbed) *absorbed = B_lu * n_l; /* the two terms of the difference, for artis_oracle_cellcache_extra */
+  if (stimulated) *stimulated = B_ul * n_u;
+  return (B_lu * n_l) - (B_ul * n_u);
+}
+static inline double get_tau_sobolev(const Oracle *o, const CellCache *cc, int lineindex, double t_current) {
+  return dmax(tau_sobolev_popfactor(o, cc, lineindex, NULL, NULL) * HCLIGHTOVERFOURPI * t_current, 0.);
 }
 /* get_nu_cmf_abort rpkt.cc:54 */
 static double get_nu_cmf_abort(const double pos[3], const double dir[3], double prop_time, double nu_rf, double abort_dist) {
@@ -3569,6 +3574,93 @@ int artis_oracle_cellcache(const artis_model *m, const artis_cellstate *cs, cons
   memcpy(cooling_contrib, cc->cooling_contrib, sizeof(double) * (size_t)m->ncoolingterms);
   memcpy(ion_cooling_contribs, cc->ion_cooling_contribs, sizeof(double) * (size_t)m->nions);
   *chi_ff_nnionpart = cc->chi_ff_nnionpart;
+  const int err = o.error;
+  oracle_free(&o);
+  return err ? -1 : 0;
+}
+
+/* What the engine's rows keep beside those spans (tables.h DevCache, artis_amd_debug_cellcache_array), from the functions above -- no formula
+ * is restated here. Any pointer may be NULL.
+ *   line_dpop [nlines]: the population factor of get_tau_sobolev (rpkt.cc:75); line_dpop_terms [nlines][2]: the two terms B_lu n_l and
+ *     B_ul n_u it is the difference of (a test measures a difference of nearly equal terms against the larger term);
+ *   bf_* [nphixstargets_total]: of the bound-free pair (level, target) the coefficients rad_recombination_ratecoeff / col_recombination_ratecoeff
+ *     (macroatom.cc:646, :660: as the recombining level's loop calls them), col_ionisation_ratecoeff (macroatom.cc:686) and the coefficient of the
+ *     bound-free cooling term (get_bfcoolingcoeff, kpkt.cc:165);
+ *   ion_cooling_C [nions]: calculate_cooling_rates_ion() of every ion, the totals kpkt.cc:288-294 adds up;
+ *   expansionopacities / expansionopacity_planck_cumulative [ARTIS_EXPOPAC_NBINS]: the cell cache's own tables (calculate_expansion_opacities);
+ *     *have_expopac = 0 and nothing written where the cache has none (another build, tables of the host, a thick cell: update_grid.cc:655);
+ *   nt_ionratecoeff [nions]: nt_ionisation_ratecoeff of every ion with a higher stage (0 for an element's last ion, which select_nt_ionisation
+ *     never asks for); nt_ionenrate_cum [nions]: the running sum of ion_ntion_energyrate in select_nt_ionisation's order (an element's last ion
+ *     repeats the sum so far); *have_nt = 0 and nothing written without NT_ON. */
+int artis_oracle_cellcache_extra(const artis_model *m, const artis_cellstate *cs, const artis_timestep *ts, int nonemptymgi, double *line_dpop,
+                                 double *line_dpop_terms, double *bf_radrecomb, double *bf_colrecomb, double *bf_colion, double *bf_cooling,
+                                 double *ion_cooling_C, float *expansionopacities, double *expansionopacity_planck_cumulative,
+                                 int *have_expopac, double *nt_ionratecoeff, double *nt_ionenrate_cum, int *have_nt) {
+  Oracle o;
+  int64_t stats[ARTIS_NSTATS] = {0};
+  artis_estimators est;
+  memset(&est, 0, sizeof(est));
+  est.stats = stats;
+  oracle_init(&o, m, cs, ts, &est);
+  const int c = nonemptymgi;
+  cellcache_populate(&o, c);
+  const CellCache *cc = &o.cache[c];
+  const float T_e = cs->Te[c];
+  const float clumpednne = cell_clumpednne(&o, c);
+  for (int li = 0; li < m->nlines; li++) {
+    double absorbed = 0., stimulated = 0.;
+    const double dpop = tau_sobolev_popfactor(&o, cc, li, &absorbed, &stimulated);
+    if (line_dpop) line_dpop[li] = dpop;
+    if (line_dpop_terms) {
+      line_dpop_terms[2 * li] = absorbed;
+      line_dpop_terms[(2 * li) + 1] = stimulated;
+    }
+  }
+  for (int element = 0; element < m->nelements; element++) {
+    const int nions = get_nions(&o, element);
+    for (int ion = 0; ion < nions; ion++) {
+      const int ui = uniqueion(&o, element, ion);
+      if (ion_cooling_C) ion_cooling_C[ui] = calculate_cooling_rates_ion(&o, cc, c, element, ion, NULL);
+      if (ion == nions - 1) continue;
+      const int start = ionlevelstart(&o, element, ion);
+      for (int level = 0; level < get_nlevels(&o, element, ion); level++) {
+        const int ul = start + level;
+        for (int t = 0; t < m->level_nphixstargets[ul]; t++) {
+          const int k = m->level_phixstargetstart[ul] + t;
+          const double epsilon_trans = get_phixs_threshold(&o, element, ion, level, t);
+          if (bf_radrecomb) bf_radrecomb[k] = rad_recombination_ratecoeff(&o, T_e, clumpednne, element, ion + 1, level, t);
+          if (bf_colrecomb) bf_colrecomb[k] = col_recombination_ratecoeff(&o, T_e, clumpednne, element, ion + 1, level, t, epsilon_trans);
+          if (bf_colion) bf_colion[k] = col_ionisation_ratecoeff(&o, T_e, clumpednne, element, ion, level, t, epsilon_trans);
+          if (bf_cooling) bf_cooling[k] = get_bfcoolingcoeff(&o, ul, t, T_e);
+        }
+      }
+    }
+  }
+  if (have_expopac) *have_expopac = 0;
+#if ARTIS_EXPOPAC_TABLES
+  if (cc->expansionopacities) {
+    if (have_expopac) *have_expopac = 1;
+    if (expansionopacities) memcpy(expansionopacities, cc->expansionopacities, sizeof(float) * ARTIS_EXPOPAC_NBINS);
+    if (expansionopacity_planck_cumulative)
+      memcpy(expansionopacity_planck_cumulative, cc->expansionopacity_planck_cumulative, sizeof(double) * ARTIS_EXPOPAC_NBINS);
+  }
+#endif
+  if (have_nt) *have_nt = 0;
+#if ARTIS_OPT_NT_ON
+  if (have_nt) *have_nt = 1;
+  {
+    double ratesum = 0.;
+    for (int element = 0; element < m->nelements; element++) {
+      const int nions = get_nions(&o, element);
+      for (int ion = 0; ion < nions; ion++) {
+        const int ui = uniqueion(&o, element, ion);
+        if (ion < nions - 1) ratesum += ion_ntion_energyrate(&o, c, element, ion);
+        if (nt_ionratecoeff) nt_ionratecoeff[ui] = (ion < nions - 1) ? nt_ionisation_ratecoeff(&o, c, element, ion) : 0.;
+        if (nt_ionenrate_cum) nt_ionenrate_cum[ui] = ratesum;
+      }
+    }
+  }
+#endif
   const int err = o.error;
   oracle_free(&o);
   return err ? -1 : 0;

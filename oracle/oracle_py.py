@@ -100,7 +100,7 @@ def update_packets(model: abi.Model, cells: abi.CellState, ts: abi.Timestep, pac
         raise RuntimeError("oracle reported an internal assertion failure")
 
 
-def cellcache(model: abi.Model, cells: abi.CellState, ts: abi.Timestep, nonemptymgi: int) -> dict:
+def cellcache(model: abi.Model, cells: abi.CellState, ts: abi.Timestep, nonemptymgi: int, preset: str = "classic") -> dict:
     d = model.d
     out = {
         "levelpops": np.zeros(d["nlevels"]),
@@ -117,8 +117,41 @@ def cellcache(model: abi.Model, cells: abi.CellState, ts: abi.Timestep, nonempty
     chi = C.c_double(0.0)
     args = [C.cast(model.ref(), C.c_void_p), C.cast(cells.ref(), C.c_void_p), C.cast(ts.ref(), C.c_void_p),
             C.c_int(nonemptymgi)] + [v.ctypes.data_as(C.c_void_p) for v in out.values()] + [C.byref(chi)]
-    rc = lib().artis_oracle_cellcache(*args)
+    rc = lib(preset).artis_oracle_cellcache(*args)
     if rc != 0:
         raise RuntimeError("oracle cellcache failed")
     out["chi_ff_nnionpart"] = chi.value
+    return out
+
+
+def cellcache_extra(model: abi.Model, cells: abi.CellState, ts: abi.Timestep, nonemptymgi: int, preset: str = "classic") -> dict:
+    """artis_oracle_cellcache_extra: what the engine's rows keep beside the reference's spans, from the oracle's own functions. The expansion
+    tables and the non-thermal arrays are present only where the oracle's cell cache has them (an expansion-opacity build with no tables from
+    the host and a cell that is not thick; an NT_ON build). line_dpop_terms: (nlines, 2), the two terms line_dpop is the difference of."""
+    d = model.d
+    nt = max(int(d["nphixstargets_total"]), 1)
+    out = {
+        "line_dpop": np.zeros(max(int(d["nlines"]), 1)), "line_dpop_terms": np.zeros(2 * max(int(d["nlines"]), 1)),
+        "bf_radrecomb": np.zeros(nt), "bf_colrecomb": np.zeros(nt), "bf_colion": np.zeros(nt), "bf_cooling": np.zeros(nt),
+        "ion_cooling_C": np.zeros(int(d["nions"])),
+        "expansionopacities": np.zeros(abi.EXPOPAC_NBINS, dtype=np.float32), "expansionopacity_planck_cumulative": np.zeros(abi.EXPOPAC_NBINS),
+    }
+    ntarr = {"nt_ionratecoeff": np.zeros(int(d["nions"])), "nt_ionenrate_cum": np.zeros(int(d["nions"]))}
+    have_expopac, have_nt = C.c_int(0), C.c_int(0)
+    L = lib(preset)
+    L.artis_oracle_cellcache_extra.restype = C.c_int
+    args = [C.cast(model.ref(), C.c_void_p), C.cast(cells.ref(), C.c_void_p), C.cast(ts.ref(), C.c_void_p), C.c_int(nonemptymgi)] + \
+           [v.ctypes.data_as(C.c_void_p) for v in out.values()] + [C.byref(have_expopac)] + \
+           [v.ctypes.data_as(C.c_void_p) for v in ntarr.values()] + [C.byref(have_nt)]
+    rc = L.artis_oracle_cellcache_extra(*args)
+    if rc != 0:
+        raise RuntimeError("oracle cellcache_extra failed")
+    out["line_dpop"] = out["line_dpop"][:int(d["nlines"])]
+    out["line_dpop_terms"] = out["line_dpop_terms"][:2 * int(d["nlines"])].reshape(-1, 2)
+    for k in ("bf_radrecomb", "bf_colrecomb", "bf_colion", "bf_cooling"):
+        out[k] = out[k][:int(d["nphixstargets_total"])]
+    if not have_expopac.value:
+        del out["expansionopacities"], out["expansionopacity_planck_cumulative"]
+    if have_nt.value:
+        out.update(ntarr)
     return out

@@ -14,6 +14,7 @@
 
 #include "../../artis_amd/csrc/model_build.h"
 #include "../../artis_amd/csrc/physics.h"
+#include "../../artis_amd/csrc/cellcache_view.h"
 
 using namespace artis;
 
@@ -455,13 +456,10 @@ int artis_emu_update_packets(const artis_model *m, const artis_cellstate *cs, co
 // times the last artis_emu_update_packets() call found the pool of on-demand records used up and emptied it
 int artis_emu_last_pool_resets() { return g_last_pool_resets; }
 
-int artis_emu_cellcache(const artis_model *m, const artis_cellstate *cs, const artis_timestep *ts, int c, double *levelpops,
-                        double *maprocessrates, double *matrans, double *allcont_nnlevel, double *allcont_departure,
-                        double *allcont_edgepart, uint64_t *allcont_keepbits, double *corrphotoioncoeff, double *cooling_contrib,
-                        double *ion_cooling_contribs, double *chi_ff_nnionpart) {
-  Emu e;
-  setup(e, m, cs, ts, nullptr, 1);
-  populate_all(e);
+// the reference's spans of cell c from the populated rows of e (artis_emu_cellcache, artis_emu_cc_main)
+static int cellcache_main(Emu &e, int c, double *levelpops, double *maprocessrates, double *matrans, double *allcont_nnlevel,
+                          double *allcont_departure, double *allcont_edgepart, uint64_t *allcont_keepbits, double *corrphotoioncoeff,
+                          double *cooling_contrib, double *ion_cooling_contribs, double *chi_ff_nnionpart) {
   const DevModel &M = e.env.M;
   const DevCache &K = e.env.K;
   std::memcpy(levelpops, K.levelpops + (int64_t)c * M.nlevels, sizeof(double) * M.nlevels);
@@ -494,5 +492,66 @@ int artis_emu_cellcache(const artis_model *m, const artis_cellstate *cs, const a
   std::memcpy(ion_cooling_contribs, K.ion_cooling_contribs + (int64_t)c * M.nions, sizeof(double) * M.nions);
   *chi_ff_nnionpart = K.chi_ff_nnionpart[c];
   return e.err;
+}
+int artis_emu_cellcache(const artis_model *m, const artis_cellstate *cs, const artis_timestep *ts, int c, double *levelpops,
+                        double *maprocessrates, double *matrans, double *allcont_nnlevel, double *allcont_departure,
+                        double *allcont_edgepart, uint64_t *allcont_keepbits, double *corrphotoioncoeff, double *cooling_contrib,
+                        double *ion_cooling_contribs, double *chi_ff_nnionpart) {
+  Emu e;
+  setup(e, m, cs, ts, nullptr, 1);
+  populate_all(e);
+  return cellcache_main(e, c, levelpops, maprocessrates, matrans, allcont_nnlevel, allcont_departure, allcont_edgepart, allcont_keepbits,
+                        corrphotoioncoeff, cooling_contrib, ion_cooling_contribs, chi_ff_nnionpart);
+}
+
+// The same views of rows that stay: the population of every cell runs once (artis_emu_cc_open; *err: its error flag), then the reference's spans
+// (artis_emu_cc_main) and any array of a row as stored (artis_emu_cc_array: the engine's artis_amd_debug_cellcache_array, same enumerators, -1
+// where the engine returns ARTIS_ERR_ARG) are read cell by cell. The model and the cell state have to outlive the handle.
+void *artis_emu_cc_open(const artis_model *m, const artis_cellstate *cs, const artis_timestep *ts, int *err) {
+  Emu *e = new Emu;
+  setup(*e, m, cs, ts, nullptr, 1);
+  populate_all(*e);
+  if (err) *err = e->err;
+  return e;
+}
+void artis_emu_cc_close(void *h) { delete static_cast<Emu *>(h); }
+int artis_emu_cc_main(void *h, int c, double *levelpops, double *maprocessrates, double *matrans, double *allcont_nnlevel,
+                      double *allcont_departure, double *allcont_edgepart, uint64_t *allcont_keepbits, double *corrphotoioncoeff,
+                      double *cooling_contrib, double *ion_cooling_contribs, double *chi_ff_nnionpart) {
+  Emu &e = *static_cast<Emu *>(h);
+  if (c < 0 || c >= e.env.M.npts_nonempty) return -1;
+  return cellcache_main(e, c, levelpops, maprocessrates, matrans, allcont_nnlevel, allcont_departure, allcont_edgepart, allcont_keepbits,
+                        corrphotoioncoeff, cooling_contrib, ion_cooling_contribs, chi_ff_nnionpart);
+}
+int artis_emu_cc_array(void *h, int c, int which, void *dst, int64_t dst_bytes, int64_t *written_bytes) {
+  Emu &e = *static_cast<Emu *>(h);
+  if (written_bytes) *written_bytes = 0;
+  CcArrayView v;
+  if (c < 0 || c >= e.env.M.npts_nonempty || !dst || !cc_array_view(e.env.M, e.env.C, e.env.K, e.expopac_own, which, &v)) return -1;
+  const int64_t bytes = (int64_t)v.elem * v.per;
+  if (dst_bytes < bytes) {
+    if (written_bytes) *written_bytes = bytes;
+    return -1;
+  }
+  std::memcpy(dst, (const char *)v.base + (krow(e.env, c) * bytes), (size_t)bytes);  // (every cell is resident here: an array of DevCells has the same index)
+  if (written_bytes) *written_bytes = bytes;
+  return 0;
+}
+// A row of cooling guides (tables.h "COOLING GUIDES") for the cumulative lists given: cool_guide_entry() of every entry, laid out as
+// populate_cool_guide() lays a cell's row out. Returns nguide of the model (0: no guides); fills out[0 .. min(nguide, cap)).
+int artis_emu_cool_guide_row(const artis_model *m, const double *ion_cooling_contribs, const double *cooling_contrib, uint16_t *out, int64_t cap) {
+  Emu e;
+  std::memset(&e.env, 0, sizeof(e.env));
+  double hot = 1., pool = 0.25;
+  ma_tiers_from_env(&hot, &pool);
+  e.env.M = make_host_model_view(*m, e.own, hot, pool);
+  const DevModel &M = e.env.M;
+  std::vector<uint16_t> row((size_t)M.nguide + 1, 0);
+  e.env.K.cool_guide = row.data();
+  e.env.K.ion_cooling_contribs = const_cast<double *>(ion_cooling_contribs);
+  e.env.K.cooling_contrib = const_cast<double *>(cooling_contrib);
+  for (int g = 0; g < M.nguide; g++) populate_cool_guide(e.env, 0, g);
+  for (int64_t g = 0; g < M.nguide && g < cap; g++) out[g] = row[(size_t)g];
+  return M.nguide;
 }
 }
