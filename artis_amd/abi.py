@@ -762,6 +762,53 @@ def packet_init_arrays(ngrid: int, ncell: int, npaths: int, npackets: int) -> di
                 trials=np.zeros(npackets, np.int32))
 
 
+# initial temperatures and the first cell state (include/artis_amd.h artis_amd_initial_state*)
+GREY_FEGROUP_APPROX, GREY_TANAKA2020, GREY_JUST2022 = 0, 1, 2
+INITIAL_INSIDE, INITIAL_BELOW_MINTEMP, INITIAL_ABOVE_MAXTEMP, INITIAL_NONFINITE = 0, 1, 2, 3
+INITIAL_BRANCH_MASK, INITIAL_KAPPA_INVALID = 3, 4
+INITIAL_BRANCHES = ("inside", "below_mintemp", "above_maxtemp", "nonfinite")
+INITIAL_KERNELS = ("energy", "cells")
+
+
+class InitialParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("tstart", C.c_double), ("nts_first", C.c_int32), ("num_grey_timesteps", C.c_int32),
+                ("optical_depth_is_thick", C.c_double), ("optical_depth_is_thick_vpkt", C.c_double), ("rpkt_grey_type", C.c_int32),
+                ("mfegroup", C.c_double), ("mtot_input", C.c_double), ("ffegrp", _F32P), ("initelectronfrac", _F32P), ("energy_vector", _F64P)]
+
+
+class InitialResult(C.Structure):
+    _fields_ = [("struct_size", C.c_int64), ("T_initial", _F32P), ("endecay_per_mass", _F64P), ("kappagrey", _F32P), ("grey_depth", _F32P),
+                ("thick", _I32P), ("flags", _I32P), ("energy_vector", _F64P), ("path_scale", _F64P), ("path_x_dom", _F64P),
+                ("ncells_branch", C.c_int64 * 4), ("ncells_kappa_invalid", C.c_int64), ("first_nonfinite_cell", C.c_int32),
+                ("npts_nonempty", C.c_int32), ("npaths", C.c_int32), ("rpkt_grey_type", C.c_int32), ("nts_first", C.c_int32),
+                ("reserved", C.c_int32), ("first_nonfinite_rho_tmin", C.c_double), ("first_nonfinite_endecay", C.c_double),
+                ("tstart", C.c_double), ("kernel_ms", C.c_double * 2)]
+
+
+def initial_params(d: dict):
+    """(InitialParams, the arrays it points into: keep them alive while it is used) from a dict over artis_initial_params's fields
+    (synth.initial_model plus tstart and the step's numbers); an array that is None or missing stays a NULL pointer"""
+    keep = {}
+    p = InitialParams(struct_size=C.sizeof(InitialParams), tstart=float(d["tstart"]), nts_first=int(d.get("nts_first", 0)),
+                      num_grey_timesteps=int(d.get("num_grey_timesteps", 0)), optical_depth_is_thick=float(d.get("optical_depth_is_thick", 0.0)),
+                      optical_depth_is_thick_vpkt=float(d.get("optical_depth_is_thick_vpkt", 0.0)), rpkt_grey_type=int(d.get("rpkt_grey_type", 0)),
+                      mfegroup=float(d.get("mfegroup", 0.0)), mtot_input=float(d.get("mtot_input", 0.0)))
+    for k, dt, pt in (("ffegrp", np.float32, _F32P), ("initelectronfrac", np.float32, _F32P), ("energy_vector", np.float64, _F64P)):
+        if d.get(k) is None:
+            continue
+        a = np.ascontiguousarray(d[k], dtype=dt).reshape(-1)
+        keep[k] = a if a.size else np.zeros(1, dt)
+        setattr(p, k, keep[k].ctypes.data_as(pt))
+    return p, keep
+
+
+def initial_arrays(ncell: int, npaths: int) -> dict:
+    """zeroed host arrays for the outputs of artis_initial_result (the keys are its field names)"""
+    return dict(T_initial=np.zeros(ncell, np.float32), endecay_per_mass=np.zeros(ncell), kappagrey=np.zeros(ncell, np.float32),
+                grey_depth=np.zeros(ncell, np.float32), thick=np.zeros(ncell, np.int32), flags=np.zeros(ncell, np.int32),
+                energy_vector=np.zeros(npaths), path_scale=np.zeros(npaths), path_x_dom=np.zeros(npaths))
+
+
 # thermal balance of the thin cells (include/artis_amd.h artis_amd_thermal_*)
 THERMAL_BRACKETED, THERMAL_PINNED_LOW, THERMAL_PINNED_HIGH, THERMAL_NONFINITE = 256, 512, 1024, 2048
 THERMAL_DAMPED_UP, THERMAL_DAMPED_DOWN, THERMAL_MAXIT, THERMAL_RENORM_ONE = 4096, 8192, 16384, 32768

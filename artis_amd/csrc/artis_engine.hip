@@ -33,6 +33,7 @@
 #include "decay_update.h"
 #include "deposition.h"
 #include "packet_init.h"
+#include "initial_state.h"
 #include "thermal_balance.h"
 #include "bf_heating.h"
 #include "ratecoeff_tables.h"
@@ -85,6 +86,9 @@ struct DepState;
 void dep_free(DepState *st);
 struct PinitState;
 void pinit_free(PinitState *st);
+struct InitState;
+void init_free(InitState *st);
+void init_invalidate(InitState *st);  // a new decay set-up: what the initial state was made on is gone
 struct TbState;
 void tb_free(TbState *st);
 struct BfhState;
@@ -165,6 +169,7 @@ struct artis_amd_engine {
   DecayState *decay = nullptr;  // artis_amd_decay_*: nothing until artis_amd_decay_setup
   DepState *dep = nullptr;      // artis_amd_deposition_*: nothing until artis_amd_deposition_setup
   PinitState *pinit = nullptr;  // artis_amd_packet_init*: nothing until artis_amd_packet_init_setup
+  InitState *init = nullptr;    // artis_amd_initial_state*: nothing until the first call
   TbState *tb = nullptr;        // artis_amd_thermal_*: nothing until the first call
   BfhState *bfh = nullptr;      // artis_amd_bfheating_*: nothing until the first call
   RcState *rc = nullptr;        // artis_amd_ratecoeff_*: nothing until the first call
@@ -1284,6 +1289,7 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
   decay_free(e->decay);
   dep_free(e->dep);
   pinit_free(e->pinit);
+  init_free(e->init);
   tb_free(e->tb);
   bfh_free(e->bfh);
   rc_free(e->rc);
@@ -1302,14 +1308,42 @@ void artis_amd_engine_destroy(artis_amd_engine *e) {
 
 namespace {
 
+// The arrays every cell state has (ARTIS_CELL_ARRAYS), allocated in place of the previous state's; the optional ones absent. Shared by
+// cellstate_upload, which copies the host's arrays into them, and by the hand-over of artis_amd_grid_update_initial (stage_ionbal.h),
+// which asks for them zeroed and fills them on the device. No cell state is resident afterwards until the caller says so.
+int cellstate_alloc(artis_amd_engine *e, const bool zeroed) {
+  e->have_cells = false;  // until every array of the new state is resident
+  free_all(e->cell_allocs);
+  e->pi_coeff = nullptr;
+  const DevModel &h = e->Mh;
+#define ALC(f, T, count)                                                \
+  {                                                                     \
+    T *d = nullptr;                                                     \
+    const int64_t cnt = (int64_t)(count);                               \
+    const size_t bytes = sizeof(T) * (size_t)(cnt > 0 ? cnt : 1);       \
+    HIP_TRY(hipMalloc((void **)&d, bytes));                             \
+    e->cell_allocs.push_back(d);                                        \
+    if (zeroed) HIP_TRY(hipMemset(d, 0, bytes));                        \
+    e->C.f = d;                                                         \
+  }
+  ARTIS_CELL_ARRAYS(ALC, h)
+#undef ALC
+#define NUL(f, T, count) e->C.f = nullptr;
+  ARTIS_CELL_OPTIONAL_ARRAYS(NUL, h)
+#undef NUL
+  e->C.nt_excitations_stored = 0;
+  e->C.nt_ionratecoeff = nullptr;
+  e->C.nt_ionenrate_cum = nullptr;
+  return ARTIS_OK;
+}
+
+int cellstate_options(artis_amd_engine *e, const bool corrphotoioncoeff_follows);
+
 // artis_amd_set_cellstate in two halves, shared with artis_amd_set_cellstate_photoion (stage_photoion.h), which computes
 // corrphotoioncoeff between them. The first: the uploads and what the build's options need from the host; corrphotoioncoeff_follows:
 // the caller makes that array on the device before cellstate_finish.
 int cellstate_upload(artis_amd_engine *e, const artis_cellstate *cells, const artis_timestep *ts, const bool corrphotoioncoeff_follows) {
   HIP_TRY(hipSetDevice(e->device));
-  e->have_cells = false;  // until every array of the new state is resident
-  free_all(e->cell_allocs);
-  e->pi_coeff = nullptr;
   const DevModel &h = e->Mh;
   DevCells hc = make_host_cells_view(*cells);
   std::vector<float> zero_ffegrp;
@@ -1317,11 +1351,10 @@ int cellstate_upload(artis_amd_engine *e, const artis_cellstate *cells, const ar
     zero_ffegrp.assign((size_t)(h.npts_nonempty > 0 ? h.npts_nonempty : 1), 0.f);
     hc.ffegrp = zero_ffegrp.data();
   }
-#define UPC(f, T, count)                                                                   \
-  {                                                                                        \
-    int rc = upload_array<T>(e->cell_allocs, hc.f, (int64_t)(count), (const T **)&e->C.f); \
-    if (rc != ARTIS_OK) return rc;                                                         \
-  }
+  int rc = cellstate_alloc(e, false);
+  if (rc != ARTIS_OK) return rc;
+#define UPC(f, T, count) \
+  if ((int64_t)(count) > 0) HIP_TRY(hipMemcpy(const_cast<T *>(e->C.f), hc.f, sizeof(T) * (size_t)(count), hipMemcpyHostToDevice));
   ARTIS_CELL_ARRAYS(UPC, h)
 #undef UPC
 #define UPO(f, T, count)                                                                     \
@@ -1336,9 +1369,16 @@ int cellstate_upload(artis_amd_engine *e, const artis_cellstate *cells, const ar
   ARTIS_CELL_OPTIONAL_ARRAYS(UPO, h)
 #undef UPO
   e->C.nt_excitations_stored = (int32_t)nt_stored;
-  e->C.nt_ionratecoeff = nullptr;
-  e->C.nt_ionenrate_cum = nullptr;
-  // what the options this library was built with need from the host
+  rc = cellstate_options(e, corrphotoioncoeff_follows);
+  if (rc != ARTIS_OK) return rc;
+  e->S = make_step(*ts);
+  return ARTIS_OK;
+}
+
+// what the options this library was built with need of a cell state whose arrays are in place (absent optional ones null): the
+// refusals, and the expansion-opacity tables the engine makes itself
+int cellstate_options(artis_amd_engine *e, const bool corrphotoioncoeff_follows) {
+  const DevModel &h = e->Mh;
   if (!ARTIS_OPT_USE_LUT_PHOTOION && h.nphixstargets_total > 0 && !e->C.corrphotoioncoeff && !corrphotoioncoeff_follows) {
     g_last_error = "this build has USE_LUT_PHOTOION off: artis_cellstate.corrphotoioncoeff is required";
     return ARTIS_ERR_ARG;
@@ -1378,7 +1418,6 @@ int cellstate_upload(artis_amd_engine *e, const artis_cellstate *cells, const ar
       return ARTIS_ERR_ARG;
     }
   }
-  e->S = make_step(*ts);
   return ARTIS_OK;
 }
 
@@ -1907,6 +1946,7 @@ int artis_amd_debug_sort_list(artis_amd_engine *e, const int32_t *keys, const in
 #include "stage_decay.h"
 #include "stage_deposition.h"
 #include "stage_packet_init.h"
+#include "stage_initial.h"
 #include "stage_thermal.h"
 #include "stage_bfheat.h"
 #include "stage_ratecoeff.h"

@@ -99,6 +99,7 @@ int artis_amd_decay_setup(artis_amd_engine *e, const artis_decay_model *d) {
   e->dep = nullptr;
   pinit_free(e->pinit);  // ... and the pellet set-up made on both
   e->pinit = nullptr;
+  init_invalidate(e->init);  // ... and an initial state made on all three is no longer one of this network
   DecayState *st = new DecayState();
   st->ncell = n;
   const int64_t nn = d->nnuclides, np = d->npaths, nflat = (int64_t)r.path_lambda.size(), nrow = (int64_t)r.row_coef.size();

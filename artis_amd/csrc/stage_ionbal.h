@@ -149,7 +149,57 @@ struct IbMatter {
   const float *thermal_Te = nullptr;
   const double *thermal_gamma = nullptr, *thermal_renorm = nullptr;
   const float *thermal_clump = nullptr;  // ... and the clumping factors of every cell the solve's (they become the cell state's)
+  // artis_amd_grid_update_initial (stage_initial.h): the first timestep. T_J = T_R = T_e = initial_T, W = initial_W (ones) and
+  // kappagrey are the initial state's (device arrays), and so is the balance's "current" state: ground populations of 0 and THICK
+  // flags, what the reference holds before its first update_grid. No cell state has to be resident
+  const float *initial_T = nullptr, *initial_W = nullptr, *initial_kappagrey = nullptr, *initial_ground = nullptr;
+  const int32_t *initial_thick = nullptr;
 };
+
+__global__ void __launch_bounds__(BLOCK) k_ib_fill(double *dst, double value, int64_t count) {
+  const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i < count) dst[i] = value;
+}
+
+// The first cell state of an engine that has none (the hand-over of artis_amd_grid_update_initial): the arrays of
+// artis_amd_set_cellstate, allocated zeroed, and what the hand-over below does not write. Where every array of DevCells that a
+// supported build's propagation or a later stage reads then comes from:
+//   rho, elem_massfracs, elem_meanweight (allocated here, ahead of the    the decay update, through the balance's scratch
+//   options' refusals, in USE_CALCULATED_MEANATOMICWEIGHT builds)
+//   Te, TJ, TR, W, kappagrey, thick                                       the initial state (stage_initial.h), through the scratch
+//   nne, nnetot, ion_partfuncts, ion_groundlevelpops                      the balance
+//   clumpfactor                                                           u->clumpfactor (required here)
+//   ffegrp                                                                u->ffegrp, else zeros as artis_amd_set_cellstate uploads for an absent one
+//   corrphotoionrenorm                                                    1 in every cell (grid.cc:561; the balance's forced Saha writes the same)
+//   expansionopacities, expansionopacity_planck_cumulative                the engine's own, made at cell-cache population (cellstate_options)
+//   levelpops, corrphotoioncoeff, radfieldbin_*, nt_*, Jb_lu_normed       absent, as after an artis_amd_set_cellstate without them; a build
+//                                                                         that needs one from the host is refused by cellstate_options
+// On an error no state is resident and nothing of it is kept.
+int ib_first_cellstate(artis_amd_engine *e, hipStream_t s) {
+  int rc = cellstate_alloc(e, true);
+  const int64_t nmw = (int64_t)e->Mh.npts_nonempty * e->Mh.nelements;
+  if (rc == ARTIS_OK && ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && nmw > 0) {
+    // before cellstate_options: a build that reads element number densities (XCOM, NT_ON) refuses a state without this array
+    float *d = nullptr;
+    if (hipMalloc((void **)&d, sizeof(float) * (size_t)nmw) != hipSuccess) {
+      rc = stage_error(ARTIS_ERR_HIP, "grid_update_initial: allocation of elem_meanweight");
+    } else {
+      e->cell_allocs.push_back(d);
+      e->C.elem_meanweight = d;
+    }
+  }
+  if (rc == ARTIS_OK) rc = cellstate_options(e, false);
+  const int64_t nrenorm = (int64_t)e->Mh.npts_nonempty * (e->Mh.nbfcontinua_ground > 0 ? e->Mh.nbfcontinua_ground : 1);
+  if (rc == ARTIS_OK && nrenorm > 0) {  // (after the allocation's hipMemset, which has ended when it returns: StageBlock::make relies on the same)
+    hipLaunchKernelGGL(k_ib_fill, dim3(nblocks(nrenorm)), dim3(BLOCK), 0, s, const_cast<double *>(e->C.corrphotoionrenorm), 1., nrenorm);
+    if (hipGetLastError() != hipSuccess) rc = stage_error(ARTIS_ERR_HIP, "grid_update_initial: k_ib_fill");
+  }
+  if (rc != ARTIS_OK) {
+    free_all(e->cell_allocs);
+    e->C = DevCells{};
+  }
+  return rc;
+}
 
 // artis_amd_grid_update (matter == nullptr: u's host arrays) and artis_amd_grid_update_decayed (matter: copied device to device into the same scratch)
 int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_timestep *ts_next, void *hip_stream, const IbMatter *matter) {
@@ -158,11 +208,12 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
   return stage_error(ARTIS_ERR_UNSUPPORTED, "grid_update: this build has NLTE populations (the nebular family): the ion balance is the host's");
 #endif
   STAGE_STRUCT_SIZE(u, artis_grid_update, "grid_update");
-  if (!e->have_cells) return stage_error(ARTIS_ERR_ARG, "grid_update: no cell state (artis_amd_set_cellstate)");
+  const bool initial = matter && matter->initial_T;
+  if (!e->have_cells && !initial) return stage_error(ARTIS_ERR_ARG, "grid_update: no cell state (artis_amd_set_cellstate)");
   if (u->use_fit != 0 && u->use_fit != 1) return stage_error(ARTIS_ERR_ARG, "grid_update: use_fit must be 0 or 1");
   if (u->use_fit && (!e->rf || !e->rf->valid || !e->fit_since_step))
     return stage_error(ARTIS_ERR_ARG, "grid_update: use_fit = 1 needs an artis_amd_radfield_fit since the last propagation call");
-  if (!u->use_fit && (!u->TJ || !u->TR || !u->W || !u->Te)) return stage_error(ARTIS_ERR_ARG, "grid_update: use_fit = 0 needs TJ, TR, W and Te");
+  if (!u->use_fit && !initial && (!u->TJ || !u->TR || !u->W || !u->Te)) return stage_error(ARTIS_ERR_ARG, "grid_update: use_fit = 0 needs TJ, TR, W and Te");
   if (!matter && (!u->rho || !u->elem_massfracs || !u->thick)) return stage_error(ARTIS_ERR_ARG, "grid_update: rho, elem_massfracs and thick are required");
   if (matter && !matter->thick && !u->thick) return stage_error(ARTIS_ERR_ARG, "grid_update: thick is required");
   if (!matter && ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !u->elem_meanweight)
@@ -185,10 +236,13 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
     HIP_TRY(stage_copy(st->d_thick, u->thick, n, hipMemcpyHostToDevice, &s));
   if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT)
     HIP_TRY(stage_copy(st->d_meanweight, matter ? matter->meanweight : u->elem_meanweight, n * ne, from_matter, &s));
-  HIP_TRY(stage_copy(st->d_kappagrey, u->kappagrey, n, hipMemcpyHostToDevice, &s));
+  if (initial)
+    HIP_TRY(stage_copy(st->d_kappagrey, matter->initial_kappagrey, n, hipMemcpyDeviceToDevice, &s));
+  else
+    HIP_TRY(stage_copy(st->d_kappagrey, u->kappagrey, n, hipMemcpyHostToDevice, &s));
   HIP_TRY(stage_copy(st->d_clump, u->clumpfactor, n, hipMemcpyHostToDevice, &s));
   HIP_TRY(stage_copy(st->d_ffegrp, u->ffegrp, n, hipMemcpyHostToDevice, &s));
-  if (!u->use_fit) {
+  if (!u->use_fit && !initial) {
     HIP_TRY(stage_copy(st->d_hTJ, u->TJ, n, hipMemcpyHostToDevice, &s));
     HIP_TRY(stage_copy(st->d_hTR, u->TR, n, hipMemcpyHostToDevice, &s));
     HIP_TRY(stage_copy(st->d_hW, u->W, n, hipMemcpyHostToDevice, &s));
@@ -204,10 +258,14 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
   a.fit_W = u->use_fit ? e->rf->d_W : st->d_hW;
   a.fit_Te = u->use_fit ? e->rf->d_Te : st->d_hTe;
   a.fit_flags = u->use_fit ? e->rf->d_flags : nullptr;
+  if (initial) {
+    a.fit_TJ = a.fit_TR = a.fit_Te = matter->initial_T;
+    a.fit_W = matter->initial_W;
+  }
   a.host_Te = (u->use_fit && u->Te) ? st->d_hTe : nullptr;
   if (matter && matter->thermal_Te) a.host_Te = matter->thermal_Te;
-  a.cur_ground = e->C.ion_groundlevelpops;
-  a.cur_thick = e->C.thick;
+  a.cur_ground = initial ? matter->initial_ground : e->C.ion_groundlevelpops;
+  a.cur_thick = initial ? matter->initial_thick : e->C.thick;
   a.gamma_raw = e->E.gammaestimator;
   if (u->use_fit) {
     a.assocvol = e->rf->d_assocvol;
@@ -294,6 +352,8 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
                                                 std::to_string(st->ncells_flagged[4]) + " / " + std::to_string(st->ncells_flagged[6]) + " / " +
                                                 std::to_string(st->ncells_flagged[5]) + "); the previous cell state stays");
   // the hand-over: the engine's cell state becomes the result (artis_amd_set_cellstate), then the cell cache is filled
+  const bool first_state = !e->have_cells;
+  if (first_state && (rc = ib_first_cellstate(e, s)) != ARTIS_OK) return rc;
   if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT && !e->C.elem_meanweight && n * ne > 0) {
     float *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, sizeof(float) * (size_t)(n * ne)));
@@ -311,7 +371,7 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
   HIP_TRY(stage_copy(e->C.ion_groundlevelpops, st->d_ground, n * ni, hipMemcpyDeviceToDevice, &s));
   HIP_TRY(stage_copy(e->C.elem_massfracs, st->d_massfrac, n * ne, hipMemcpyDeviceToDevice, &s));
   if (ARTIS_OPT_USE_CALCULATED_MEANATOMICWEIGHT) HIP_TRY(stage_copy(e->C.elem_meanweight, st->d_meanweight, n * ne, hipMemcpyDeviceToDevice, &s));
-  if (u->kappagrey) HIP_TRY(stage_copy(e->C.kappagrey, st->d_kappagrey, n, hipMemcpyDeviceToDevice, &s));
+  if (u->kappagrey || initial) HIP_TRY(stage_copy(e->C.kappagrey, st->d_kappagrey, n, hipMemcpyDeviceToDevice, &s));
   if (u->clumpfactor) HIP_TRY(stage_copy(e->C.clumpfactor, st->d_clump, n, hipMemcpyDeviceToDevice, &s));
   if (matter && matter->thermal_clump) HIP_TRY(stage_copy(e->C.clumpfactor, matter->thermal_clump, n, hipMemcpyDeviceToDevice, &s));
   if (u->ffegrp) HIP_TRY(stage_copy(e->C.ffegrp, st->d_ffegrp, n, hipMemcpyDeviceToDevice, &s));
@@ -328,6 +388,7 @@ int ib_grid_update(artis_amd_engine *e, const artis_grid_update *u, const artis_
   // (the thickness last: the balance and the renormalisation read the current one)
   HIP_TRY(stage_copy(e->C.thick, st->d_thick, n, hipMemcpyDeviceToDevice, &s));
   HIP_TRY(hipStreamSynchronize(s));
+  e->have_cells = true;  // (it was, but after the first state of artis_amd_grid_update_initial)
   e->cellstate_serial++;
   e->S = make_step(*ts_next);
   const auto t0 = std::chrono::steady_clock::now();

@@ -80,6 +80,9 @@ def load_library(build_if_missing: bool = False, preset: str = "classic"):
     L.artis_amd_packet_init_setup.argtypes = [C.c_void_p, C.POINTER(abi.PacketInitModel)]
     L.artis_amd_packet_init.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p, C.c_void_p]
     L.artis_amd_packet_init_download.argtypes = [C.c_void_p, C.POINTER(abi.PacketInitResult)]
+    L.artis_amd_initial_state.argtypes = [C.c_void_p, C.POINTER(abi.InitialParams), C.c_void_p]
+    L.artis_amd_initial_state_download.argtypes = [C.c_void_p, C.POINTER(abi.InitialResult)]
+    L.artis_amd_grid_update_initial.argtypes = [C.c_void_p, C.POINTER(abi.GridUpdate), C.c_void_p, C.c_void_p]
     L.artis_amd_thermal_solve.argtypes = [C.c_void_p, C.POINTER(abi.ThermalParams), C.c_void_p]
     L.artis_amd_thermal_rates.argtypes = [C.c_void_p, C.POINTER(abi.ThermalParams), C.c_void_p, C.c_int, C.c_void_p]
     L.artis_amd_thermal_download.argtypes = [C.c_void_p, C.POINTER(abi.ThermalResult)]
@@ -122,6 +125,7 @@ EXPORTED_SYMBOLS = [
     "artis_amd_deposition_setup", "artis_amd_deposition_update", "artis_amd_deposition_download", "artis_amd_deposition_devptr",
     "artis_amd_grid_update_deposited",
     "artis_amd_packet_init_setup", "artis_amd_packet_init", "artis_amd_packet_init_download",
+    "artis_amd_initial_state", "artis_amd_initial_state_download", "artis_amd_grid_update_initial",
     "artis_amd_thermal_solve", "artis_amd_thermal_rates", "artis_amd_thermal_download", "artis_amd_grid_update_thermal",
     "artis_amd_bfheating_update", "artis_amd_bfheating_download", "artis_amd_thermal_solve_bfheated", "artis_amd_debug_gk61",
     "artis_amd_ratecoeff_compute", "artis_amd_ratecoeff_download",
@@ -488,6 +492,46 @@ class Engine:
             out[k] = float(getattr(info, k))
         out["kernel_ms"] = {k: float(info.kernel_ms[i]) for i, k in enumerate(abi.PINIT_KERNELS)}
         return out
+
+    # initial temperatures and the first cell state (include/artis_amd.h artis_amd_initial_state*)
+    def initial_state(self, params: dict, stream: int = 0) -> dict:
+        """T_initial, kappagrey, grey depth and thickness flag of every cell before the first timestep, on the device: a dict over
+        artis_initial_params's fields (synth.initial_model plus tstart, nts_first, num_grey_timesteps and the depths; energy_vector
+        [npaths] from the host, used as it is, or absent: the device forms it). Needs decay_setup, deposition_setup, packet_init_setup
+        and a decay_update at tstart. Returns the download."""
+        p, keep = abi.initial_params(params)
+        self._check(self.L.artis_amd_initial_state(self.h, C.byref(p), C.c_void_p(stream)))
+        del keep
+        return self.initial_state_download()
+
+    def initial_state_download(self, arrays: bool = True) -> dict:
+        """numpy arrays under the field names of artis_initial_result, "ncells_branch" as a dict over abi.INITIAL_BRANCHES, the reported
+        scalars, "kernel_ms" as a dict over abi.INITIAL_KERNELS; arrays=False: only the reported fields"""
+        info = abi.InitialResult(struct_size=C.sizeof(abi.InitialResult))
+        self._check(self.L.artis_amd_initial_state_download(self.h, C.byref(info)))  # sizes first
+        out = abi.initial_arrays(info.npts_nonempty, info.npaths) if arrays else {}
+        types = dict(abi.InitialResult._fields_)
+        for k, v in out.items():
+            if v.size:
+                setattr(info, k, v.ctypes.data_as(types[k]))
+        if arrays:
+            self._check(self.L.artis_amd_initial_state_download(self.h, C.byref(info)))
+        out["ncells_branch"] = {k: int(info.ncells_branch[i]) for i, k in enumerate(abi.INITIAL_BRANCHES)}
+        for k in ("ncells_kappa_invalid", "first_nonfinite_cell", "npts_nonempty", "npaths", "rpkt_grey_type", "nts_first"):
+            out[k] = int(getattr(info, k))
+        for k in ("first_nonfinite_rho_tmin", "first_nonfinite_endecay", "tstart"):
+            out[k] = float(getattr(info, k))
+        out["kernel_ms"] = {k: float(info.kernel_ms[i]) for i, k in enumerate(abi.INITIAL_KERNELS)}
+        return out
+
+    def grid_update_initial(self, ts_first: abi.Timestep, clumpfactor=None, ffegrp=None, stream: int = 0) -> dict:
+        """The first cell state: grid_update with the matter of the last decay_update(ts_first.mid) and the temperatures, W = 1,
+        kappagrey and thickness flags of the last initial_state, none of which leaves the device. Needs no set_cellstate before it."""
+        u, keep = abi.grid_update_config(False, None, None, None, clumpfactor=clumpfactor, ffegrp=ffegrp)
+        self._check(self.L.artis_amd_grid_update_initial(self.h, C.byref(u), C.cast(ts_first.ref(), C.c_void_p), C.c_void_p(stream)))
+        self._ts = ts_first
+        del keep
+        return self.grid_update_download()
 
     # thermal balance of the thin cells (include/artis_amd.h artis_amd_thermal_*)
     def thermal_solve(self, bfheatingcoeffs, rho=None, elem_massfracs=None, elem_meanweight=None, ntlepton_dep=None, dep_alpha=None,

@@ -1199,3 +1199,23 @@ def packet_init_model(model: abi.Model, network: dict, energies: dict, tmax: flo
                use_model_initial_energy=int(initial_energy), uniform_pellet_energies=1, max_trials_per_launch=int(max_trials_per_launch),
                initenergyq=initenergyq(model, seed + 6) if initial_energy else None)
     return out
+
+
+# ---- initial temperatures and the first cell state (include/artis_amd.h artis_amd_initial_state*)
+def initial_model(model: abi.Model, cs: abi.CellState, rpkt_grey_type: int = 0, seed: int = 53) -> dict:
+    """The model-side fields of artis_initial_params for a grid made by build(): ffegrp (the cell state's), mfegroup and mtot_input as
+    calc_modelinit_totmassnuclides sums them over the cells in order (grid.cc:953-971, one propagation cell per model cell here), and
+    initelectronfrac [npts_nonempty] spread over Tanaka's table (0.05 to 0.45: every row and the 0.96 above the last). The caller adds
+    tstart, nts_first, num_grey_timesteps and the optical depths."""
+    rng = np.random.default_rng(seed)
+    n = int(model["npts_nonempty"])
+    ffegrp = np.asarray(cs["ffegrp"], np.float32) if cs["ffegrp"] is not None else np.zeros(n, np.float32)
+    vol = assocvolume_tmin(model)
+    mtot = mfe = 0.0
+    for c in range(n):
+        mass = float(np.float32(model["rho_tmin"][c])) * float(vol[c])
+        if mass > 0:
+            mtot += mass
+            mfe += mass * float(ffegrp[c])
+    return dict(rpkt_grey_type=int(rpkt_grey_type), ffegrp=ffegrp, mfegroup=mfe, mtot_input=mtot,
+                initelectronfrac=rng.uniform(0.05, 0.45, n).astype(np.float32))

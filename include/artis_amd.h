@@ -1109,6 +1109,74 @@ int artis_amd_packet_init(artis_amd_engine *eng, int64_t npackets, uint32_t seed
 /* Copy the results of the last artis_amd_packet_init to the host (sizes in the reported fields even when every pointer is NULL). */
 int artis_amd_packet_init_download(artis_amd_engine *eng, artis_packet_init_result *out);
 
+/* ---- initial temperatures and the first cell state ------------------------------------------
+ * What the reference does to the cells before the first timestep, on the device: assign_initial_temperatures() (grid.cc:1077-1135) --
+ * the energy every decay path has released per mass of its top nuclide between t_model and tstart, weighted for the adiabatic loss
+ * since (calc_energy_per_massoftopnuc_decaypath_withexpansion decay.cc:1086, the useexpansionfactor branch of calculate_decaychain
+ * decay.h:56), per cell the sequential sum over the paths (decay.cc:1052) plus initenergyq when the pellet set-up has both
+ * initial_packets_on and use_model_initial_energy, T_initial with its three clamps, T_e = T_J = T_R = T_initial, W = 1 --, kappagrey
+ * (calculate_cell_kappagrey grid.cc:1864-1926, the type a RUNTIME field) and the first step's grey depth and thickness flags
+ * (update_grid.cc:606-627). artis_amd_grid_update_initial then balances every cell with forced Saha from these arrays and the decay
+ * update's matter and makes the result the engine's FIRST cell state: no artis_amd_set_cellstate is needed before it. Builds without
+ * NLTE populations; the nebular family: ARTIS_ERR_UNSUPPORTED. Every output element has one writer, no float atomics: bitwise
+ * reproducible. The result block is allocated at the first artis_amd_initial_state. */
+#define ARTIS_GREY_FEGROUP_APPROX 0 /* RpktGreyType of constants.h:91, in its order */
+#define ARTIS_GREY_TANAKA2020 1
+#define ARTIS_GREY_JUST2022 2
+#define ARTIS_INITIAL_INSIDE 0         /* a cell's flags: which branch of grid.cc:1113-1128 it took ... */
+#define ARTIS_INITIAL_BELOW_MINTEMP 1
+#define ARTIS_INITIAL_ABOVE_MAXTEMP 2
+#define ARTIS_INITIAL_NONFINITE 3
+#define ARTIS_INITIAL_BRANCH_MASK 3
+#define ARTIS_INITIAL_KAPPA_INVALID 4  /* ... and this bit: its kappagrey is negative or not finite (the asserts of grid.cc:1923-1924) */
+typedef struct artis_initial_params {
+  int64_t struct_size;                    /* sizeof(artis_initial_params) */
+  double tstart;                          /* globals::timesteps[0].mid */
+  int32_t nts_first, num_grey_timesteps;  /* the step the flags are for */
+  double optical_depth_is_thick, optical_depth_is_thick_vpkt;
+  int32_t rpkt_grey_type;                 /* ARTIS_GREY_FEGROUP_APPROX / _TANAKA2020 / _JUST2022: RPKT_GREY_TYPE of artisoptions.h */
+  double mfegroup, mtot_input;            /* FEGROUP_APPROX */
+  const float *ffegrp;                    /* [npts_nonempty] FEGROUP_APPROX */
+  const float *initelectronfrac;          /* [npts_nonempty] TANAKA2020 */
+  const double *energy_vector;            /* NULL: the device forms it; else the host's [npaths], used as it is */
+} artis_initial_params;
+typedef struct artis_initial_result {
+  int64_t struct_size; /* sizeof(artis_initial_result) */
+  /* host arrays to fill; NULL: skip */
+  float *T_initial;          /* [npts_nonempty] */
+  double *endecay_per_mass;  /* [npts_nonempty] decayedenergy_per_mass of grid.cc:1107 (with initenergyq when the channel is on) */
+  float *kappagrey;          /* [npts_nonempty] */
+  float *grey_depth;         /* [npts_nonempty] */
+  int32_t *thick;            /* [npts_nonempty] ARTIS_CELL_* for the packets of step nts_first */
+  int32_t *flags;            /* [npts_nonempty] ARTIS_INITIAL_* */
+  double *energy_vector;     /* [npaths] as the device used it */
+  double *path_scale;        /* [npaths] what the rounding of a path's expansion sum is measured in (0 with a handed-in vector) */
+  double *path_x_dom;        /* [npaths] lambda x timediff of the term that sets it */
+  /* reported */
+  int64_t ncells_branch[4];  /* cells per ARTIS_INITIAL_INSIDE / _BELOW_MINTEMP / _ABOVE_MAXTEMP / _NONFINITE */
+  int64_t ncells_kappa_invalid;
+  int32_t first_nonfinite_cell; /* the lowest non-empty cell index with a non-finite temperature; -1: none */
+  int32_t npts_nonempty, npaths, rpkt_grey_type, nts_first, reserved;
+  double first_nonfinite_rho_tmin, first_nonfinite_endecay; /* of that cell (0 without one) */
+  double tstart;
+  double kernel_ms[2];       /* HIP-event time: [0] k_init_energy (or the vector's upload), [1] k_init_cells */
+} artis_initial_result;
+/* Needs artis_amd_decay_setup, artis_amd_deposition_setup, artis_amd_packet_init_setup and a valid artis_amd_decay_update at
+ * t_mid == tstart (its rho and elem_massfracs), else ARTIS_ERR_ARG with a text naming what is missing; also for tstart < t_model, an
+ * unknown grey type, TANAKA2020 with an initelectronfrac <= 0, FEGROUP_APPROX without ffegrp or with mtot_input <= 0. Synchronous. */
+int artis_amd_initial_state(artis_amd_engine *eng, const artis_initial_params *params, void *hip_stream);
+/* Copy the results of the last artis_amd_initial_state to the host (sizes in the reported fields even when every pointer is NULL). */
+int artis_amd_initial_state_download(artis_amd_engine *eng, artis_initial_result *out);
+/* artis_amd_grid_update for the first timestep: matter from the last artis_amd_decay_update (as artis_amd_grid_update_decayed),
+ * T_J = T_R = T_e = T_initial, W = 1, kappagrey and the flags of step ts_first->nts from the last artis_amd_initial_state, device to
+ * device. u->use_fit must be 0 and u->TJ / TR / W / Te / rho / elem_massfracs / elem_meanweight / thick / kappagrey NULL.
+ * u->clumpfactor is required while no cell state is resident; u->ffegrp NULL: zeros, as artis_amd_set_cellstate. The balance's
+ * "current" state is the reference's before its first update_grid: ground populations 0 (grid.cc:427) and every cell THICK
+ * (update_grid.cc:495-501: W == 1), whatever is resident. Works without a resident cell state; a refused balance leaves the engine
+ * as it was (without a previous state: without one). ARTIS_ERR_ARG unless the initial state and the decay update were made for
+ * ts_first->mid and ts_first->nts. */
+int artis_amd_grid_update_initial(artis_amd_engine *eng, const artis_grid_update *u, const artis_timestep *ts_first, void *hip_stream);
+
 /* ---- thermal balance of the thin cells -----------------------------------------------------
  * What the reference's grid update does for a cell the radiation-field fit has fitted, outside an LTE iteration, on the device: the
  * renormalisation of the photoionisation estimator (update_grid.cc:344-387), Gamma per ground population of every ion with a ground
